@@ -11,11 +11,17 @@ buffer (``ddq_step_pipelined_async``: bit-identical to sequential steps).  Workl
 configs[1] -- deepq Snake, batch 32, 4-frame 64x64 history, 30 000-slot HBM
 replay filled with synthetic Snake frames.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
 Prints ONE JSON line (rank 0).  ``value`` = minibatch updates/s summed over
-all ranks (each rank consumes its own minibatch per step: weak scaling).
+all ranks (each rank consumes its own minibatch per step: weak scaling);
+``ms_per_step`` = wall milliseconds per timed step.  A plain run sets up,
+warms up, times the K steps and prints that line.  ``--dump-outputs DIR``
+writes what the last timed step left (weights of both towers, gradient,
+optimizer state, the head's blobs) as DIR/<name>.npy.  ``--full`` adds every
+other leg (step-time distribution, per-kernel and roofline figures, gather
+stress, deepq16, frame sweep, messaging, CPU baseline, exchange paths).
 ``roofline``: dominant kernel's in-step time (its own dispatch start / stop
 events, hipExtLaunchKernel, in eager steps: ddq_profile_step) vs the peak of
 the arithmetic it runs (split-bf16 kernels:
@@ -770,6 +776,135 @@ def frame_sweep(B=256, frames=range(16, 129, 8), steps=60, warmup=10, rule="rmsp
             "f32_mfma_peak_TFLOPs": F32_MFMA_PEAK / 1e12, "frames": res}
 
 
+def step_figures(args, net, cfg, run, dt, B, S, local, rank, exchanged):
+    """--full: the measured step's other figures, after the timed steps:
+    step-time distribution, per-kernel in-step times and the roofline block."""
+    # step-time distribution: chunks of graph steps bracketed by HIP events on
+    # the ctx stream (no host sync inside a chunk)
+    dist_ms = None
+    if not args.eager and args.chunks > 0:
+        timer = dev_timer(net)
+        per = sorted(timer(lambda: run(args.chunk_steps), 1) / args.chunk_steps / 1e3
+                     for _ in range(args.chunks))
+        dist_ms = {"median": round(float(np.median(per)), 4),
+                   "p10": round(float(np.percentile(per, 10)), 4),
+                   "p90": round(float(np.percentile(per, 90)), 4),
+                   "chunks": args.chunks, "steps_per_chunk": args.chunk_steps}
+
+    # per-kernel device times: eager steps whose every kernel carries start /
+    # stop events of its own (hipExtLaunchKernel: the dispatch packet's
+    # timestamps -- what rocprofv3's kernel trace reads -- with no marker
+    # packets between the kernels), on the ctx stream the kernels run on;
+    # median over --profile-steps steps
+    pnet = net
+    if exchanged and args.exchange == "async":   # an async ctx runs async steps only
+        pnet = make_net(B, S, args.replay, local, rank)
+    pcfg = cfg if not (exchanged and args.exchange == "async") else \
+        pnet.step_cfg(args.rule, lr=1e-4, target_period=10, exchange="none", seed=1234,
+                      store_grads=not args.no_grad_store)
+    prof = {}
+    for _ in range(max(1, args.profile_steps)):
+        for name, us in pnet.profile_step(pcfg):
+            prof.setdefault(name, []).append(us)
+    avg = {k: float(np.median(v)) for k, v in prof.items()}
+    flops = kernel_flops(B, S)
+    dom = max((k for k in avg if k in flops), key=lambda k: avg[k])
+    dom_us = avg[dom]
+    # for reference: the same layer launched 100 times back to back on the same
+    # cache-warm input (not the roofline figure)
+    iso_us = pnet.time_layer(dom, 100) if dom.endswith("_fwd") and dom.startswith("conv") \
+        and not args.no_isolated else None
+    if pnet is not net:
+        pnet.close()
+    achieved = flops[dom] / (dom_us * 1e-6) / 1e12
+    # peak of the arithmetic the kernel runs (a fused kernel: its FLOPs over
+    # the ideal time of its parts)
+    dom_peak = flops[dom] / ideal_s(dom, B, S)
+    step_flops = net.step_flops()
+    step_rl = step_roofline(B, S, net.num_params)
+    traffic, traffic_src = pmc_traffic(dom, B, S)
+    return {
+        "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3),
+                     "peak": round(dom_peak / 1e12, 1), "unit": "TFLOP/s",
+                     "frac": round(achieved * 1e12 / dom_peak, 4),
+                     "arith": KERNEL_ARITH.get(dom, "f32"),
+                     "peak_basis": "algorithmic f32 FLOPs; peak = bf16 dense 2.5 PF/s over "
+                                   "the bf16 products per f32 product (split: 6, split3: "
+                                   "3; f32 MFMA: 157.3)",
+                     "vs_f32_mfma_peak": round(achieved * 1e12 / F32_MFMA_PEAK, 4),
+                     "traffic": traffic, "traffic_unit": "bytes/launch",
+                     "traffic_source": traffic_src,
+                     "kernel_us": round(dom_us, 3),
+                     "kernel_us_timing": "in-step: median over %d eager steps of the "
+                                         "kernel's own dispatch start / stop "
+                                         "(hipExtLaunchKernel events on the ctx stream)"
+                                         % max(1, args.profile_steps),
+                     "isolated_us": None if iso_us is None else round(iso_us, 3),
+                     "isolated_timing": "the same layer, 100 back-to-back launches on one "
+                                        "cache-warm input (not the roofline figure)",
+                     "step_tflops": round(step_flops / (dt / args.steps) / 1e12, 3),
+                     "step_ideal_us": step_rl["ideal_us"],
+                     "step_frac": round(step_rl["ideal_us"] * 1e-3 / (dt / args.steps * 1e3), 4),
+                     "step_frac_basis": "step_roofline(): MFMA kernels at their "
+                                        "arithmetic's peak + algorithmic HBM bytes"},
+        "kernels_us": {k: round(v, 2) for k, v in avg.items()},
+        "kernels_us_timing": "each kernel's own dispatch start / stop in eager steps "
+                             "(ddq_profile_step, hipExtLaunchKernel events); compare "
+                             "profiles/rNN_kernel_stats_step.csv (rocprofv3, graph replay)",
+        "kernel_roofline": kernel_roofline(avg, B, S, net.num_params),
+        "step_ms_distribution": dist_ms,
+    }
+
+
+def full_legs(args, net, cfg, B, S):
+    """--full, one GPU, rank 0: the legs beside the measured step."""
+    out = {}
+    if args.acting:
+        out["with_acting"] = acting_rate(net, cfg, S)
+    if not args.no_gather_stress:
+        out["gather_stress"] = gather_stress()
+    if not args.no_sweep:
+        out["deepq16"] = deepq16_line()
+        # C3 (BASELINE.json configs[2]): B = 256; the default line carries
+        # the reduced sweep 16 / 64 / 128, --sweep the reference's 16..128/8
+        out["frame_sweep"] = frame_sweep(frames=range(16, 129, 8) if args.sweep
+                                         else (16, 64, 128))
+    if not args.no_messaging:
+        out["messaging"] = messaging_costs()
+    if not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(B, S, seed=7)
+    if not args.no_exchange_paths and not args.force_exchange:
+        out["exchange_paths"] = exchange_paths(net, args.rule)
+    return out
+
+
+DUMP_BUDGET = 60 << 20         # bytes of array data per --dump-outputs (< 64 MB with headers)
+DUMP_BLOBS = ("Q_out", "P_out", "Q_sa", "P_sa", "target_Q_sa", "loss")
+
+
+def dump_outputs(net, path):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the Q and P weights, the step's gradient, the optimizer state and
+    the head's blobs -- as float32 <name>.npy under `path`.  Whole arrays while
+    they fit DUMP_BUDGET together; beyond that (frames above 64) every large
+    array is a fixed seed-0 sample of its elements, in index order."""
+    arrs = {"theta_q": net.get_flat(0), "theta_p": net.get_flat(1),
+            "grads": net.get_grads_flat(), "optimizer_state": net.optimizer_state()}
+    for name in DUMP_BLOBS:
+        arrs[name] = np.asarray(net.blob(name), np.float32)
+    budget = DUMP_BUDGET // 4
+    if sum(a.size for a in arrs.values()) > budget:
+        big = [k for k, a in arrs.items() if a.size > budget // len(arrs)]
+        cap = (budget - sum(a.size for k, a in arrs.items() if k not in big)) // len(big)
+        rng = np.random.default_rng(0)
+        for k in big:
+            idx = np.sort(rng.choice(arrs[k].size, cap, replace=False))
+            arrs[k] = arrs[k].ravel()[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float32))
+
+
 def main():
     # the JSON line is the only thing on stdout: C-level writes to fd 1 (e.g.
     # RCCL's version banner at communicator init) go to stderr
@@ -779,6 +914,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (weights, "
+                         "gradient, optimizer state, head blobs) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps also run every other leg: step-time "
+                         "distribution, per-kernel / roofline figures, gather stress, deepq16, "
+                         "frame sweep, messaging, CPU baseline, exchange paths (the --no-* "
+                         "options below drop single legs; --acting and --sweep add to them)")
     ap.add_argument("--frame", type=int, default=64)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--replay", type=int, default=30000)
@@ -826,6 +969,8 @@ def main():
                          "head (default: the next step's draw + gather ride on this step's "
                          "apply launch into a second minibatch buffer -- bit-identical results)")
     args = ap.parse_args()
+    if (args.acting or args.sweep) and not args.full:
+        ap.error("--acting and --sweep are legs of --full")
     args.pipeline = not args.no_pipeline
 
     from ddq import dist as ddist
@@ -883,7 +1028,9 @@ def main():
     args.pipeline = mode == "pipelined"
     args.no_overlap = not ov
     # the same command without the preheat: W warmup steps, then 20 timed steps
-    # on a chip fresh from idle (the measured context goes on from there)
+    # on a chip fresh from idle (the measured context goes on from there: these
+    # W + 20 steps are part of the state the timed steps start from, so they
+    # run in a plain run too)
     cold = None
     if args.preheat_ms > 0 and world == 1:
         run(args.warmup)
@@ -913,50 +1060,13 @@ def main():
     if heated is not None:
         heated[0].close()
 
-    # step-time distribution: chunks of graph steps bracketed by HIP events on
-    # the ctx stream (no host sync inside a chunk)
-    dist_ms = None
-    if not args.eager and args.chunks > 0:
-        timer = dev_timer(net)
-        per = sorted(timer(lambda: run(args.chunk_steps), 1) / args.chunk_steps / 1e3
-                     for _ in range(args.chunks))
-        dist_ms = {"median": round(float(np.median(per)), 4),
-                   "p10": round(float(np.percentile(per, 10)), 4),
-                   "p90": round(float(np.percentile(per, 90)), 4),
-                   "chunks": args.chunks, "steps_per_chunk": args.chunk_steps}
+    # the last timed step's results, read before a --full leg runs further steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(net, args.dump_outputs)
 
-    # per-kernel device times: eager steps whose every kernel carries start /
-    # stop events of its own (hipExtLaunchKernel: the dispatch packet's
-    # timestamps -- what rocprofv3's kernel trace reads -- with no marker
-    # packets between the kernels), on the ctx stream the kernels run on;
-    # median over --profile-steps steps
-    pnet = net
-    if exchanged and args.exchange == "async":   # an async ctx runs async steps only
-        pnet = make_net(B, S, args.replay, local, rank)
-    pcfg = cfg if not (exchanged and args.exchange == "async") else \
-        pnet.step_cfg(args.rule, lr=1e-4, target_period=10, exchange="none", seed=1234,
-                      store_grads=not args.no_grad_store)
-    prof = {}
-    for _ in range(max(1, args.profile_steps)):
-        for name, us in pnet.profile_step(pcfg):
-            prof.setdefault(name, []).append(us)
-    avg = {k: float(np.median(v)) for k, v in prof.items()}
-    flops = kernel_flops(B, S)
-    dom = max((k for k in avg if k in flops), key=lambda k: avg[k])
-    dom_us = avg[dom]
-    # for reference: the same layer launched 100 times back to back on the same
-    # cache-warm input (not the roofline figure)
-    iso_us = pnet.time_layer(dom, 100) if dom.endswith("_fwd") and dom.startswith("conv") \
-        and not args.no_isolated else None
-    if pnet is not net:
-        pnet.close()
-    achieved = flops[dom] / (dom_us * 1e-6) / 1e12
-    # peak of the arithmetic the kernel runs (a fused kernel: its FLOPs over
-    # the ideal time of its parts)
-    dom_peak = flops[dom] / ideal_s(dom, B, S)
-    step_flops = net.step_flops()
-    step_rl = step_roofline(B, S, net.num_params)
-    traffic, traffic_src = pmc_traffic(dom, B, S)
+    # --full: the step's other figures (every rank: exchanged steps are collective)
+    figures = step_figures(args, net, cfg, run, dt, B, S, local, rank, exchanged) \
+        if args.full else {}
     if rank == 0:
         out = {
             "metric": METRIC,
@@ -986,53 +1096,11 @@ def main():
                        "grad_store": "fc4 weight gradient stored" if not args.no_grad_store or exchanged
                                      else "fc4 weight gradient applied, not stored "
                                           "(DDQ_STEP_NO_GRAD_STORE)"},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3),
-                         "peak": round(dom_peak / 1e12, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved * 1e12 / dom_peak, 4),
-                         "arith": KERNEL_ARITH.get(dom, "f32"),
-                         "peak_basis": "algorithmic f32 FLOPs; peak = bf16 dense 2.5 PF/s over "
-                                       "the bf16 products per f32 product (split: 6, split3: "
-                                       "3; f32 MFMA: 157.3)",
-                         "vs_f32_mfma_peak": round(achieved * 1e12 / F32_MFMA_PEAK, 4),
-                         "traffic": traffic, "traffic_unit": "bytes/launch",
-                         "traffic_source": traffic_src,
-                         "kernel_us": round(dom_us, 3),
-                         "kernel_us_timing": "in-step: median over %d eager steps of the "
-                                             "kernel's own dispatch start / stop "
-                                             "(hipExtLaunchKernel events on the ctx stream)"
-                                             % max(1, args.profile_steps),
-                         "isolated_us": None if iso_us is None else round(iso_us, 3),
-                         "isolated_timing": "the same layer, 100 back-to-back launches on one "
-                                            "cache-warm input (not the roofline figure)",
-                         "step_tflops": round(step_flops / (dt / args.steps) / 1e12, 3),
-                         "step_ideal_us": step_rl["ideal_us"],
-                         "step_frac": round(step_rl["ideal_us"] * 1e-3 / (dt / args.steps * 1e3), 4),
-                         "step_frac_basis": "step_roofline(): MFMA kernels at their "
-                                            "arithmetic's peak + algorithmic HBM bytes"},
-            "kernels_us": {k: round(v, 2) for k, v in avg.items()},
-            "kernels_us_timing": "each kernel's own dispatch start / stop in eager steps "
-                                 "(ddq_profile_step, hipExtLaunchKernel events); compare "
-                                 "profiles/rNN_kernel_stats_step.csv (rocprofv3, graph replay)",
-            "kernel_roofline": kernel_roofline(avg, B, S, net.num_params),
-            "step_ms_distribution": dist_ms,
-            "final_loss": loss,
         }
-        if args.acting and world == 1:
-            out["with_acting"] = acting_rate(net, cfg, S)
-        if not args.no_gather_stress and world == 1:
-            out["gather_stress"] = gather_stress()
-        if not args.no_sweep and world == 1:
-            out["deepq16"] = deepq16_line()
-            # C3 (BASELINE.json configs[2]): B = 256; the default line carries
-            # the reduced sweep 16 / 64 / 128, --sweep the reference's 16..128/8
-            out["frame_sweep"] = frame_sweep(frames=range(16, 129, 8) if args.sweep
-                                             else (16, 64, 128))
-        if not args.no_messaging and world == 1:
-            out["messaging"] = messaging_costs()
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(B, S, seed=7)
-        if not args.no_exchange_paths and world == 1 and not args.force_exchange:
-            out["exchange_paths"] = exchange_paths(net, args.rule)
+        out.update(figures)
+        out["final_loss"] = loss
+        if args.full and world == 1:
+            out.update(full_legs(args, net, cfg, B, S))
         print(json.dumps(out), file=json_out, flush=True)
     if world > 1:
         dist.barrier()

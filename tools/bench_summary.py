@@ -4,9 +4,10 @@ import sys
 
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("bench", d["value"], d["ms_per_step"], d.get("step_ms_distribution"))
-print("roofline", {k: d["roofline"].get(k) for k in ("kernel", "frac", "kernel_us", "step_frac",
-                                                     "step_ideal_us", "traffic")})
-print("kernels", json.dumps(d["kernels_us"]))
+if "roofline" in d:     # the legs below: a bench.py --full line
+    print("roofline", {k: d["roofline"].get(k) for k in ("kernel", "frac", "kernel_us",
+                                                         "step_frac", "step_ideal_us", "traffic")})
+    print("kernels", json.dumps(d["kernels_us"]))
 for k, v in d.get("exchange_paths", {}).get("paths", {}).items():
     print("exchange", k, v["updates_per_s"], v["vs_exchange_free"], v["mode"])
 if "deepq16" in d:
