@@ -42,15 +42,27 @@ inline void ddq_launch(F kern, const dim3& grid, const dim3& block, uint32_t sme
 // ddq_debug_stamps / tools/gpu/stamps.py): lane 0 of a workgroup records the
 // 100 MHz real-time clock at a kernel's phase boundaries.  Empty otherwise.
 #ifdef DDQ_STAMPS
-constexpr int kStampSlots = 48, kStampBlocks = 512;
+constexpr int kStampSlots = 56, kStampBlocks = 512;
 extern __device__ uint64_t g_stamps[kStampBlocks * kStampSlots];
 #define DDQ_STAMP(slot)                                                        \
   do {                                                                         \
     if (threadIdx.x == 0 && blockIdx.x < kStampBlocks)                         \
       g_stamps[blockIdx.x * kStampSlots + (slot)] = wall_clock64();            \
   } while (0)
+// where the workgroup runs: XCC_ID (hardware register 20) << 32 | HW_ID
+// (register 4: cu_id bits 11:8, sh_id 12, se_id 15:13), read by thread 0;
+// bits 48.. the workgroup's waves, bit 62 marks the slot written
+#define DDQ_STAMP_HWID(slot)                                                   \
+  do {                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < kStampBlocks)                         \
+      g_stamps[blockIdx.x * kStampSlots + (slot)] =                            \
+          ((uint64_t)(__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 15) << 32) | \
+          (uint64_t)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |                \
+          ((uint64_t)(blockDim.x >> 6) << 48) | (1ull << 62);                  \
+  } while (0)
 #else
 #define DDQ_STAMP(slot) do { } while (0)
+#define DDQ_STAMP_HWID(slot) do { } while (0)
 #endif
 
 constexpr int kWave = 64;          // CDNA wavefront

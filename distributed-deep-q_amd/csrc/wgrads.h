@@ -96,6 +96,10 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
   const int cb = ts / KS, ky = ts % KS;
   const int r0 = g * a.RPG;
   const int r1 = min(a.B * H, r0 + a.RPG);
+  // stamp slots (DDQ_STAMPS builds): conv2's unit 48..50, conv3's 51..53 --
+  // body entry, wave 0's last row done, exit
+  [[maybe_unused]] constexpr int SB = CIN == 32 ? 48 : 51;
+  DDQ_STAMP(SB);
 
   // zero the pixels rows never write: the input halo / tail, the dconv tail
   {
@@ -367,6 +371,7 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
       compute();
     }
   }
+  DDQ_STAMP(SB + 1);
 
   // ---- sum the four waves' tiles in fixed order, store the group slab ----
   float* red = reinterpret_cast<float*>(smem);        // [4 waves][16 r][64 lanes]
@@ -402,12 +407,20 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
     __syncthreads();
     if (threadIdx.x < 32) {
       const int co = threadIdx.x, c8 = co >> 3, j = co & 7;
+      // all 64 values (wave, then lane order) first, then the adds in that
+      // order: as one loop every add waited for its own LDS read, and the
+      // ky == 0 workgroups ended ~4.6 us after the others -- the launch's
+      // last (profiles/r07_pair_stamps_before.txt)
+      float x[64];
+#pragma unroll
+      for (int i = 0; i < 64; ++i) x[i] = red[((i >> 4) * 64 + c8 + 4 * (i & 15)) * 8 + j];
       float v = 0.f;
-      for (int ww = 0; ww < 4; ++ww)
-        for (int l = c8; l < 64; l += 4) v += red[(ww * 64 + l) * 8 + j];
+#pragma unroll
+      for (int i = 0; i < 64; ++i) v += x[i];
       wt_store(srs, sbase + (uint32_t)((co * a.NP + KC) * 4), v);
     }
   }
+  DDQ_STAMP(SB + 2);
 }
 
 template <int CIN, int PAD>
@@ -419,15 +432,21 @@ inline size_t wgrads_smem_bytes(int W) {
 // Two weight gradients in one launch (conv2's and conv3's: both need only the
 // data gradient conv3's data-gradient launch wrote): blocks [0, n0) are the
 // first's, the rest the second's -- one kernel boundary fewer, and the second's
-// workgroups fill the CUs the first's tail leaves idle.  n0 is a multiple of 8,
-// so each keeps its XCD-aware decode.  LDS: the larger of the two.  Two waves
-// per SIMD (<= 256 registers): the other wave's MFMAs cover each wave's row
-// staging and LDS round trips.
+// workgroups share the CUs with the first's.  n0 is a multiple of 8, so each
+// keeps its XCD-aware decode.  LDS: the larger of the two.  <= 256 registers,
+// so two workgroups fit a CU (two waves per SIMD, the other wave's MFMAs over
+// each wave's row staging and LDS round trips) -- but only while both are
+// there: at 64 x 64, B = 32 every CU holds one conv2 workgroup and (224 of
+// 256) one conv3 workgroup, conv3's end at about half the launch and nothing
+// takes their slots, so the SIMDs hold two waves for 44 % of the CUs' time,
+// one for 37 % (profiles/r07_pair_stamps_before.txt; DESIGN section 6 for the
+// eight-lane form that was measured against this and not kept).
 template <int CIN0, int COUT0, int KS0, int PAD0, int WMAX0, int DSRC0, int CIN1, int COUT1,
           int KS1, int PAD1, int WMAX1, int DSRC1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrads_pair_kernel(
     const WgradSArgs a0, const WgradSArgs a1, int n0) {
   extern __shared__ __attribute__((aligned(16))) char sm_wgp[];
+  DDQ_STAMP_HWID(54);
   if ((int)blockIdx.x < n0)
     wgrads_body<CIN0, COUT0, KS0, PAD0, WMAX0, DSRC0>(a0, sm_wgp, blockIdx.x);
   else

@@ -18,7 +18,7 @@ S = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 mode = sys.argv[4] if len(sys.argv) > 4 else "fb"
-SLOTS, BLOCKS = 48, 512
+SLOTS, BLOCKS = 56, 512
 
 net = ddq.DeepQNet(batch=B, frame=S)
 rng = np.random.default_rng(0)
@@ -74,10 +74,67 @@ for r, t in enumerate(runs):
         print("run %d slots %d+: %d blocks, span %.2f us; slot: median since own start / last "
               "since launch start (us): %s" % (r, lo, len(tt), (tt[:, used].max() - t0) * 10 / 1000,
                                             " ".join("%d:%.2f/%.2f" % (k, a, b) for k, (a, b) in rel.items())))
+# the conv2 + conv3 weight-gradient pair (wgrads.h): per unit kind (conv2's
+# slots 48..50, conv3's 51..53: entry, wave 0's last row done, exit) the times
+# since the launch's first entry, and from slot 54 (the hardware id) how the
+# units share the CUs and how many waves a SIMD holds over the launch
+for r, t in enumerate(runs):
+    u = t.astype(np.uint64)
+    kinds = [(name, lo, np.nonzero(t[:, lo] > 0)[0]) for name, lo in (("conv2", 48), ("conv3", 51))]
+    if not any(len(b) for _, _, b in kinds):
+        continue
+    t0 = min(t[b, lo].min() for _, lo, b in kinds if len(b))
+    t1 = max(t[b, lo + 2].max() for _, lo, b in kinds if len(b))
+    us = lambda v: (v - t0) * 10 / 1000
+    print("pair run %d: launch span %.2f us" % (r, us(t1)))
+    for name, lo, b in kinds:
+        if not len(b):
+            continue
+        e, d, x = us(t[b, lo]), us(t[b, lo + 1]), us(t[b, lo + 2])
+        print("  %s: %d units; entry median %.2f max %.2f; rows done median %.2f max %.2f; "
+              "exit min %.2f median %.2f max %.2f; own length median %.2f us"
+              % (name, len(b), np.median(e), e.max(), np.median(d), d.max(), x.min(),
+                 np.median(x), x.max(), np.median(x - e)))
+    hw = u[:, 54]
+    has = np.nonzero((hw >> np.uint64(62)) & np.uint64(1))[0]
+    if not len(has):
+        continue
+    # CU key: (xcc, se, sh, cu); a workgroup's waves spread over the CU's 4 SIMDs
+    key = {int(b): (int(hw[b] >> np.uint64(32)) & 15, int(hw[b] >> np.uint64(13)) & 7,
+                    int(hw[b] >> np.uint64(12)) & 1, int(hw[b] >> np.uint64(8)) & 15) for b in has}
+    waves = {int(b): (int(hw[b] >> np.uint64(48)) & 63) for b in has}
+    c2 = set(int(b) for b in kinds[0][2])
+    per_cu = {}
+    for b, k in key.items():
+        per_cu.setdefault(k, []).append(b)
+    h2 = np.bincount([sum(b in c2 for b in bl) for bl in per_cu.values()])
+    ha = np.bincount([len(bl) for bl in per_cu.values()])
+    print("  CUs used %d; CUs by conv2 units held: %s; by workgroups held: %s" % (
+        len(per_cu), " ".join("%d:%d" % (i, n) for i, n in enumerate(h2) if n),
+        " ".join("%d:%d" % (i, n) for i, n in enumerate(ha) if n)))
+    # CU-time by resident waves per SIMD (workgroup waves / 4), entry to exit
+    share = {}
+    for bl in per_cu.values():
+        ev = []
+        for b in bl:
+            ent = min(t[b, lo] for lo in (48, 51) if t[b, lo] > 0)
+            ext = max(t[b, lo + 2] for lo in (48, 51) if t[b, lo] > 0)
+            ev += [(ent, waves[b] / 4.0), (ext, -waves[b] / 4.0)]
+        ev.sort()
+        cur, last = 0.0, t0
+        for when, dw in ev:
+            share[cur] = share.get(cur, 0) + (when - last)
+            cur, last = cur + dw, when
+        share[0.0] = share.get(0.0, 0) + (t1 - last)
+    tot = float(sum(share.values()))
+    print("  used CUs' time by waves per SIMD: %s" % " ".join(
+        "%g:%.1f%%" % (k, 100 * v / tot) for k, v in sorted(share.items())))
 # the meeting tiles' arrival skew: per K4 block (conv2 24.., conv3 32..) the
 # pre-meeting stamp since the launch's start, slowest first
 for lo, name in ((24, "conv2"), (32, "conv3")):
     t = runs[-1]
+    if not (t[:, lo] > 0).any():
+        continue
     t0 = t[t[:, 16 if lo == 0 else 24] > 0][:, 24].min() if (t[:, 24] > 0).any() else 0
     sel = np.nonzero((t[:, lo] > 0) & (t[:, lo + 3] > 0))[0]
     arr = sorted(((t[b, lo + 3] - t0) * 10 / 1000, b, [(t[b, lo + k] - t[b, lo]) * 10 / 1000 for k in range(1, 6)])
