@@ -8,8 +8,9 @@
 // runs on a machine without a GPU.  It computes what the HIP library computes
 // -- the deepq network of models/deepq/train_val.prototxt:38-483 (both
 // towers, Q(s,a), the Bellman target 0.85 max_a P + r, the Euclidean loss, the
-// Q backward), the replay ring of replay.py and the param-server update rules
-// of server.py:49-124 -- with plain C++ loops over NCHW fp32 tensors,
+// Q backward), the replay ring of replay.py, the Snake actor of expgain.py +
+// gamesim/SnakeGame.py (ddq_actor_*) and the param-server update rules of
+// server.py:49-124 -- with plain C++ loops over NCHW fp32 tensors,
 // accumulating every dot product in double and rounding once per layer
 // output (so it is no less exact than the GPU's fp32-exact split products).
 // The update rules round exactly as the HIP library's apply_rule (built with
@@ -91,6 +92,13 @@ struct ddq_ctx {
   std::vector<int16_t> r_reward;
   int64_t head = 0, valid = 0, capacity = 0;
   int64_t steps = 0;
+  // Snake actor (ddq_actor_*): 4-board history (oldest first), the start board,
+  // the zoom maps and the RNG stream position
+  bool actor = false;
+  int8_t a_boards[4][100], a_init[100];
+  std::vector<int32_t> a_row, a_col;
+  uint64_t a_seed = 0, a_draws = 0;
+  int64_t a_steps = 0, a_games = 0, a_reward = 0;
   std::string err;
 };
 
@@ -786,6 +794,168 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
     actions[b] = best;
   }
   c->tw[0] = std::move(keep);
+  return DDQ_OK;
+}
+
+// ---- Snake actor (expgain.py:30-111 + gamesim/SnakeGame.py on this ctx) ----
+}  // extern "C"
+
+namespace {
+
+uint64_t mix64(uint64_t x) {   // splitmix64
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// draw k of the actor's stream: splitmix64(seed ^ splitmix64(k))
+uint64_t actor_next(ddq_ctx* c) { return mix64(c->a_seed ^ mix64(c->a_draws++)); }
+
+uint64_t actor_randrange(ddq_ctx* c, uint64_t n) {   // high 64 bits of r * n
+  return (uint64_t)(((unsigned __int128)actor_next(c) * n) >> 64);
+}
+
+// expgain.epsilon (expgain.py:55-60)
+double actor_eps(int64_t it) {
+  if (it > 50000) return 0.1;
+  return 0.1 + (1.0 - 0.1) * (double)std::max<int64_t>(50000 - it, 0) / 50000.0;
+}
+
+struct Cell { int x, y; };
+
+// SnakeGame.set_state: the body, head first; false when the codes are not 0..k-1
+bool snake_body(const int8_t* b, std::vector<Cell>* body) {
+  int k = 0;
+  for (int i = 0; i < 100; ++i) {
+    if (b[i] < -2) return false;
+    k += b[i] >= 0;
+  }
+  body->assign(k, Cell{-1, -1});
+  for (int i = 0; i < 100; ++i)
+    if (b[i] >= 0) {
+      if (b[i] >= k || (*body)[b[i]].x >= 0) return false;
+      (*body)[b[i]] = Cell{i / 10, i % 10};
+    }
+  return true;
+}
+
+// the preprocessor: gray_scale, then the nearest-neighbour zoom through the maps
+void actor_render(const ddq_ctx* c, std::vector<uint8_t>* out) {
+  const int S = c->S;
+  out->resize((size_t)kC * S * S);
+  for (int f = 0; f < kC; ++f)
+    for (int i = 0; i < S; ++i)
+      for (int j = 0; j < S; ++j) {
+        const int v = c->a_boards[f][c->a_row[i] * 10 + c->a_col[j]];
+        (*out)[((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
+      }
+}
+
+// one generate_experience (expgain.py:82-111)
+int actor_step(ddq_ctx* c, double eps) {
+  std::vector<uint8_t> frames;
+  actor_render(c, &frames);
+  int32_t act = 0;
+  // ExpGain.select_action: the coin first; the net is asked only when greedy
+  if ((double)(actor_next(c) >> 11) * 0x1.0p-53 < eps) {
+    act = (int32_t)actor_randrange(c, kA);
+  } else {
+    const int rc = ddq_select_action(c, frames.data(), 1, &act);
+    if (rc != DDQ_OK) return rc;
+  }
+  // SnakeGame.cpu_play on the newest board
+  const int8_t* cur = c->a_boards[3];
+  std::vector<Cell> body;
+  snake_body(cur, &body);
+  const int hdx = body[0].x - body[1].x, hdy = body[0].y - body[1].y;
+  static const int step[4][2] = {{0, 1}, {-1, 0}, {0, -1}, {1, 0}};   // w a s d
+  int dx = step[act][0], dy = step[act][1];
+  if (dx == -hdx && dy == -hdy) { dx = hdx; dy = hdy; }
+  const Cell to{body[0].x + dx, body[0].y + dy};
+  bool over = to.x < 0 || to.x >= 10 || to.y < 0 || to.y >= 10;
+  for (const Cell& b : body) over = over || (b.x == to.x && b.y == to.y);
+  int reward = -1;
+  int8_t next[100];
+  if (!over) {
+    const bool eat = cur[to.x * 10 + to.y] == -2;
+    body.insert(body.begin(), to);
+    if (!eat) body.pop_back();
+    for (int i = 0; i < 100; ++i) next[i] = cur[i] == -2 ? -2 : -1;
+    for (size_t k = 0; k < body.size(); ++k) next[body[k].x * 10 + body[k].y] = (int8_t)k;
+    reward = eat ? 1 : 0;
+    if (eat) {   // _add_apple: empty cells x-major then y
+      std::vector<int> empty;
+      for (int i = 0; i < 100; ++i)
+        if (next[i] == -1) empty.push_back(i);
+      if (!empty.empty()) next[empty[actor_randrange(c, empty.size())]] = -2;
+    }
+  }
+  if (over) {
+    const int rc = ddq_replay_add(c, act, reward, nullptr);
+    if (rc != DDQ_OK) return rc;
+    for (auto& b : c->a_boards) memcpy(b, c->a_init, 100);   // reset_game
+  } else {
+    memmove(c->a_boards[0], c->a_boards[1], 300);
+    memcpy(c->a_boards[3], next, 100);
+    actor_render(c, &frames);
+    const int rc = ddq_replay_add(c, act, reward, frames.data());
+    if (rc != DDQ_OK) return rc;
+  }
+  c->a_steps += 1;
+  c->a_games += over;
+  c->a_reward += reward;
+  return DDQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_map,
+                     const int32_t* col_map, uint64_t seed) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!init_board || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
+  for (int i = 0; i < c->S; ++i)
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+  std::vector<Cell> body;
+  if (!snake_body(init_board, &body) || body.size() < 2)
+    return fail(c, DDQ_EINVAL, "init_board: snake cells must be the codes 0..k-1, k >= 2");
+  if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
+    return fail(c, DDQ_EINVAL, "init_board: head and neck are not neighbours");
+  if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  memcpy(c->a_init, init_board, 100);
+  for (auto& b : c->a_boards) memcpy(b, init_board, 100);
+  c->a_row.assign(row_map, row_map + c->S);
+  c->a_col.assign(col_map, col_map + c->S);
+  c->a_seed = seed;
+  c->a_draws = 0;
+  c->a_steps = c->a_games = c->a_reward = 0;
+  c->actor = true;
+  return DDQ_OK;
+}
+
+int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  if (nsteps < 1) return fail(c, DDQ_EINVAL, "nsteps must be >= 1 (got %d)", nsteps);
+  const double eps = actor_eps(iter_num);
+  for (int i = 0; i < nsteps; ++i) {
+    const int rc = actor_step(c, eps);
+    if (rc != DDQ_OK) return rc;
+  }
+  return DDQ_OK;
+}
+
+int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  if (boards) memcpy(boards, c->a_boards, 400);
+  if (stats) {
+    stats[0] = c->a_steps; stats[1] = c->a_games; stats[2] = c->a_reward;
+    stats[3] = (int64_t)c->a_draws;
+  }
   return DDQ_OK;
 }
 

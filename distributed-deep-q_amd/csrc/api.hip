@@ -3,6 +3,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +53,11 @@ struct ddq_ctx {
   float *act_h4 = nullptr, *act_part = nullptr, *act_q = nullptr;
   __bf16 *act_p1s = nullptr, *act_p2s = nullptr;
   int32_t* act_out = nullptr;
+  // device-resident actor (ddq_actor_create): its state, zoom maps and NHWC input
+  ActorState* a_state = nullptr;
+  uint8_t* a_maps = nullptr;
+  float* a_in = nullptr;
+  bool actor = false;
   // index log (ddq_index_log_enable)
   int32_t* log_buf = nullptr;
   int64_t log_buf_cap = 0;
@@ -970,6 +976,109 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
                         c->act_out, c->act_p1s, c->act_p2s, c->stream));
   HIP_TRY(c, hipMemcpyAsync(actions, c->act_out, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return DDQ_OK;
+}
+
+// ---------------- device-resident actor ----------------
+// expgain.epsilon (expgain.py:55-60) in double, same operation order
+static double actor_epsilon(int64_t it) {
+  const double lo = 0.1, hi = 1.0, limit = 50000.0;
+  if (it > 50000) return lo;
+  const int64_t left = std::max<int64_t>(50000 - it, 0);
+  return lo + (hi - lo) * (double)left / limit;
+}
+
+// init_board: snake cells are exactly the codes 0..k-1 (k >= 2), head and neck
+// neighbours; every other cell empty (-1) or apple (-2)
+static const char* actor_board_error(const int8_t* b) {
+  int at[100];
+  int k = 0;
+  for (int i = 0; i < 100; ++i) at[i] = -1;
+  for (int c = 0; c < 100; ++c) {
+    const int v = b[c];
+    if (v < -2 || v >= 100) return "board code out of range";
+    if (v >= 0) {
+      if (at[v] >= 0) return "snake code used twice";
+      at[v] = c;
+      ++k;
+    }
+  }
+  if (k < 2) return "snake shorter than 2 cells";
+  for (int i = 0; i < k; ++i)
+    if (at[i] < 0) return "snake codes are not 0..k-1";
+  const int dx = at[0] / 10 - at[1] / 10, dy = at[0] % 10 - at[1] % 10;
+  if (std::abs(dx) + std::abs(dy) != 1) return "head and neck are not neighbours";
+  return nullptr;
+}
+
+static ActorEnv actor_env(const ddq_ctx* c) {
+  ActorEnv e{};
+  e.state = c->a_state; e.maps = c->a_maps; e.actor_in = c->a_in; e.S = c->nb.S;
+  e.r_state = c->r_state; e.r_action = c->r_action; e.r_reward = c->r_reward;
+  e.r_nonterm = c->r_nonterm; e.meta = c->r_meta;
+  return e;
+}
+
+int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_map,
+                     const int32_t* col_map, uint64_t seed) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!init_board || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
+  const int S = c->nb.S;
+  std::vector<uint8_t> maps(2 * (size_t)S);
+  for (int i = 0; i < S; ++i) {
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+    maps[i] = (uint8_t)row_map[i];
+    maps[S + i] = (uint8_t)col_map[i];
+  }
+  if (const char* why = actor_board_error(init_board))
+    return fail(c, DDQ_EINVAL, "init_board: %s", why);
+  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  TRY(set_dev(c));
+  if (!c->a_state) TRY(dalloc(c, &c->a_state, 1));
+  if (!c->a_maps) TRY(dalloc(c, &c->a_maps, maps.size()));
+  if (!c->a_in) TRY(dalloc(c, &c->a_in, (size_t)S * S * 4));
+  ActorState st{};
+  st.seed = seed;
+  for (int f = 0; f < 5; ++f) memcpy(st.boards + f * 100, init_board, 100);
+  HIP_TRY(c, hipMemcpyAsync(c->a_state, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, scopy(c, c->a_maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, launch_actor_env(actor_env(c), c->act_q, 0, 0, c->stream));   // render only
+  c->actor = true;
+  return DDQ_OK;
+}
+
+int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  if (nsteps < 1) return fail(c, DDQ_EINVAL, "nsteps must be >= 1 (got %d)", nsteps);
+  TRY(set_dev(c));
+  // explore iff random() = (r >> 11) * 2^-53 < epsilon, i.e. (r >> 11) < ceil(epsilon * 2^53)
+  const uint64_t thresh = (uint64_t)std::ceil(actor_epsilon(iter_num) * 9007199254740992.0);
+  const ActorEnv e = actor_env(c);
+  for (int i = 0; i < nsteps; ++i) {
+    // the forward of ddq_select_action with one state, on the actor's own input
+    HIP_TRY(c, launch_act(c->nb, c->a_in, 1, c->act_p3, c->act_h4, c->act_part, c->act_q,
+                          nullptr, c->act_p1s, c->act_p2s, c->stream));
+    HIP_TRY(c, launch_actor_env(e, c->act_q, thresh, 1, c->stream));
+  }
+  // host mirror of the ring: one transition per step, as ddq_replay_add
+  c->head = (c->head + nsteps) % c->capacity;
+  c->valid = std::min(c->capacity, c->valid + nsteps);
+  return DDQ_OK;
+}
+
+int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  TRY(set_dev(c));
+  ActorState st;
+  HIP_TRY(c, scopy(c, &st, c->a_state, sizeof(st), hipMemcpyDeviceToHost));
+  if (boards) memcpy(boards, st.boards, 400);
+  if (stats) {
+    stats[0] = st.steps; stats[1] = st.games; stats[2] = st.reward_sum;
+    stats[3] = (int64_t)st.draws;
+  }
   return DDQ_OK;
 }
 

@@ -214,6 +214,32 @@ hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, in
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
                       __bf16* pool2s, hipStream_t s);
+// Device-resident Snake actor (actor.h).  boards: the 4-frame history of 10x10
+// board codes [x*10+y] (SnakeGame.encode_state), oldest first, then init_board;
+// draws: position in the actor's RNG stream splitmix64(seed ^ splitmix64(k)).
+struct ActorState {
+  uint64_t seed, draws;
+  int64_t steps, games, reward_sum;
+  int8_t boards[5 * 100];
+  int8_t pad[4];
+};
+struct ActorEnv {
+  ActorState* state;
+  const uint8_t* maps;              // row_map[S] then col_map[S], entries in [0,10)
+  float* actor_in;                  // the state as f32 NHWC (S,S,4): the forward's input
+  int S;
+  uint8_t* r_state;
+  uint8_t* r_action;
+  int16_t* r_reward;
+  uint8_t* r_nonterm;
+  ReplayMeta* meta;
+};
+// One workgroup: (play != 0) epsilon-greedy action from q[0..4) and the coin
+// against thresh = ceil(epsilon * 2^53), one game step, the transition into
+// ring slot meta->head, head / valid advanced; then the render of the next
+// state into that slot (not after a game over) and into actor_in.
+hipError_t launch_actor_env(const ActorEnv& e, const float* q, uint64_t thresh, int play,
+                            hipStream_t s);
 // large-batch device draw (bitmap claim + ordered compaction) into idx[0..n)
 // and the Caffe-layout (n,4,S,S) f32 gather of replay.py:167-183
 hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t seed,

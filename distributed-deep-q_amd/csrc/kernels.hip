@@ -2308,3 +2308,6 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
 }
 
 }  // namespace ddq
+
+// the device-resident actor's environment step (after launch_act's forward)
+#include "actor.h"

@@ -3,5 +3,6 @@ worker/param-server hot path).  Compute lives in libddq_hip.so (hand-written HIP
 gfx950); this package mirrors the reference's Python operator surface."""
 from ._lib import DDQError  # noqa: F401
 from .net import DeepQNet, GAMMA, NUM_ACTIONS, NFRAME  # noqa: F401
+from .actor import ActorRng, DeviceActor, zoom_maps  # noqa: F401
 
 __version__ = "0.1.0"

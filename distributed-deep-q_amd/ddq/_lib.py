@@ -110,6 +110,9 @@ _SIGS = {
     "ddq_read_blob": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _i64]),
     "ddq_read_pool_mask": (ctypes.c_int, [_P, _i32, _P, _i64]),
     "ddq_select_action": (ctypes.c_int, [_P, _P, _i32, _P]),
+    "ddq_actor_create": (ctypes.c_int, [_P, _P, _P, _P, _u64]),
+    "ddq_actor_step_async": (ctypes.c_int, [_P, _i32, _i64]),
+    "ddq_actor_read": (ctypes.c_int, [_P, _P, _P]),
     "ddq_apply": (ctypes.c_int, [_P, ctypes.POINTER(UpdateCfg)]),
     "ddq_apply_async": (ctypes.c_int, [_P, ctypes.POINTER(UpdateCfg)]),
     "ddq_reset_optimizer": (ctypes.c_int, [_P]),

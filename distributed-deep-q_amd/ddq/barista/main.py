@@ -7,15 +7,22 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
     python -m ddq.barista.main <train_val.prototxt> <model.npz|none>
         [--port 50001] [--driver 127.0.0.1:5500|None] [--dataset replay-dataset.hdf5]
         [--dset-size 1000] [--overwrite] [--debug] [--initial-replay 20000]
+        [--device-actor [--actor-seed N]]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
 step on the host through the CPU twin libddq_cpu.so (main.py:128,149-151, the
 reference's Caffe CPU mode: BASELINE configs[0]).
+
+``--device-actor`` (off by default) replaces the host ``ExpGain`` by
+``ddq.actor.DeviceActor``: the game, the preprocessing, the ε-greedy choice and
+the replay add run inside the net's context (ddq_actor_step_async), so
+``generate_experience`` only enqueues.
 """
 from __future__ import annotations
 
 import argparse
 import os
+import random
 import socket
 import time
 
@@ -80,6 +87,10 @@ def get_args(argv=None):
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("--initial-replay", type=int, default=20000)
     ap.add_argument("--max-requests", type=int, default=0, help="exit after N requests (tests)")
+    ap.add_argument("--device-actor", dest="device_actor", action="store_true",
+                    help="act on the device (ddq.actor.DeviceActor) instead of the host ExpGain")
+    ap.add_argument("--actor-seed", dest="actor_seed", type=int, default=None,
+                    help="seed of the device actor's random stream (default: random)")
     args = ap.parse_args(argv)
     if args.driver == "None":
         args.driver = None
@@ -94,6 +105,13 @@ def build_worker(args):
     net.add_dataset(replay)
     game = SnakeGame()
     pre = eg.generate_preprocessor(net.state.shape[2:], gray_scale)
+    if getattr(args, "device_actor", False):
+        from ..actor import DeviceActor
+        seed = args.actor_seed if args.actor_seed is not None else random.getrandbits(64)
+        exp_gain = DeviceActor(net, game.encode_state(), seed, preprocessor=pre)
+        if args.overwrite:                              # main.py:176-178
+            exp_gain.fill(min(args.initial_replay, args.dset_size))
+        return net, replay, exp_gain
     exp_gain = eg.ExpGain(net, ["w", "a", "s", "d"], pre, game.cpu_play, replay,
                           game.encode_state())
     if args.overwrite:                                  # main.py:176-178

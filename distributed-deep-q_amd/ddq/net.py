@@ -217,6 +217,36 @@ class DeepQNet:
         self._check(self.lib.ddq_select_action(self.ctx, ptr(s), s.shape[0], ptr(out)))
         return out
 
+    # ------------------------------------------------------------------- actor
+    def actor_create(self, init_board, row_map, col_map, seed):
+        """Device-resident Snake actor on this ctx's ring (ddq_actor_create):
+        ``init_board`` (10,10) board codes as ``SnakeGame.encode_state``,
+        ``row_map`` / ``col_map`` the zoom maps (``ddq.actor.zoom_maps``)."""
+        b = np.asarray(init_board)
+        if b.size != 100:
+            raise ValueError("init_board must have 100 cells, got %d" % b.size)
+        if b.min() < -128 or b.max() > 127:
+            raise ValueError("init_board codes must fit int8")
+        b = np.ascontiguousarray(b, np.int8)
+        rm = np.ascontiguousarray(row_map, np.int32).ravel()
+        cm = np.ascontiguousarray(col_map, np.int32).ravel()
+        if rm.size != self.frame or cm.size != self.frame:
+            raise ValueError("row_map / col_map must have %d entries" % self.frame)
+        self._check(self.lib.ddq_actor_create(self.ctx, ptr(b), ptr(rm), ptr(cm),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def actor_step(self, nsteps, iter_num):
+        """nsteps x generate_experience(iter_num) on the device; enqueued, no sync."""
+        self._check(self.lib.ddq_actor_step_async(self.ctx, int(nsteps), int(iter_num)))
+
+    def actor_read(self):
+        """Synchronise; (boards (4,10,10) int8 oldest first, stats int64[4]:
+        steps, games ended, sum of rewards, RNG draws)."""
+        boards = np.empty((NFRAME, 10, 10), np.int8)
+        stats = np.empty(4, np.int64)
+        self._check(self.lib.ddq_actor_read(self.ctx, ptr(boards), ptr(stats)))
+        return boards, stats
+
     # ------------------------------------------------------------------- apply
     def apply(self, rule="rmsprop", lr=1e-4, decay=0.9, eps=1e-8, momentum=0.9,
               weight_decay=0.0005):

@@ -39,7 +39,9 @@ extern "C" {
                               small-map step's spin timeout as DDQ_ESTATE.
                               6: DDQ_STEP_REPEAT_CONV2_FWD removed (flag 2 is refused);
                               a timed-out step applies nothing; ddq_inject_fault,
-                              ddq_small_path */
+                              ddq_small_path.  ABI 6 later gained the device actor
+                              (ddq_actor_create, ddq_actor_step_async, ddq_actor_read):
+                              new symbols only, nothing else changed */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -284,6 +286,35 @@ int ddq_read_pool_mask(ddq_ctx* ctx, int32_t layer, uint8_t* dst, int64_t n);
 /* select_action (baristanet.py:142-146) for n states (n <= B, uint8 C,H,W):
  * argmax_a Q(s,a), first max wins.  Does not touch the bound minibatch. */
 int ddq_select_action(ddq_ctx* ctx, const uint8_t* states, int32_t n, int32_t* actions);
+
+/* ---------------- device-resident actor (expgain.py, gamesim/SnakeGame.py) -- */
+/* The worker's "act once, add the transition" (main.py:61-103) without the
+ * host in it: one actor per ctx = one Snake game + the ctx's ring + its Q tower
+ * (a ring holds one trajectory: sample_direct takes s' from slot idx+1).
+ * Random numbers: draw k (k = 0, 1, ...) of an actor is
+ * r_k = splitmix64(seed ^ splitmix64(k)); random() = (r >> 11) * 2^-53,
+ * randrange(n) = high 64 bits of r * n, choice(seq) = seq[randrange(len)];
+ * one draw each, in program order: coin, action when exploring, apple when
+ * eaten (ddq.actor.ActorRng is the same stream on the host).  Actions are
+ * the reference's ["w","a","s","d"] = 0..3; the stored action is that index. */
+/* ExpGain.__init__ / reset_game (expgain.py:30-66) on the device.
+ * init_board: 100 int8 board codes [x*10+y] as SnakeGame.encode_state writes
+ * them (-1 empty, -2 apple, k = k-th cell from the head); the start of every
+ * game (the reference resets to the same init_state, apple included).
+ * row_map/col_map: S entries each in [0,10): frame pixel (i,j) shows board
+ * cell (row_map[i], col_map[j]) -- the nearest-neighbour zoom of
+ * expgain.py:12-18, computed by the caller from its own preprocessor.
+ * Needs a replay ring (DDQ_ESTATE otherwise).  Calling it again resets. */
+int ddq_actor_create(ddq_ctx* ctx, const int8_t* init_board, const int32_t* row_map,
+                     const int32_t* col_map, uint64_t seed);
+/* nsteps x generate_experience(iter_num) (expgain.py:82-111): Q forward of the
+ * current 4-frame state, epsilon-greedy action at epsilon(iter_num), one game step,
+ * add_experience into the ring.  Enqueued on the ctx stream, no sync; the
+ * ring's head / valid (ddq_replay_info) advance by nsteps at once. */
+int ddq_actor_step_async(ddq_ctx* ctx, int32_t nsteps, int64_t iter_num);
+/* Synchronise; boards: 4*100 int8, oldest frame first; stats[4]: steps taken,
+ * games ended, sum of rewards, RNG draws consumed.  Either may be NULL. */
+int ddq_actor_read(ddq_ctx* ctx, int8_t* boards, int64_t* stats);
 
 /* ---------------- apply (param server) --------------------------------- */
 /* apply_descent + update_fn (server.py:49-124) on the Q tower with the
