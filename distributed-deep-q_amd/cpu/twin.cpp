@@ -9,7 +9,8 @@
 // -- the deepq network of models/deepq/train_val.prototxt:38-483 (both
 // towers, Q(s,a), the Bellman target 0.85 max_a P + r, the Euclidean loss, the
 // Q backward), the replay ring of replay.py, the Snake actor of expgain.py +
-// gamesim/SnakeGame.py (ddq_actor_*) and the param-server update rules of
+// gamesim/SnakeGame.py (ddq_actor_*), the lock-step policy evaluation of
+// evaluation.py with per-game streams (ddq_eval_*) and the update rules of
 // server.py:49-124 -- with plain C++ loops over NCHW fp32 tensors,
 // accumulating every dot product in double and rounding once per layer
 // output (so it is no less exact than the GPU's fp32-exact split products).
@@ -99,6 +100,20 @@ struct ddq_ctx {
   std::vector<int32_t> a_row, a_col;
   uint64_t a_seed = 0, a_draws = 0;
   int64_t a_steps = 0, a_games = 0, a_reward = 0;
+  // policy evaluation (ddq_eval_*): the games in lock step, each with its own
+  // stream, move counter and episode log
+  struct EvalGame {
+    uint64_t seed = 0, draws = 0;
+    int64_t reward = 0;
+    int32_t move = 0, score = 0, moves = 0;
+    int8_t boards[4][100], init[100];
+    std::vector<int32_t> log;      // 4 per record: end_move, score, moves, ended_by
+  };
+  std::vector<EvalGame> e_games;   // empty: no evaluator
+  std::vector<int32_t> e_row, e_col;
+  double e_eps = 0.0;
+  int32_t e_max_moves = 0, e_max_ep = 0;
+  int64_t e_moves = 0;
   std::string err;
 };
 
@@ -852,6 +867,35 @@ void actor_render(const ddq_ctx* c, std::vector<uint8_t>* out) {
       }
 }
 
+// SnakeGame.cpu_play on board cur: the board after the move into next (not
+// when the game is over); returns the reward (-1: game over).  randrange(n)
+// draws the new apple's place among the n empty cells.
+template <class R>
+int snake_play(const int8_t* cur, int act, int8_t* next, R&& randrange) {
+  std::vector<Cell> body;
+  snake_body(cur, &body);
+  const int hdx = body[0].x - body[1].x, hdy = body[0].y - body[1].y;
+  static const int step[4][2] = {{0, 1}, {-1, 0}, {0, -1}, {1, 0}};   // w a s d
+  int dx = step[act][0], dy = step[act][1];
+  if (dx == -hdx && dy == -hdy) { dx = hdx; dy = hdy; }
+  const Cell to{body[0].x + dx, body[0].y + dy};
+  bool over = to.x < 0 || to.x >= 10 || to.y < 0 || to.y >= 10;
+  for (const Cell& b : body) over = over || (b.x == to.x && b.y == to.y);
+  if (over) return -1;
+  const bool eat = cur[to.x * 10 + to.y] == -2;
+  body.insert(body.begin(), to);
+  if (!eat) body.pop_back();
+  for (int i = 0; i < 100; ++i) next[i] = cur[i] == -2 ? -2 : -1;
+  for (size_t k = 0; k < body.size(); ++k) next[body[k].x * 10 + body[k].y] = (int8_t)k;
+  if (eat) {   // _add_apple: empty cells x-major then y
+    std::vector<int> empty;
+    for (int i = 0; i < 100; ++i)
+      if (next[i] == -1) empty.push_back(i);
+    if (!empty.empty()) next[empty[randrange(empty.size())]] = -2;
+  }
+  return eat ? 1 : 0;
+}
+
 // one generate_experience (expgain.py:82-111)
 int actor_step(ddq_ctx* c, double eps) {
   std::vector<uint8_t> frames;
@@ -865,32 +909,10 @@ int actor_step(ddq_ctx* c, double eps) {
     if (rc != DDQ_OK) return rc;
   }
   // SnakeGame.cpu_play on the newest board
-  const int8_t* cur = c->a_boards[3];
-  std::vector<Cell> body;
-  snake_body(cur, &body);
-  const int hdx = body[0].x - body[1].x, hdy = body[0].y - body[1].y;
-  static const int step[4][2] = {{0, 1}, {-1, 0}, {0, -1}, {1, 0}};   // w a s d
-  int dx = step[act][0], dy = step[act][1];
-  if (dx == -hdx && dy == -hdy) { dx = hdx; dy = hdy; }
-  const Cell to{body[0].x + dx, body[0].y + dy};
-  bool over = to.x < 0 || to.x >= 10 || to.y < 0 || to.y >= 10;
-  for (const Cell& b : body) over = over || (b.x == to.x && b.y == to.y);
-  int reward = -1;
   int8_t next[100];
-  if (!over) {
-    const bool eat = cur[to.x * 10 + to.y] == -2;
-    body.insert(body.begin(), to);
-    if (!eat) body.pop_back();
-    for (int i = 0; i < 100; ++i) next[i] = cur[i] == -2 ? -2 : -1;
-    for (size_t k = 0; k < body.size(); ++k) next[body[k].x * 10 + body[k].y] = (int8_t)k;
-    reward = eat ? 1 : 0;
-    if (eat) {   // _add_apple: empty cells x-major then y
-      std::vector<int> empty;
-      for (int i = 0; i < 100; ++i)
-        if (next[i] == -1) empty.push_back(i);
-      if (!empty.empty()) next[empty[actor_randrange(c, empty.size())]] = -2;
-    }
-  }
+  const int reward = snake_play(c->a_boards[3], act, next,
+                                [c](uint64_t n) { return actor_randrange(c, n); });
+  const bool over = reward < 0;
   if (over) {
     const int rc = ddq_replay_add(c, act, reward, nullptr);
     if (rc != DDQ_OK) return rc;
@@ -956,6 +978,119 @@ int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
     stats[0] = c->a_steps; stats[1] = c->a_games; stats[2] = c->a_reward;
     stats[3] = (int64_t)c->a_draws;
   }
+  return DDQ_OK;
+}
+
+// ---- policy evaluation (evaluation.py:10-51 with per-game streams) ----
+int ddq_eval_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards, const int32_t* row_map,
+                    const int32_t* col_map, uint64_t seed, double epsilon, int32_t max_moves,
+                    int32_t max_episodes) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
+  if (ngames < 1 || ngames > c->B)
+    return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, c->B);
+  if (!(epsilon >= 0.0 && epsilon <= 1.0))
+    return fail(c, DDQ_EINVAL, "epsilon must be in [0,1] (got %g)", epsilon);
+  if (max_moves < 0) return fail(c, DDQ_EINVAL, "max_moves must be >= 0 (got %d)", max_moves);
+  if (max_episodes < 1)
+    return fail(c, DDQ_EINVAL, "max_episodes must be >= 1 (got %d)", max_episodes);
+  for (int i = 0; i < c->S; ++i)
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+  for (int g = 0; g < ngames; ++g) {
+    const int8_t* b = init_boards + 100 * g;
+    std::vector<Cell> body;
+    if (!snake_body(b, &body) || body.size() < 2)
+      return fail(c, DDQ_EINVAL, "init_boards[%d]: snake cells must be the codes 0..k-1, k >= 2", g);
+    if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
+      return fail(c, DDQ_EINVAL, "init_boards[%d]: head and neck are not neighbours", g);
+  }
+  c->e_games.assign(ngames, ddq_ctx::EvalGame{});
+  for (int g = 0; g < ngames; ++g) {
+    ddq_ctx::EvalGame& eg = c->e_games[g];
+    eg.seed = mix64(mix64(seed) ^ (uint64_t)g);
+    memcpy(eg.init, init_boards + 100 * g, 100);
+    for (auto& b : eg.boards) memcpy(b, eg.init, 100);
+  }
+  c->e_row.assign(row_map, row_map + c->S);
+  c->e_col.assign(col_map, col_map + c->S);
+  c->e_eps = epsilon;
+  c->e_max_moves = max_moves;
+  c->e_max_ep = max_episodes;
+  c->e_moves = 0;
+  return DDQ_OK;
+}
+
+int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->e_games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
+  const int n = (int)c->e_games.size(), S = c->S;
+  const size_t fs = (size_t)kC * S * S;
+  std::vector<uint8_t> frames(n * fs);
+  std::vector<int32_t> greedy(n);
+  for (int m = 0; m < nmoves; ++m) {
+    // every game's state, idle ones included, in one batched forward
+    for (int g = 0; g < n; ++g)
+      for (int f = 0; f < kC; ++f)
+        for (int i = 0; i < S; ++i)
+          for (int j = 0; j < S; ++j) {
+            const int v = c->e_games[g].boards[f][c->e_row[i] * 10 + c->e_col[j]];
+            frames[g * fs + ((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
+          }
+    const int rc = ddq_select_action(c, frames.data(), n, greedy.data());
+    if (rc != DDQ_OK) return rc;
+    for (int g = 0; g < n; ++g) {
+      ddq_ctx::EvalGame& eg = c->e_games[g];
+      if ((int32_t)eg.log.size() >= 4 * c->e_max_ep) continue;   // its log is full: idle
+      auto next_draw = [&eg]() { return mix64(eg.seed ^ mix64(eg.draws++)); };
+      auto randrange = [&](uint64_t k) {
+        return (uint64_t)(((unsigned __int128)next_draw() * k) >> 64);
+      };
+      int act = greedy[g];
+      if (c->e_eps > 0.0 && (double)(next_draw() >> 11) * 0x1.0p-53 < c->e_eps)
+        act = (int)randrange(kA);
+      int8_t next[100];
+      const int reward = snake_play(eg.boards[3], act, next, randrange);
+      eg.reward += reward;
+      eg.score += reward;
+      eg.moves += 1;
+      const bool over = reward < 0;
+      if (over || (c->e_max_moves > 0 && eg.moves >= c->e_max_moves)) {
+        eg.log.insert(eg.log.end(), {eg.move, eg.score, eg.moves, over ? 0 : 1});
+        eg.score = eg.moves = 0;
+        for (auto& b : eg.boards) memcpy(b, eg.init, 100);   // reset_game
+      } else {
+        memmove(eg.boards[0], eg.boards[1], 300);
+        memcpy(eg.boards[3], next, 100);
+      }
+      eg.move += 1;
+    }
+  }
+  c->e_moves += nmoves;
+  return DDQ_OK;
+}
+
+int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, int8_t* boards,
+                  uint64_t* draws) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->e_games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  int64_t eps = 0, rew = 0, dr = 0;
+  const size_t per = 4 * (size_t)c->e_max_ep;
+  for (size_t g = 0; g < c->e_games.size(); ++g) {
+    const ddq_ctx::EvalGame& eg = c->e_games[g];
+    eps += (int64_t)eg.log.size() / 4;
+    rew += eg.reward;
+    dr += (int64_t)eg.draws;
+    if (episodes) episodes[g] = (int32_t)(eg.log.size() / 4);
+    if (log) {
+      std::fill(log + g * per, log + (g + 1) * per, 0);
+      std::copy(eg.log.begin(), eg.log.end(), log + g * per);
+    }
+    if (boards) memcpy(boards + 400 * g, eg.boards, 400);
+    if (draws) draws[g] = eg.draws;
+  }
+  if (stats) { stats[0] = c->e_moves; stats[1] = eps; stats[2] = rew; stats[3] = dr; }
   return DDQ_OK;
 }
 

@@ -31,6 +31,78 @@ __device__ __forceinline__ uint8_t actor_level(int v) {
   return v == kEmptyCell ? 0 : (v == kAppleCell ? 255 : 200);
 }
 
+// first maximum of a state's four Q values, as argmax_kernel
+__device__ __forceinline__ int actor_first_max(const float* __restrict__ q) {
+  int act = 0;
+  for (int a = 1; a < kActions; ++a)
+    if (q[a] > q[act]) act = a;
+  return act;
+}
+
+// One SnakeGame.cpu_play by one thread: action act on board cur, the board
+// after the move into nbd (untouched when the game is over).  Returns the
+// reward: 1 apple eaten, 0 plain move, -1 game over (wall or body).  The new
+// apple is draw k of the stream, k advanced.  Shared by the actor's and the
+// evaluator's environment kernels: the rules exist once.
+__device__ __forceinline__ int snake_move(const int8_t* cur, int8_t* nbd, int act, uint64_t seed,
+                                          uint64_t& k) {
+  int head = 0, neck = 0, len = 0;
+  for (int c = 0; c < kCells; ++c) {
+    const int v = cur[c];
+    if (v == 0) head = c;
+    if (v == 1) neck = c;
+    len += v >= 0;
+  }
+  const int hx = head / kSide, hy = head % kSide;
+  const int dx = hx - neck / kSide, dy = hy - neck % kSide;   // heading (set_state)
+  // ["w","a","s","d"] = y+1, x-1, y-1, x+1
+  int mx = (act == 3) - (act == 1), my = (act == 0) - (act == 2);
+  if (mx == -dx && my == -dy) { mx = dx; my = dy; }   // a reversal keeps the heading
+  const int nx = hx + mx, ny = hy + my, nc = nx * kSide + ny;
+  if (nx < 0 || nx >= kSide || ny < 0 || ny >= kSide || cur[nc] >= 0) return -1;
+  const bool eat = cur[nc] == kAppleCell;
+  for (int c = 0; c < kCells; ++c) {
+    int v = cur[c];
+    if (v >= 0) v = (!eat && v == len - 1) ? kEmptyCell : v + 1;   // the tail moves on
+    nbd[c] = (int8_t)v;
+  }
+  nbd[nc] = 0;
+  if (eat) {   // the new apple: entry randrange(n) of the empty cells, x-major then y
+    int n = 0;
+    for (int c = 0; c < kCells; ++c) n += nbd[c] == kEmptyCell;
+    if (n > 0) {
+      int j = (int)__umul64hi(actor_draw(seed, k), (uint64_t)n);
+      for (int c = 0; c < kCells; ++c)
+        if (nbd[c] == kEmptyCell && j-- == 0) { nbd[c] = kAppleCell; break; }
+    }
+  }
+  return eat ? 1 : 0;
+}
+
+// Pixels p..p+3 (one row, p % 4 == 0) of the four frames through the zoom maps,
+// from the gray levels lv[4][kCells]
+__device__ __forceinline__ void actor_pixels(const uint8_t* lv, const uint8_t* __restrict__ maps,
+                                             int S, int p, uchar4 px[4]) {
+  const int i = p / S, j = p - i * S;
+  const int row = maps[i] * kSide;
+  const uchar4 cm = *reinterpret_cast<const uchar4*>(maps + S + j);
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const uint8_t* l = lv + f * kCells + row;
+    px[f] = make_uchar4(l[cm.x], l[cm.y], l[cm.z], l[cm.w]);
+  }
+}
+
+// the same four pixels as f32 NHWC: 16 floats at in + 4 p
+__device__ __forceinline__ void actor_store_nhwc(float* __restrict__ in, int p,
+                                                 const uchar4 px[4]) {
+  float4* dst = reinterpret_cast<float4*>(in + (size_t)p * 4);
+  dst[0] = f4(px[0].x, px[1].x, px[2].x, px[3].x);
+  dst[1] = f4(px[0].y, px[1].y, px[2].y, px[3].y);
+  dst[2] = f4(px[0].z, px[1].z, px[2].z, px[3].z);
+  dst[3] = f4(px[0].w, px[1].w, px[2].w, px[3].w);
+}
+
 // play = 0: render the current boards into actor_in only (ddq_actor_create).
 // thresh = ceil(epsilon * 2^53): explore iff (r >> 11) < thresh, which is
 // random() < epsilon for random() = (r >> 11) * 2^-53.
@@ -52,48 +124,15 @@ __global__ __launch_bounds__(kActorThreads) void actor_env_kernel(
 
   if (play && t == 0) {
     const int8_t* cur = bd + 3 * kCells;
-    int head = 0, neck = 0, len = 0;
-    for (int c = 0; c < kCells; ++c) {
-      const int v = cur[c];
-      if (v == 0) head = c;
-      if (v == 1) neck = c;
-      len += v >= 0;
-    }
-    const int hx = head / kSide, hy = head % kSide;
-    const int dx = hx - neck / kSide, dy = hy - neck % kSide;   // heading (set_state)
     // 1. greedy action: first maximum, as argmax_kernel
-    int act = 0;
-    for (int a = 1; a < kActions; ++a)
-      if (q[a] > q[act]) act = a;
+    int act = actor_first_max(q);
     // 2. coin, then the action when exploring
     const uint64_t seed = as->seed;
     uint64_t k = as->draws;
     if ((actor_draw(seed, k) >> 11) < thresh) act = (int)__umul64hi(actor_draw(seed, k), kActions);
-    // 3. one move; ["w","a","s","d"] = y+1, x-1, y-1, x+1
-    int mx = (act == 3) - (act == 1), my = (act == 0) - (act == 2);
-    if (mx == -dx && my == -dy) { mx = dx; my = dy; }   // a reversal keeps the heading
-    const int nx = hx + mx, ny = hy + my, nc = nx * kSide + ny;
-    const bool over = nx < 0 || nx >= kSide || ny < 0 || ny >= kSide || cur[nc] >= 0;
-    int reward = -1;
-    if (!over) {
-      const bool eat = cur[nc] == kAppleCell;
-      reward = eat ? 1 : 0;
-      for (int c = 0; c < kCells; ++c) {
-        int v = cur[c];
-        if (v >= 0) v = (!eat && v == len - 1) ? kEmptyCell : v + 1;   // the tail moves on
-        nbd[c] = (int8_t)v;
-      }
-      nbd[nc] = 0;
-      if (eat) {   // the new apple: entry randrange(n) of the empty cells, x-major then y
-        int n = 0;
-        for (int c = 0; c < kCells; ++c) n += nbd[c] == kEmptyCell;
-        if (n > 0) {
-          int j = (int)__umul64hi(actor_draw(seed, k), (uint64_t)n);
-          for (int c = 0; c < kCells; ++c)
-            if (nbd[c] == kEmptyCell && j-- == 0) { nbd[c] = kAppleCell; break; }
-        }
-      }
-    }
+    // 3. one move
+    const int reward = snake_move(cur, nbd, act, seed, k);
+    const bool over = reward < 0;
     // 4./5. the transition's scalars into slot head; head / valid; the stats
     const int64_t cap = meta->capacity, h = meta->head;
     if (h >= 0 && h < cap) {
@@ -131,27 +170,16 @@ __global__ __launch_bounds__(kActorThreads) void actor_env_kernel(
   // render through the zoom maps, 4 pixels of one row per thread (S % 8 == 0):
   // u8 (C,H,W) into the ring slot, f32 NHWC into actor_in
   const int SS = S * S;
-  const uint8_t* cmap = maps + S;
   uint8_t* slot = s_slot >= 0 ? r_state + (size_t)s_slot * 4 * SS : nullptr;
   for (int p4 = t; p4 * 4 < SS; p4 += kActorThreads) {
-    const int p = p4 * 4, i = p / S, j = p - i * S;
-    const int row = maps[i] * kSide;
-    const uchar4 cm = *reinterpret_cast<const uchar4*>(cmap + j);
+    const int p = p4 * 4;
     uchar4 px[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      const uint8_t* l = lv + f * kCells + row;
-      px[f] = make_uchar4(l[cm.x], l[cm.y], l[cm.z], l[cm.w]);
-    }
+    actor_pixels(lv, maps, S, p, px);
     if (slot) {
 #pragma unroll
       for (int f = 0; f < 4; ++f) *reinterpret_cast<uchar4*>(slot + (size_t)f * SS + p) = px[f];
     }
-    float4* dst = reinterpret_cast<float4*>(actor_in + (size_t)p * 4);
-    dst[0] = f4(px[0].x, px[1].x, px[2].x, px[3].x);
-    dst[1] = f4(px[0].y, px[1].y, px[2].y, px[3].y);
-    dst[2] = f4(px[0].z, px[1].z, px[2].z, px[3].z);
-    dst[3] = f4(px[0].w, px[1].w, px[2].w, px[3].w);
+    actor_store_nhwc(actor_in, p, px);
   }
 }
 

@@ -58,6 +58,16 @@ struct ddq_ctx {
   uint8_t* a_maps = nullptr;
   float* a_in = nullptr;
   bool actor = false;
+  // device-resident evaluator (ddq_eval_create): B games' state and input, the
+  // zoom maps, the per-game episode logs (grown on demand)
+  EvalGame* e_games = nullptr;
+  int32_t* e_log = nullptr;
+  size_t e_log_cap = 0;            // int32 elements allocated
+  uint8_t* e_maps = nullptr;
+  float* e_in = nullptr;
+  int e_n = 0, e_max_moves = 0, e_max_ep = 0;   // e_n = 0: no evaluator
+  uint64_t e_thresh = 0;
+  int64_t e_moves = 0;             // lock-step moves enqueued since create
   // index log (ddq_index_log_enable)
   int32_t* log_buf = nullptr;
   int64_t log_buf_cap = 0;
@@ -1079,6 +1089,135 @@ int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
     stats[0] = st.steps; stats[1] = st.games; stats[2] = st.reward_sum;
     stats[3] = (int64_t)st.draws;
   }
+  return DDQ_OK;
+}
+
+// ---------------- device-resident policy evaluation ----------------
+static EvalEnv eval_env(const ddq_ctx* c) {
+  EvalEnv e{};
+  e.games = c->e_games; e.log = c->e_log; e.maps = c->e_maps; e.eval_in = c->e_in;
+  e.S = c->nb.S; e.ngames = c->e_n; e.max_moves = c->e_max_moves; e.max_episodes = c->e_max_ep;
+  return e;
+}
+
+// one lock-step move: the Q forward of the games' states at n = ngames on the
+// evaluator's own input (the act_* scratch is shared with ddq_select_action and
+// the actor: calls on a ctx are serialised), then the environment kernel
+static int enqueue_eval_move(ddq_ctx* c) {
+  HIP_TRY(c, launch_act(c->nb, c->e_in, c->e_n, c->act_p3, c->act_h4, c->act_part, c->act_q,
+                        nullptr, c->act_p1s, c->act_p2s, c->stream));
+  HIP_TRY(c, launch_eval_env(eval_env(c), c->act_q, c->e_thresh, 1, c->stream));
+  return DDQ_OK;
+}
+
+// (Eager enqueue on purpose: the move's launch arguments never change, so it
+// replays from a captured graph, and that was built and measured -- 72.3 us
+// per move against 73.1 eager at 64x64, N = 32, the device being the limit at
+// 19 us of host enqueue per move; profiles/eval_rate_graph_ab.json.  Not
+// faster beyond the noise, so it is not kept.)
+// seed of game i's stream: splitmix64(splitmix64(seed) ^ i) (ddq.actor.game_seed)
+static uint64_t eval_mix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+int ddq_eval_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards, const int32_t* row_map,
+                    const int32_t* col_map, uint64_t seed, double epsilon, int32_t max_moves,
+                    int32_t max_episodes) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
+  const int S = c->nb.S, B = c->nb.B;
+  if (ngames < 1 || ngames > B)
+    return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, B);
+  if (!(epsilon >= 0.0 && epsilon <= 1.0))
+    return fail(c, DDQ_EINVAL, "epsilon must be in [0,1] (got %g)", epsilon);
+  if (max_moves < 0) return fail(c, DDQ_EINVAL, "max_moves must be >= 0 (got %d)", max_moves);
+  if (max_episodes < 1)
+    return fail(c, DDQ_EINVAL, "max_episodes must be >= 1 (got %d)", max_episodes);
+  std::vector<uint8_t> maps(2 * (size_t)S);
+  for (int i = 0; i < S; ++i) {
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+    maps[i] = (uint8_t)row_map[i];
+    maps[S + i] = (uint8_t)col_map[i];
+  }
+  for (int g = 0; g < ngames; ++g)
+    if (const char* why = actor_board_error(init_boards + 100 * g))
+      return fail(c, DDQ_EINVAL, "init_boards[%d]: %s", g, why);
+  TRY(set_dev(c));
+  c->e_n = 0;
+  if (!c->e_games) TRY(dalloc(c, &c->e_games, (size_t)B));
+  if (!c->e_maps) TRY(dalloc(c, &c->e_maps, maps.size()));
+  if (!c->e_in) TRY(dalloc(c, &c->e_in, (size_t)B * S * S * 4));
+  const size_t nlog = (size_t)ngames * max_episodes * 4;
+  if (nlog > c->e_log_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->e_log) {
+      c->allocs.erase(std::find(c->allocs.begin(), c->allocs.end(), (void*)c->e_log));
+      hipFree(c->e_log);
+      c->e_log = nullptr;
+      c->e_log_cap = 0;
+    }
+    TRY(dalloc(c, &c->e_log, nlog));
+    c->e_log_cap = nlog;
+  }
+  std::vector<EvalGame> gs(ngames);
+  const uint64_t base = eval_mix64(seed);
+  for (int g = 0; g < ngames; ++g) {
+    gs[g] = EvalGame{};
+    gs[g].seed = eval_mix64(base ^ (uint64_t)g);
+    for (int f = 0; f < 5; ++f) memcpy(gs[g].boards + f * 100, init_boards + 100 * g, 100);
+  }
+  HIP_TRY(c, hipMemsetAsync(c->e_log, 0, nlog * sizeof(int32_t), c->stream));
+  HIP_TRY(c, scopy(c, c->e_games, gs.data(), gs.size() * sizeof(EvalGame), hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->e_maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
+  c->e_n = ngames;
+  c->e_max_moves = max_moves;
+  c->e_max_ep = max_episodes;
+  // explore iff random() = (r >> 11) * 2^-53 < epsilon; epsilon = 0: no coin at all
+  c->e_thresh = (uint64_t)std::ceil(epsilon * 9007199254740992.0);
+  c->e_moves = 0;
+  const hipError_t e = launch_eval_env(eval_env(c), c->act_q, 0, 0, c->stream);   // render only
+  if (e != hipSuccess) {
+    c->e_n = 0;
+    return fail(c, DDQ_EHIP, "eval render failed: %s", hipGetErrorString(e));
+  }
+  return DDQ_OK;
+}
+
+int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->e_n) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
+  TRY(set_dev(c));
+  for (int i = 0; i < nmoves; ++i) TRY(enqueue_eval_move(c));
+  c->e_moves += nmoves;
+  return DDQ_OK;
+}
+
+int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, int8_t* boards,
+                  uint64_t* draws) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->e_n) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  TRY(set_dev(c));
+  const int n = c->e_n;
+  std::vector<EvalGame> gs(n);
+  HIP_TRY(c, scopy(c, gs.data(), c->e_games, gs.size() * sizeof(EvalGame), hipMemcpyDeviceToHost));
+  if (log)
+    HIP_TRY(c, scopy(c, log, c->e_log, (size_t)n * c->e_max_ep * 4 * sizeof(int32_t),
+                     hipMemcpyDeviceToHost));
+  int64_t eps = 0, rew = 0, dr = 0;
+  for (int g = 0; g < n; ++g) {
+    eps += gs[g].episodes;
+    rew += gs[g].reward_sum;
+    dr += (int64_t)gs[g].draws;
+    if (episodes) episodes[g] = gs[g].episodes;
+    if (boards) memcpy(boards + 400 * g, gs[g].boards, 400);
+    if (draws) draws[g] = gs[g].draws;
+  }
+  if (stats) { stats[0] = c->e_moves; stats[1] = eps; stats[2] = rew; stats[3] = dr; }
   return DDQ_OK;
 }
 

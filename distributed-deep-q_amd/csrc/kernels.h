@@ -240,6 +240,30 @@ struct ActorEnv {
 // state into that slot (not after a game over) and into actor_in.
 hipError_t launch_actor_env(const ActorEnv& e, const float* q, uint64_t thresh, int play,
                             hipStream_t s);
+// Device-resident policy evaluation (eval.h): ngames independent Snake games in
+// lock step, one workgroup each.  EvalGame: one game's RNG stream (as the
+// actor's), its lock-step move counter, the records in its log, the running
+// episode's score / moves and its boards (4-frame history, then its start board).
+struct EvalGame {
+  uint64_t seed, draws;
+  int64_t reward_sum;
+  int32_t move, episodes, score, moves;
+  int8_t boards[5 * 100];
+  int8_t pad[4];
+};
+struct EvalEnv {
+  EvalGame* games;                  // [ngames]
+  int32_t* log;                     // [ngames][max_episodes][4]: end_move, score, moves, ended_by
+  const uint8_t* maps;              // row_map[S] then col_map[S]
+  float* eval_in;                   // [ngames] states as f32 NHWC (S,S,4): the forward's input
+  int S, ngames, max_moves, max_episodes;
+};
+// ngames workgroups: (play != 0) game g's action from q[4g..4g+4) (the coin
+// only when thresh > 0), one game step, the episode record when the game is
+// over or max_moves is reached, then the render of its next state into its
+// slice of eval_in.  A game whose log is full does nothing.
+hipError_t launch_eval_env(const EvalEnv& e, const float* q, uint64_t thresh, int play,
+                           hipStream_t s);
 // large-batch device draw (bitmap claim + ordered compaction) into idx[0..n)
 // and the Caffe-layout (n,4,S,S) f32 gather of replay.py:167-183
 hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t seed,

@@ -2311,3 +2311,5 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
 
 // the device-resident actor's environment step (after launch_act's forward)
 #include "actor.h"
+// the device-resident evaluator's environment step: one game per workgroup
+#include "eval.h"

@@ -31,6 +31,12 @@ def splitmix64(x):
     return x ^ (x >> 31)
 
 
+def game_seed(seed, i):
+    """Seed of game i's stream in a batch of games on one ``seed`` (the device
+    evaluator, ``ddq_eval_create``): splitmix64(splitmix64(seed) ^ i)."""
+    return splitmix64(splitmix64(int(seed) & _M64) ^ (int(i) & _M64))
+
+
 class ActorRng:
     """The actor's random stream with the ``random.Random`` methods ``ExpGain``
     and ``SnakeGame`` use; ``draws`` counts the numbers consumed."""

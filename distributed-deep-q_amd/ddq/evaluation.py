@@ -16,11 +16,17 @@ GPU network.
   score.  ``max_moves`` (default None = the reference's unbounded games) ends
   a game that has not finished after that many moves, for drivers that
   cannot risk a policy that circles forever.
+  ``streams="per_game"`` gives every engine its own game and random stream
+  (the contract of ``ddq_eval_create``, include/ddq_hip.h).
+* ``DevicePolicyEvaluator(...).evaluate(model, num_trials)``: that per-game
+  evaluation with the games on the device (``ddq_eval_*``): no host copy and
+  no synchronisation between moves, the same trials and the same average.
 * ``evaluate_model(barista_net, model, num_batches)``: q_convergence.py:15-25
   -- mean of Q_out over ``num_batches`` minibatches sampled from the net's
   dataset.
 * ``start(architecture_file, model_file, snapshots, ...)``: evaluation.py:
-  54-72 over snapshot files instead of Redis keys; returns {name: average}.
+  54-72 over snapshot files instead of Redis keys; returns {name: average};
+  ``device=True`` evaluates with ``DevicePolicyEvaluator``.
 """
 from __future__ import annotations
 
@@ -68,17 +74,76 @@ def load_snapshot(path):
     return {k: [np.asarray(a, np.float32) for a in v] for k, v in snap.items()}
 
 
-class PolicyEvaluator:
-    """evaluation.py:10-51."""
+ACTIONS = ["w", "a", "s", "d"]
 
-    def __init__(self, architecture_file, model_file, net=None, seed=None, max_moves=None):
+
+def select_trials(logs, num_trials):
+    """The trials of a per-game evaluation: ``logs[i]`` holds game i's records
+    (end_move, score, moves, ended_by); all records sorted by (end_move, game
+    index), the first ``num_trials`` of them -- the order in which
+    ``PolicyEvaluator.evaluate`` counts finished games.  Returns a list of
+    (end_move, game, score, moves, ended_by)."""
+    recs = sorted((int(r[0]), i, int(r[1]), int(r[2]), int(r[3]))
+                  for i, log in enumerate(logs) for r in log)
+    if len(recs) < num_trials:
+        raise ValueError("%d episodes logged, %d trials wanted" % (len(recs), num_trials))
+    return recs[:num_trials]
+
+
+def _start_boards(init_states, n, seed):
+    """(n,10,10) start boards: the given one replicated, or one per game."""
+    if init_states is None:
+        init_states = SnakeGame(random.Random(seed)).encode_state()
+    b = np.array(init_states, np.int64)
+    if b.ndim == 2:
+        b = np.repeat(b[None], n, axis=0)
+    if b.shape != (n, 10, 10):
+        raise ValueError("start boards %s for %d games" % (b.shape, n))
+    return b
+
+
+class PolicyEvaluator:
+    """evaluation.py:10-51.
+
+    ``streams="per_game"`` (with ``epsilon`` and ``init_states``, one board or
+    one per engine) is the host form of ``DevicePolicyEvaluator``'s contract:
+    engine i plays its own ``SnakeGame`` on ``ActorRng(game_seed(seed, i))``,
+    explores with probability ``epsilon`` (no coin is drawn at 0), logs its
+    episodes, and the trials are chosen by ``select_trials``.  The defaults
+    are the reference's loop: one game object and one stream for all engines."""
+
+    def __init__(self, architecture_file, model_file, net=None, seed=None, max_moves=None,
+                 streams="shared", epsilon=0.0, init_states=None):
         from .barista.baristanet import BaristaNet
+        if streams not in ("shared", "per_game"):
+            raise ValueError("streams must be 'shared' or 'per_game', got %r" % (streams,))
         self.net = net if net is not None else BaristaNet(architecture_file, model_file, None)
         self.batch_size = self.net.batch_size
         self.max_moves = max_moves
-        game = SnakeGame(random.Random(seed))
+        self.streams = streams
+        self.epsilon = float(epsilon)
+        self.episodes = []
         preprocessor = generate_preprocessor(self.net.state.shape[2:], gray_scale)
-        self.engines = [ExpGain(self.net, ["w", "a", "s", "d"], preprocessor, game.cpu_play,
+        if streams == "per_game":
+            from .actor import ActorRng, game_seed
+            if not 0.0 <= self.epsilon <= 1.0:
+                raise ValueError("epsilon must be in [0,1], got %r" % (epsilon,))
+            seed = 0 if seed is None else seed
+            n = self.batch_size
+            if init_states is not None and np.ndim(init_states) == 3:
+                n = len(init_states)
+            boards = _start_boards(init_states, n, seed)
+            self.engines = []
+            for i in range(n):
+                game = SnakeGame(random.Random(0))      # (its start apple is never seen)
+                game.rng = ActorRng(game_seed(seed, i))
+                self.engines.append(ExpGain(self.net, ACTIONS, preprocessor, game.cpu_play,
+                                            None, boards[i], rng=game.rng))
+            return
+        if epsilon != 0.0 or init_states is not None:
+            raise ValueError("epsilon / init_states need streams='per_game'")
+        game = SnakeGame(random.Random(seed))
+        self.engines = [ExpGain(self.net, ACTIONS, preprocessor, game.cpu_play,
                                 None, game.encode_state())
                         for _ in range(self.batch_size)]
 
@@ -89,6 +154,8 @@ class PolicyEvaluator:
             set_net_params(self.net, model)
         for eg in self.engines:
             eg.reset_game()
+        if self.streams == "per_game":
+            return self._evaluate_per_game(num_trials)
         total_score = 0
         trials_completed = 0
         scores = [0] * self.batch_size
@@ -109,6 +176,91 @@ class PolicyEvaluator:
                     moves[i] = 0
         return float(total_score) / num_trials
 
+    def _evaluate_per_game(self, num_trials):
+        n = len(self.engines)
+        for eg in self.engines:
+            eg.rng.draws = 0                   # every evaluation starts the streams anew
+        max_moves = self.max_moves or 0
+        logs = [[] for _ in range(n)]
+        scores, moves = [0] * n, [0] * n
+        done = move = 0
+        while done < num_trials:
+            states = np.stack([eg.get_preprocessed_state() for eg in self.engines])
+            actions = self.net.select_action(states, batch_size=n)
+            for i, eg in enumerate(self.engines):
+                if len(logs[i]) >= num_trials:  # a full log: the game is idle
+                    continue
+                act = int(actions[i])
+                if self.epsilon > 0.0 and eg.rng.random() < self.epsilon:
+                    act = eg.rng.randrange(len(eg.actions))
+                scores[i] += eg.play_action(eg.actions[act])
+                moves[i] += 1
+                if eg.game_over or (max_moves > 0 and moves[i] >= max_moves):
+                    logs[i].append((move, scores[i], moves[i], 0 if eg.game_over else 1))
+                    done += 1
+                    eg.reset_game()
+                    scores[i] = moves[i] = 0
+            move += 1
+        self.episodes = select_trials(logs, num_trials)
+        return float(sum(r[2] for r in self.episodes)) / num_trials
+
+
+class DevicePolicyEvaluator:
+    """``PolicyEvaluator(streams="per_game")`` with the games on the device
+    (``ddq_eval_*``): ``games`` (default: the batch size) Snake games in lock
+    step on the net's ctx, one batched Q forward and one environment kernel
+    per move, nothing copied and nothing synchronised between moves.
+
+    ``evaluate`` enqueues ``chunk`` moves at a time and reads the per-game
+    episode counts after each chunk (one synchronise per chunk).  Without
+    ``max_moves`` the games are unbounded, as in the reference; ``move_limit``
+    raises once that many lock-step moves have not produced the trials."""
+
+    def __init__(self, architecture_file, model_file, net=None, seed=0, max_moves=None,
+                 epsilon=0.0, init_state=None, games=None, chunk=32, move_limit=None):
+        from .actor import zoom_maps
+        from .barista.baristanet import BaristaNet
+        self.net = net if net is not None else BaristaNet(architecture_file, model_file, None)
+        self.dqn = getattr(self.net, "dqn", self.net)
+        self.batch_size = self.dqn.batch
+        self.games = self.batch_size if games is None else int(games)
+        self.seed = 0 if seed is None else int(seed)
+        self.max_moves = max_moves
+        self.epsilon = float(epsilon)
+        self.chunk = int(chunk)
+        if self.chunk < 1:
+            raise ValueError("chunk must be >= 1, got %d" % self.chunk)
+        self.move_limit = move_limit
+        self.boards = _start_boards(init_state, self.games, self.seed)
+        S = self.dqn.frame
+        self.row_map, self.col_map = zoom_maps((S, S), S)
+        self.episodes = []
+        self.stats = None
+
+    def evaluate(self, model, num_trials):
+        """Runs ``num_trials`` games and returns the average score; the chosen
+        records (end_move, game, score, moves, ended_by) stay in ``episodes``."""
+        from .barista.netutils import set_net_params
+        if model is not None:
+            set_net_params(self.net, model)
+        num_trials = int(num_trials)
+        self.dqn.eval_create(self.boards, self.row_map, self.col_map, self.seed, self.epsilon,
+                             self.max_moves or 0, num_trials)
+        moves = 0
+        while True:
+            self.dqn.eval_run(self.chunk)
+            moves += self.chunk
+            if int(self.dqn.eval_read(full=False).sum()) >= num_trials:
+                break
+            if self.move_limit is not None and moves >= self.move_limit:
+                raise RuntimeError("%d lock-step moves without %d finished games"
+                                   % (moves, num_trials))
+        out = self.dqn.eval_read()
+        self.stats = out["stats"]
+        logs = [out["log"][i, :k] for i, k in enumerate(out["episodes"])]
+        self.episodes = select_trials(logs, num_trials)
+        return float(sum(r[2] for r in self.episodes)) / num_trials
+
 
 def evaluate_model(barista_net, model, num_batches):
     """q_convergence.py:15-25: average Q_out over ``num_batches`` minibatches."""
@@ -124,10 +276,11 @@ def evaluate_model(barista_net, model, num_batches):
 
 
 def start(architecture_file, model_file, snapshots="centralModel-*", num_trials=32,
-          results=None, recompute=False, evaluator=None):
+          results=None, recompute=False, evaluator=None, device=False):
     """evaluation.py:54-72 over snapshot files (a glob or a list) instead of
     Redis keys.  ``results`` (a dict) carries earlier averages; entries are
-    recomputed only with ``recompute``."""
+    recomputed only with ``recompute``.  ``device``: when no evaluator is
+    passed, build a ``DevicePolicyEvaluator`` instead of the host one."""
     results = {} if results is None else results
     paths = sorted(glob.glob(snapshots)) if isinstance(snapshots, str) else list(snapshots)
     pe = evaluator
@@ -136,6 +289,7 @@ def start(architecture_file, model_file, snapshots="centralModel-*", num_trials=
         if key in results and not recompute:
             continue
         if pe is None:
-            pe = PolicyEvaluator(architecture_file, model_file)
+            pe = (DevicePolicyEvaluator if device else PolicyEvaluator)(architecture_file,
+                                                                        model_file)
         results[key] = pe.evaluate(load_snapshot(path), num_trials)
     return results

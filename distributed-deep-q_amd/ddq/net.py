@@ -247,6 +247,52 @@ class DeepQNet:
         self._check(self.lib.ddq_actor_read(self.ctx, ptr(boards), ptr(stats)))
         return boards, stats
 
+    # -------------------------------------------------------------- evaluation
+    def eval_create(self, init_boards, row_map, col_map, seed, epsilon=0.0, max_moves=0,
+                    max_episodes=1):
+        """Device-resident policy evaluation (ddq_eval_create): one Snake game
+        per (10,10) board of ``init_boards`` (n,10,10), n <= batch, in lock step;
+        game i draws from ``ActorRng(game_seed(seed, i))``.  ``max_moves`` 0:
+        unbounded episodes; ``max_episodes``: entries of each game's log."""
+        b = np.asarray(init_boards)
+        if b.size == 0 or b.size % 100:
+            raise ValueError("init_boards must hold (10,10) boards, got %d cells" % b.size)
+        if b.min() < -128 or b.max() > 127:
+            raise ValueError("init_boards codes must fit int8")
+        b = np.ascontiguousarray(b, np.int8).reshape(-1, 10, 10)
+        rm = np.ascontiguousarray(row_map, np.int32).ravel()
+        cm = np.ascontiguousarray(col_map, np.int32).ravel()
+        if rm.size != self.frame or cm.size != self.frame:
+            raise ValueError("row_map / col_map must have %d entries" % self.frame)
+        self._check(self.lib.ddq_eval_create(self.ctx, b.shape[0], ptr(b), ptr(rm), ptr(cm),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, float(epsilon),
+                                             int(max_moves), int(max_episodes)))
+        self._eval_shape = (b.shape[0], int(max_episodes))
+
+    def eval_run(self, nmoves):
+        """nmoves lock-step moves of all games; enqueued, no sync."""
+        self._check(self.lib.ddq_eval_run_async(self.ctx, int(nmoves)))
+
+    def eval_read(self, full=True):
+        """Synchronise.  ``full``: dict of stats int64[4] (moves enqueued,
+        episodes logged, sum of rewards, RNG draws), episodes (n,), log
+        (n, max_episodes, 4) int32 (end_move, score, moves, ended_by), boards
+        (n,4,10,10) int8 oldest first, draws (n,) uint64; otherwise only the
+        per-game episode counts."""
+        n, me = getattr(self, "_eval_shape", (self.batch, 0))
+        episodes = np.zeros(n, np.int32)
+        if not full:
+            self._check(self.lib.ddq_eval_read(self.ctx, None, ptr(episodes), None, None, None))
+            return episodes
+        stats = np.zeros(4, np.int64)
+        log = np.zeros((n, me, 4), np.int32)
+        boards = np.zeros((n, NFRAME, 10, 10), np.int8)
+        draws = np.zeros(n, np.uint64)
+        self._check(self.lib.ddq_eval_read(self.ctx, ptr(stats), ptr(episodes),
+                                           ptr(log) if me else None, ptr(boards), ptr(draws)))
+        return {"stats": stats, "episodes": episodes, "log": log, "boards": boards,
+                "draws": draws}
+
     # ------------------------------------------------------------------- apply
     def apply(self, rule="rmsprop", lr=1e-4, decay=0.9, eps=1e-8, momentum=0.9,
               weight_decay=0.0005):

@@ -41,7 +41,9 @@ extern "C" {
                               a timed-out step applies nothing; ddq_inject_fault,
                               ddq_small_path.  ABI 6 later gained the device actor
                               (ddq_actor_create, ddq_actor_step_async, ddq_actor_read):
-                              new symbols only, nothing else changed */
+                              new symbols only, nothing else changed; and then the
+                              device evaluator (ddq_eval_create, ddq_eval_run_async,
+                              ddq_eval_read), again new symbols only */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -315,6 +317,42 @@ int ddq_actor_step_async(ddq_ctx* ctx, int32_t nsteps, int64_t iter_num);
 /* Synchronise; boards: 4*100 int8, oldest frame first; stats[4]: steps taken,
  * games ended, sum of rewards, RNG draws consumed.  Either may be NULL. */
 int ddq_actor_read(ddq_ctx* ctx, int8_t* boards, int64_t* stats);
+
+/* ---------------- device-resident policy evaluation (evaluation.py:10-51) -- */
+/* PolicyEvaluator.evaluate without the host between the moves: ngames <= B
+ * independent Snake games in lock step on this ctx.  One move of all games is
+ * the Q forward of their states at n = ngames and one environment kernel (one
+ * workgroup per game); no copy, no synchronisation.  No replay ring is needed
+ * or touched, nor the bound minibatch, the actor or the step counters.
+ * Random numbers: game i has the actor's kind of stream on
+ * game_seed(seed, i) = splitmix64(splitmix64(seed) ^ i).  Draws per move, in
+ * program order: the coin (only when epsilon > 0: epsilon = 0 is the
+ * reference's greedy evaluation and draws none), the action when exploring
+ * ((r >> 11) < ceil(epsilon * 2^53)), the apple when one is eaten.  The greedy
+ * action is the first maximum of the game's own four Q values.
+ * An episode of game i ends when the game is over, or (max_moves > 0) with its
+ * max_moves-th move; game over wins when both happen at once; the final -1 is
+ * part of the score.  The game then restarts from its own init board
+ * (init_boards: ngames * 100 board codes as ddq_actor_create's, checked alike)
+ * and appends one record of four int32 to its own log of max_episodes entries:
+ * end_move (the lock-step move index, from 0, counted per game on the device),
+ * score, moves, ended_by (0 game over, 1 max_moves).  A game whose log is full
+ * is idle: it plays, draws and renders nothing more.  The evaluator's result
+ * is defined on the logs: all records sorted by (end_move, game index), the
+ * first num_trials of them -- the order in which the host evaluator counts.
+ * Calling it again resets the evaluator. */
+int ddq_eval_create(ddq_ctx* ctx, int32_t ngames, const int8_t* init_boards,
+                    const int32_t* row_map, const int32_t* col_map, uint64_t seed,
+                    double epsilon, int32_t max_moves, int32_t max_episodes);
+/* nmoves lock-step moves, enqueued on the ctx stream, no sync. */
+int ddq_eval_run_async(ddq_ctx* ctx, int32_t nmoves);
+/* Synchronise.  stats[4]: lock-step moves enqueued, episodes logged, sum of
+ * all rewards, RNG draws over all games; episodes: ngames record counts; log:
+ * ngames * max_episodes * 4 int32 (unused entries 0); boards: ngames * 4 * 100
+ * int8, oldest frame first; draws: ngames stream positions.  Every output
+ * pointer may be NULL. */
+int ddq_eval_read(ddq_ctx* ctx, int64_t* stats, int32_t* episodes, int32_t* log,
+                  int8_t* boards, uint64_t* draws);
 
 /* ---------------- apply (param server) --------------------------------- */
 /* apply_descent + update_fn (server.py:49-124) on the Q tower with the
