@@ -114,6 +114,9 @@ struct ddq_ctx {
   double e_eps = 0.0;
   int32_t e_max_moves = 0, e_max_ep = 0;
   int64_t e_moves = 0;
+  // training monitor (ddq_monitor_*): the ring (empty: off) and the records taken
+  std::vector<ddq_monitor_record> m_ring;
+  int64_t m_total = 0;
   std::string err;
 };
 
@@ -1131,6 +1134,78 @@ int ddq_get_optimizer_state(ddq_ctx* c, float* dst, int64_t n) {
   if (!c || !dst) return fail(c, DDQ_EINVAL, "null argument");
   if (n != c->L.total) return fail(c, DDQ_EINVAL, "size mismatch");
   std::copy(c->opt.begin(), c->opt.end(), dst);
+  return DDQ_OK;
+}
+
+// ---- training monitor (netutils.py:72-96 NetLogger quantities) ----
+// period > 0 is accepted and has no effect here: the twin refuses step calls.
+int ddq_monitor_enable(ddq_ctx* c, int64_t capacity, int32_t period) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (capacity < 0 || capacity > (1ll << 24))
+    return fail(c, DDQ_EINVAL, "capacity must be in [0, 2^24] (got %lld)", (long long)capacity);
+  if (period < 0) return fail(c, DDQ_EINVAL, "period must be >= 0 (got %d)", period);
+  c->m_ring.assign((size_t)capacity, ddq_monitor_record{});
+  c->m_ring.shrink_to_fit();
+  c->m_total = 0;
+  return DDQ_OK;
+}
+
+int ddq_monitor_record_async(ddq_ctx* c, int64_t tag) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->m_ring.empty()) return fail(c, DDQ_ESTATE, "monitor not enabled (ddq_monitor_enable)");
+  ddq_monitor_record r{};
+  r.iteration = c->iter;
+  r.tag = tag;
+  r.loss = c->loss;
+  double qs = 0.0;
+  for (int b = 0; b < c->B; ++b) {
+    float m = 0.f;
+    if ((int64_t)c->q_out.size() >= (int64_t)(b + 1) * kA) {
+      const float* q = &c->q_out[(size_t)b * kA];
+      m = q[0];
+      for (int a = 1; a < kA; ++a)
+        if (q[a] > m || std::isnan(q[a])) m = q[a];
+    }
+    qs += m;
+  }
+  r.q_max_mean = (float)(qs / c->B);
+  const Layout& L = c->L;
+  const std::vector<float>* src[3] = {&c->theta[0], &c->theta[1], &c->grad};
+  for (int t = 0; t < 3; ++t) {
+    int32_t bad = 0;
+    for (int j = 0; j < 10; ++j) {
+      const int l = j / 2;
+      const int64_t o = (j & 1) ? L.b[l] : L.w[l], n = (j & 1) ? L.bn[l] : L.wn[l];
+      const float* x = src[t]->data() + o;
+      double ss = 0.0;
+      for (int64_t i = 0; i < n; ++i) {
+        const double v = x[i];
+        ss += v * v;
+        if (!std::isfinite(x[i])) ++bad;
+      }
+      const float rms = (float)std::sqrt(ss / (double)n);
+      if (t < 2) r.param_rms[t][j] = rms;
+      else r.grad_rms[j] = rms;
+    }
+    r.nonfinite[t] = bad;
+  }
+  c->m_ring[(size_t)(c->m_total % (int64_t)c->m_ring.size())] = r;
+  c->m_total++;
+  return DDQ_OK;
+}
+
+int ddq_monitor_read(ddq_ctx* c, int64_t first, int64_t n, ddq_monitor_record* out,
+                     int64_t* total) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->m_ring.empty()) return fail(c, DDQ_ESTATE, "monitor not enabled (ddq_monitor_enable)");
+  if (n < 0 || (n > 0 && !out)) return fail(c, DDQ_EINVAL, "bad argument");
+  if (total) *total = c->m_total;
+  if (n == 0) return DDQ_OK;
+  const int64_t cap = (int64_t)c->m_ring.size();
+  if (first < 0 || first + n > c->m_total || c->m_total - first > cap)
+    return fail(c, DDQ_EINVAL, "records [%lld, %lld) not in the ring (taken %lld, capacity %lld)",
+                (long long)first, (long long)(first + n), (long long)c->m_total, (long long)cap);
+  for (int64_t k = 0; k < n; ++k) out[k] = c->m_ring[(size_t)((first + k) % cap)];
   return DDQ_OK;
 }
 

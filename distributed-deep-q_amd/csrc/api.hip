@@ -24,6 +24,10 @@ int wgrad_splits_for(int layer, int B, int S, int* np);
 
 using namespace ddq;
 
+static_assert(sizeof(MonitorRecord) == sizeof(ddq_monitor_record) && sizeof(MonitorRecord) == 160 &&
+                  offsetof(MonitorRecord, grad_rms) == offsetof(ddq_monitor_record, grad_rms),
+              "MonitorRecord is ddq_monitor_record");
+
 static thread_local std::string g_last_error;
 
 static constexpr int kMaxRanks = 64;
@@ -72,6 +76,9 @@ struct ddq_ctx {
   int32_t* log_buf = nullptr;
   int64_t log_buf_cap = 0;
   int64_t log_first = 0;           // first draw the log holds (the counter at enable)
+  // training monitor (ddq_monitor_enable): mon.ring == nullptr while off
+  MonitorEnv mon{};
+  int32_t mon_period = 0;          // > 0: every single-ctx step ends with the monitor launch
   // comm (RCCL ranks, or an in-process group of ctxs exchanging by device copies)
   ncclComm_t comm = nullptr;
   int nranks = 1, rank = 0;
@@ -178,6 +185,16 @@ static int dalloc(ddq_ctx* c, T** p, size_t count) {
   c->allocs.push_back(q);
   *p = reinterpret_cast<T*>(q);
   return DDQ_OK;
+}
+
+// Free one dalloc'd buffer before the ctx goes (the stream is idle).
+template <class T>
+static void dfree(ddq_ctx* c, T*& p) {
+  if (!p) return;
+  auto it = std::find(c->allocs.begin(), c->allocs.end(), (void*)p);
+  if (it != c->allocs.end()) c->allocs.erase(it);
+  hipFree((void*)p);
+  p = nullptr;
 }
 
 #define TRY(x)                \
@@ -1488,9 +1505,9 @@ static bool fused_prefetch(const ddq_ctx* c, const ddq_step_cfg* cfg) {
   return ex != DDQ_EXCHANGE_ASYNC && c->nb.B <= 256;
 }
 
-static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
-                         const NetBuffers* pre, void (*mark)(void*, const char*), void* marg,
-                         ReplayMeta* bump = nullptr) {
+static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
+                              const NetBuffers* pre, void (*mark)(void*, const char*), void* marg,
+                              ReplayMeta* bump) {
   NetBuffers nb = nb_in;
   nb.book_inc = step_inc(c, cfg);
   // exchange-free steps: fc4's weight update rides on the slab-reduce launch
@@ -1532,6 +1549,21 @@ static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& 
                         ar_overlap));
   TRY(enqueue_exchange_apply(c, cfg, nb, mark, marg, ar_overlap));
   if (pre) HIP_TRY(c, hipStreamWaitEvent(c->stream, nb.ev[7], 0));
+  return DDQ_OK;
+}
+
+// The step, then (ddq_monitor_enable with period > 0) the monitor as its last
+// launch: loss_t, g_t and the parameters after update t; the kernel itself
+// tests the device iteration against the period, so the launch is the same
+// every step and replays from a captured graph.
+static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
+                         const NetBuffers* pre, void (*mark)(void*, const char*), void* marg,
+                         ReplayMeta* bump = nullptr) {
+  TRY(enqueue_train_body(c, cfg, nb_in, pre, mark, marg, bump));
+  if (c->mon.ring && c->mon_period > 0) {
+    if (mark) mark(marg, "monitor");
+    HIP_TRY(c, launch_monitor(c->mon, c->mon_period, -1, c->stream));
+  }
   return DDQ_OK;
 }
 
@@ -1587,6 +1619,20 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
     return fail(c, DDQ_EINVAL, "unknown step flags 0x%x", (unsigned)cfg->flags);
   if (cfg->exchange != DDQ_EXCHANGE_NONE && c->nranks > 1 && !c->comm && !c->local)
     return fail(c, DDQ_ESTATE, "no communicator");
+  return DDQ_OK;
+}
+
+// Single-ctx steps while the monitor records every period-th step: the record
+// needs the step's whole gradient in the buffer and the ctx's own iteration.
+static int check_monitor_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
+  if (!c->mon.ring || c->mon_period <= 0) return DDQ_OK;
+  if (cfg->flags & DDQ_STEP_NO_GRAD_STORE)
+    return fail(c, DDQ_EINVAL, "DDQ_STEP_NO_GRAD_STORE while the monitor records steps (period %d): "
+                               "fc4's gradient block in the buffer would be an earlier step's",
+                c->mon_period);
+  if (is_async(c, cfg))
+    return fail(c, DDQ_ESTATE, "the async exchange takes no monitor records: disable the monitor or "
+                               "enable it with period 0");
   return DDQ_OK;
 }
 
@@ -1805,6 +1851,9 @@ static int rccl_async_round(ddq_ctx* c, const ddq_step_cfg* cfg) {
 int ddq_async_begin(ddq_ctx* c, const ddq_step_cfg* cfg) {
   TRY(check_step(c, cfg));
   if (cfg->exchange != DDQ_EXCHANGE_ASYNC) return fail(c, DDQ_EINVAL, "cfg exchange is not async");
+  if (c->mon.ring && c->mon_period > 0)
+    return fail(c, DDQ_ESTATE, "the async exchange takes no monitor records: disable the monitor or "
+                               "enable it with period 0");
   TRY(set_dev(c));
   return async_prepare(c, cfg);
 }
@@ -2014,6 +2063,7 @@ int ddq_set_straggle(ddq_ctx* c, int64_t usec) {
 
 int ddq_step_async(ddq_ctx* c, const ddq_step_cfg* cfg) {
   TRY(check_step(c, cfg));
+  TRY(check_monitor_step(c, cfg));
   TRY(set_dev(c));
   if (is_async(c, cfg)) {
     TRY(async_prepare(c, cfg));
@@ -2069,6 +2119,7 @@ static int ensure_graph(ddq_ctx* c, const ddq_step_cfg* cfg) {
 
 int ddq_step_graph_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps) {
   TRY(check_step(c, cfg));
+  TRY(check_monitor_step(c, cfg));
   TRY(set_dev(c));
   if (is_async(c, cfg)) return async_graph_steps(c, cfg, nsteps);
   TRY(ensure_graph(c, cfg));
@@ -2161,6 +2212,7 @@ static int ensure_pipe(ddq_ctx* c, const ddq_step_cfg* cfg) {
 
 int ddq_step_prepare(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t mode) {
   TRY(check_step(c, cfg));
+  TRY(check_monitor_step(c, cfg));
   TRY(set_dev(c));
   if (mode == 1) return ensure_graph(c, cfg);
   if (mode == 2) return ensure_pipe(c, cfg);
@@ -2170,6 +2222,7 @@ int ddq_step_prepare(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t mode) {
 
 int ddq_step_pipelined_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps) {
   TRY(check_step(c, cfg));
+  TRY(check_monitor_step(c, cfg));
   TRY(set_dev(c));
   if (nsteps <= 0) return DDQ_OK;
   TRY(ensure_pipe(c, cfg));
@@ -2475,6 +2528,126 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
 
 int64_t ddq_step_count(const ddq_ctx* c) { return c ? c->steps : -1; }
 
+// ---------------- training monitor ----------------
+static void monitor_release(ddq_ctx* c) {
+  MonitorEnv& m = c->mon;
+  MonitorChunk* ch = const_cast<MonitorChunk*>(m.chunks);
+  MonitorBlob* bl = const_cast<MonitorBlob*>(m.blobs);
+  dfree(c, ch);
+  dfree(c, bl);
+  dfree(c, m.psum);
+  dfree(c, m.pnf);
+  dfree(c, m.ticket);
+  dfree(c, m.count);
+  dfree(c, m.ring);
+  m = MonitorEnv{};
+  c->mon_period = 0;
+}
+
+int ddq_monitor_enable(ddq_ctx* c, int64_t capacity, int32_t period) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (capacity < 0 || capacity > (1ll << 24))
+    return fail(c, DDQ_EINVAL, "capacity must be in [0, 2^24] (got %lld)", (long long)capacity);
+  if (period < 0) return fail(c, DDQ_EINVAL, "period must be >= 0 (got %d)", period);
+  if (period > 0 && capacity > 0 && c->async_on)
+    return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: it takes no monitor "
+                               "records of its own (period must be 0)");
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);   // captured steps hold (or lack) the monitor launch
+  monitor_release(c);
+  if (capacity == 0) return DDQ_OK;
+  // chunk table: (tensor, blob) major, offset minor; no chunk straddles a blob
+  const ParamLayout& L = c->nb.L;
+  std::vector<MonitorChunk> chunks;
+  std::vector<MonitorBlob> blobs(kMonBlobs);
+  for (int t = 0; t < 3; ++t)
+    for (int l = 0; l < 5; ++l)
+      for (int i = 0; i < 2; ++i) {
+        const int64_t off = i ? L.b[l] : L.w[l], cnt = i ? L.bn[l] : L.wn[l];
+        if ((off | cnt) & 3)   // the kernel's float4 path (it has a scalar one: slow, not wrong)
+          return fail(c, DDQ_ESTATE, "monitor: blob %d.%d at %lld + %lld is no multiple of 4 floats",
+                      l, i, (long long)off, (long long)cnt);
+        MonitorBlob& b = blobs[t * 10 + 2 * l + i];
+        b.first = (int32_t)chunks.size();
+        b.count = cnt;
+        for (int64_t o = 0; o < cnt; o += kMonChunk)
+          chunks.push_back({t, 2 * l + i, (uint32_t)(off + o),
+                            (int32_t)std::min<int64_t>(kMonChunk, cnt - o)});
+        b.n = (int32_t)chunks.size() - b.first;
+      }
+  MonitorEnv m{};
+  m.nchunks = (int)chunks.size();
+  MonitorChunk* dch = nullptr;
+  MonitorBlob* dbl = nullptr;
+  const int rc = [&]() -> int {
+    TRY(dalloc(c, &dch, chunks.size()));
+    m.chunks = dch;
+    TRY(dalloc(c, &dbl, blobs.size()));
+    m.blobs = dbl;
+    TRY(dalloc(c, &m.psum, chunks.size()));
+    TRY(dalloc(c, &m.pnf, chunks.size()));
+    TRY(dalloc(c, &m.ticket, 4));
+    TRY(dalloc(c, &m.count, 2));
+    TRY(dalloc(c, &m.ring, (size_t)capacity));
+    HIP_TRY(c, scopy(c, dch, chunks.data(), chunks.size() * sizeof(MonitorChunk),
+                     hipMemcpyHostToDevice));
+    HIP_TRY(c, scopy(c, dbl, blobs.data(), blobs.size() * sizeof(MonitorBlob),
+                     hipMemcpyHostToDevice));
+    return DDQ_OK;
+  }();
+  m.t[0] = c->nb.theta[0];
+  m.t[1] = c->nb.theta[1];
+  m.t[2] = c->nb.grad;
+  m.capacity = capacity;
+  m.iter = c->nb.iter;
+  m.loss = c->nb.loss;
+  m.q_out = c->nb.q_out;
+  m.B = c->nb.B;
+  c->mon = m;
+  if (rc != DDQ_OK) {
+    const std::string msg = c->err;
+    monitor_release(c);
+    c->err = msg;
+    return rc;
+  }
+  c->mon_period = period;
+  return DDQ_OK;
+}
+
+int ddq_monitor_record_async(ddq_ctx* c, int64_t tag) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->mon.ring) return fail(c, DDQ_ESTATE, "monitor not enabled (ddq_monitor_enable)");
+  TRY(set_dev(c));
+  HIP_TRY(c, launch_monitor(c->mon, 0, tag, c->stream));
+  return DDQ_OK;
+}
+
+int ddq_monitor_read(ddq_ctx* c, int64_t first, int64_t n, ddq_monitor_record* out,
+                     int64_t* total) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->mon.ring) return fail(c, DDQ_ESTATE, "monitor not enabled (ddq_monitor_enable)");
+  if (n < 0 || (n > 0 && !out)) return fail(c, DDQ_EINVAL, "bad argument");
+  TRY(set_dev(c));
+  int64_t cnt = 0;
+  HIP_TRY(c, scopy(c, &cnt, c->mon.count, sizeof(cnt), hipMemcpyDeviceToHost));
+  if (total) *total = cnt;
+  if (n == 0) return DDQ_OK;
+  const int64_t cap = c->mon.capacity;
+  if (first < 0 || first + n > cnt || cnt - first > cap)
+    return fail(c, DDQ_EINVAL, "records [%lld, %lld) not in the ring (taken %lld, capacity %lld)",
+                (long long)first, (long long)(first + n), (long long)cnt, (long long)cap);
+  for (int64_t k = first; k < first + n;) {   // at most two spans of the ring
+    const int64_t slot = k % cap, run = std::min(first + n - k, cap - slot);
+    HIP_TRY(c, hipMemcpyAsync(out + (k - first), c->mon.ring + slot,
+                              (size_t)run * sizeof(MonitorRecord), hipMemcpyDeviceToHost,
+                              c->stream));
+    k += run;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return DDQ_OK;
+}
+
 // ---------------- measurement ----------------
 // A mark names the kernel launched next: arm that launch's own start / stop
 // events (common.h ddq_launch).  A mark no kernel follows (an RCCL call, the
@@ -2500,6 +2673,7 @@ static void mark_cb(void* arg, const char* name) {
 int ddq_profile_step(ddq_ctx* c, const ddq_step_cfg* cfg, char* names, float* usec, int32_t cap,
                      int32_t* n) {
   TRY(check_step(c, cfg));
+  TRY(check_monitor_step(c, cfg));
   if (!n) return fail(c, DDQ_EINVAL, "null n");
   if (is_async(c, cfg)) return fail(c, DDQ_EINVAL, "profile steps take no async exchange");
   TRY(check_not_async(c));

@@ -264,6 +264,46 @@ struct EvalEnv {
 // slice of eval_in.  A game whose log is full does nothing.
 hipError_t launch_eval_env(const EvalEnv& e, const float* q, uint64_t thresh, int play,
                            hipStream_t s);
+// Device-resident training monitor (monitor.h).  MonitorRecord is
+// ddq_monitor_record (include/ddq_hip.h), field for field.
+struct MonitorRecord {
+  int64_t iteration, tag;
+  float loss, q_max_mean;
+  int32_t nonfinite[3], reserved;
+  float param_rms[2][10], grad_rms[10];
+};
+constexpr int kMonChunk = 8192;     // floats per chunk: one workgroup's share
+constexpr int kMonBlobs = 30;       // (theta_Q, theta_P, grad) x the layout's 10 blobs
+// one workgroup's floats: [off, off + count) of tensor `tensor`, inside one blob
+struct MonitorChunk {
+  int32_t tensor, blob;
+  uint32_t off;
+  int32_t count;
+};
+// blob tensor * 10 + b: its chunks are chunks[first .. first + n), in offset order
+struct MonitorBlob {
+  int32_t first, n;
+  int64_t count;
+};
+struct MonitorEnv {
+  const float* t[3];                // theta_Q, theta_P, grad
+  const MonitorChunk* chunks;
+  const MonitorBlob* blobs;         // [kMonBlobs]
+  int nchunks;
+  double* psum;                     // [nchunks] sums of squares
+  int32_t* pnf;                     // [nchunks] non-finite counts
+  int32_t* ticket;                  // arrivals of this launch (0 between launches)
+  int64_t* count;                   // records taken since enable
+  MonitorRecord* ring;
+  int64_t capacity;
+  const int64_t* iter;
+  const float* loss;
+  const float* q_out;
+  int B;
+};
+// One record (chunks' workgroups, the last to finish writes it); period > 0:
+// only when *iter % period == 0 (every workgroup returns at once otherwise).
+hipError_t launch_monitor(const MonitorEnv& e, int32_t period, int64_t tag, hipStream_t s);
 // large-batch device draw (bitmap claim + ordered compaction) into idx[0..n)
 // and the Caffe-layout (n,4,S,S) f32 gather of replay.py:167-183
 hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t seed,

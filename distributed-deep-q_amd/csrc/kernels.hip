@@ -2313,3 +2313,5 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
 #include "actor.h"
 // the device-resident evaluator's environment step: one game per workgroup
 #include "eval.h"
+// the training monitor's reduction: one workgroup per chunk, one record
+#include "monitor.h"

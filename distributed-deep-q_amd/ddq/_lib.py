@@ -57,6 +57,14 @@ class StepCfg(ctypes.Structure):
                 ("overlap", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class MonitorRecord(ctypes.Structure):
+    """include/ddq_hip.h ddq_monitor_record (160 bytes)."""
+    _fields_ = [("iteration", ctypes.c_int64), ("tag", ctypes.c_int64),
+                ("loss", ctypes.c_float), ("q_max_mean", ctypes.c_float),
+                ("nonfinite", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32),
+                ("param_rms", (ctypes.c_float * 10) * 2), ("grad_rms", ctypes.c_float * 10)]
+
+
 STEP_NO_GRAD_STORE = 1     # include/ddq_hip.h DDQ_STEP_NO_GRAD_STORE
 FAULT_NONE, FAULT_MEET_TIMEOUT = 0, 1   # include/ddq_hip.h enum ddq_fault
 
@@ -139,6 +147,9 @@ _SIGS = {
     "ddq_async_ready": (ctypes.c_int, [_P, ctypes.POINTER(_i32)]),
     "ddq_async_tick": (ctypes.c_int, [_P, ctypes.POINTER(StepCfg), _i32]),
     "ddq_set_straggle": (ctypes.c_int, [_P, _i64]),
+    "ddq_monitor_enable": (ctypes.c_int, [_P, _i64, _i32]),
+    "ddq_monitor_record_async": (ctypes.c_int, [_P, _i64]),
+    "ddq_monitor_read": (ctypes.c_int, [_P, _i64, _i64, _P, ctypes.POINTER(_i64)]),
     "ddq_profile_step": (ctypes.c_int, [_P, ctypes.POINTER(StepCfg), _P, _fp, _i32,
                                         ctypes.POINTER(_i32)]),
     "ddq_time_layer": (ctypes.c_int, [_P, ctypes.c_char_p, _i32, _fp]),

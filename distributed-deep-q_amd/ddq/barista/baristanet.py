@@ -28,7 +28,7 @@ import numpy as np
 
 from ..net import DeepQNet, GAMMA
 from .. import params as P
-from . import messaging
+from . import messaging, netutils
 
 
 def parse_architecture(architecture):
@@ -80,9 +80,10 @@ class BaristaNet:
         self.dqn.sync_target()
         self.dataset = None
         self.driver = driver
-        # logpath / reset_log: accepted for signature compatibility; the
-        # reference's per-step norm logging (netutils.NetLogger) is monitoring,
-        # out of scope here
+        # logpath: the reference's per-step loss / norm files (baristanet.py:45-46,
+        # netutils.NetLogger), from records of the device-resident monitor; None
+        # (what main.py passes unless --logpath is given): log() does nothing
+        self.logger = netutils.NetLogger(self, logpath, reset_log) if logpath else None
         B, S = batch, frame
         self.state = np.zeros((B, 4, S, S), np.float32)
         self.action = np.zeros((B, 4, 1, 1), np.float32)
@@ -201,4 +202,9 @@ class BaristaNet:
         return int(a[0]) if (batch_size == 1 and n == 1) else a[:max(batch_size, n)]
 
     def log(self):
-        """Monitoring hook of the reference (NetLogger); a no-op here."""
+        """baristanet.py:148-149: append this step's loss and the RMS of every
+        blob's gradient and parameters to the log files (one device monitor
+        record); nothing without a logpath.  Returns the record or None."""
+        if self.logger is None:
+            return None
+        return self.logger.write()

@@ -7,7 +7,7 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
     python -m ddq.barista.main <train_val.prototxt> <model.npz|none>
         [--port 50001] [--driver 127.0.0.1:5500|None] [--dataset replay-dataset.hdf5]
         [--dset-size 1000] [--overwrite] [--debug] [--initial-replay 20000]
-        [--device-actor [--actor-seed N]]
+        [--device-actor [--actor-seed N]] [--logpath PREFIX]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
 step on the host through the CPU twin libddq_cpu.so (main.py:128,149-151, the
@@ -17,6 +17,10 @@ reference's Caffe CPU mode: BASELINE configs[0]).
 ``ddq.actor.DeviceActor``: the game, the preprocessing, the ε-greedy choice and
 the replay add run inside the net's context (ddq_actor_step_async), so
 ``generate_experience`` only enqueues.
+
+``--logpath PREFIX`` (off by default) makes ``net.log()`` append the step's loss
+and every blob's gradient / parameter RMS to files under ``PREFIX-<date>``
+(netutils.NetLogger), from one record of the device-resident monitor.
 """
 from __future__ import annotations
 
@@ -91,6 +95,8 @@ def get_args(argv=None):
                     help="act on the device (ddq.actor.DeviceActor) instead of the host ExpGain")
     ap.add_argument("--actor-seed", dest="actor_seed", type=int, default=None,
                     help="seed of the device actor's random stream (default: random)")
+    ap.add_argument("--logpath", default=None,
+                    help="prefix of the per-step loss / norm log directory (default: no log)")
     args = ap.parse_args(argv)
     if args.driver == "None":
         args.driver = None
@@ -99,7 +105,8 @@ def get_args(argv=None):
 
 def build_worker(args):
     model = None if args.model in ("none", "None") else args.model
-    net = BaristaNet(args.architecture, model, args.driver, logpath=None, mode=args.mode)
+    net = BaristaNet(args.architecture, model, args.driver,
+                     logpath=getattr(args, "logpath", None), mode=args.mode)
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
                            overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode)
     net.add_dataset(replay)

@@ -22,6 +22,11 @@ NFRAME = 4          # expgain.py:9
 
 BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0}
 
+# include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
+MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
+                          ("q_max_mean", "<f4"), ("nonfinite", "<i4", (3,)), ("reserved", "<i4"),
+                          ("param_rms", "<f4", (2, 10)), ("grad_rms", "<f4", (10,))])
+
 
 class DeepQNet:
     """Device-resident deepq network (both towers) + minibatch + replay ring."""
@@ -292,6 +297,35 @@ class DeepQNet:
                                            ptr(log) if me else None, ptr(boards), ptr(draws)))
         return {"stats": stats, "episodes": episodes, "log": log, "boards": boards,
                 "draws": draws}
+
+    # ----------------------------------------------------------------- monitor
+    def monitor_enable(self, capacity, period=0):
+        """Device ring of ``capacity`` monitor records (0 disables).  period 0:
+        explicit records only (monitor_record); period > 0: every single-ctx
+        step whose iteration after the update is a multiple of it appends a
+        record (tag -1) as its last launch (ddq_monitor_enable)."""
+        self._check(self.lib.ddq_monitor_enable(self.ctx, int(capacity), int(period)))
+        self._monitor_cap = int(capacity)
+
+    def monitor_record(self, tag=0):
+        """One record of the ctx as it is now; enqueued, no sync."""
+        self._check(self.lib.ddq_monitor_record_async(self.ctx, int(tag)))
+
+    def monitor_read(self, first=None, n=None):
+        """Synchronise; (records, total): ``records`` a MONITOR_DTYPE array of
+        records first .. first+n-1 (default: everything still in the ring),
+        ``total`` the number of records taken since monitor_enable."""
+        total = _lib._i64()
+        self._check(self.lib.ddq_monitor_read(self.ctx, 0, 0, None, ctypes.byref(total)))
+        total = int(total.value)
+        if first is None:
+            first = max(0, total - getattr(self, "_monitor_cap", 0))
+        if n is None:
+            n = max(0, total - int(first))
+        out = np.zeros(int(n), MONITOR_DTYPE)
+        if n:
+            self._check(self.lib.ddq_monitor_read(self.ctx, int(first), int(n), ptr(out), None))
+        return out, total
 
     # ------------------------------------------------------------------- apply
     def apply(self, rule="rmsprop", lr=1e-4, decay=0.9, eps=1e-8, momentum=0.9,

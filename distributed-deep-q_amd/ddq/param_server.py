@@ -18,7 +18,12 @@ Semantics kept:
   unbounded staleness;
 * ``snapshot_frequency`` (:74-77): every that many iterations the model is
   handed to ``on_snapshot(name, params)`` (Celery's ``saveSnapshot`` in the
-  reference; a callback here).
+  reference; a callback here);
+* ``stats_frequency`` (:203-204, "Monitoring stats not implemented" in the
+  reference): with ``on_stats`` given, every that many iterations one record of
+  the device-resident monitor (the RMS of every blob of the model just applied
+  and of the gradient just pushed, tagged with the iteration) is handed to
+  ``on_stats(iteration, record)``.
 The apply runs in ``apply_kernel`` on the device (``ddq_set_grads`` +
 ``ddq_apply``), not in numpy.
 """
@@ -44,7 +49,7 @@ def get_snapshot_name(iteration):
 class ParamServer:
     def __init__(self, frame=16, batch=32, update="rmsprop", lr=1e-4, rmsprop_decay=0.9,
                  special_update=10, snapshot_freq=500, stats_freq=500, device=0,
-                 on_snapshot=None, mode="gpu"):
+                 on_snapshot=None, mode="gpu", on_stats=None):
         if update not in ("sgd", "rmsprop", "adagrad"):
             raise ValueError("update must be one of adagrad, rmsprop, sgd")
         self.net = DeepQNet(batch=batch, frame=frame, device=device, mode=mode)
@@ -55,6 +60,12 @@ class ParamServer:
         self.snapshot_frequency = int(snapshot_freq)
         self.stats_frequency = int(stats_freq)
         self.on_snapshot = on_snapshot
+        # server.py:203-204 ("Monitoring stats not implemented" there): with a
+        # callback, every stats_frequency-th push takes one device monitor
+        # record after its apply; without one nothing is enabled
+        self.on_stats = on_stats
+        if on_stats is not None:
+            self.net.monitor_enable(4, 0)
         self.iteration = 0
         self.has_model = False
         self.has_target = False
@@ -114,6 +125,12 @@ class ParamServer:
             if self.snapshot_frequency and self.iteration % self.snapshot_frequency == 0 \
                     and self.on_snapshot is not None:
                 self.on_snapshot(get_snapshot_name(self.iteration), self.model_params())
+            if self.on_stats is not None and self.stats_frequency and \
+                    self.iteration % self.stats_frequency == 0:
+                self.net.monitor_record(self.iteration)
+                _, total = self.net.monitor_read(0, 0)
+                recs, _ = self.net.monitor_read(total - 1, 1)
+                self.on_stats(self.iteration, recs[0])
         return b"Updated"
 
     # ---------------------------------------------------------------- HTTP

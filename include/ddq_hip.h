@@ -43,7 +43,9 @@ extern "C" {
                               (ddq_actor_create, ddq_actor_step_async, ddq_actor_read):
                               new symbols only, nothing else changed; and then the
                               device evaluator (ddq_eval_create, ddq_eval_run_async,
-                              ddq_eval_read), again new symbols only */
+                              ddq_eval_read), again new symbols only; and the
+                              training monitor (ddq_monitor_enable,
+                              ddq_monitor_record_async, ddq_monitor_read), likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -420,6 +422,52 @@ int ddq_group_async_ticks(ddq_ctx** ctxs, int32_t nranks, const ddq_step_cfg* cf
  * becomes pushable (ddq_async_ready, ticket runs) usec of host time after it
  * is computed -- a slow worker loop, without occupying the GPU.  0 disables. */
 int ddq_set_straggle(ddq_ctx* ctx, int64_t usec);
+
+/* ---------------- training monitor (barista/netutils.py NetLogger) ------- */
+/* The quantities net.log() appends after every step (baristanet.py:148-149,
+ * netutils.py:72-96): the loss, and the RMS of every blob's gradient and
+ * parameters, np.linalg.norm(ravel(x)) / sqrt(x.size) (netutils.py:15-17),
+ * taken on the device by one deterministic reduction launch and appended to a
+ * device ring of fixed-size records; the host reads the ring whenever it likes.
+ * A record is a snapshot of the ctx at the point in stream order where it is
+ * taken: the current theta_Q and theta_P, the gradient buffer, the loss blob
+ * and Q_out.  Squares are summed in double in a fixed order (no float atomics),
+ * each RMS is rounded to fp32 once. */
+typedef struct ddq_monitor_record {
+  int64_t iteration;        /* device applied-updates counter when taken            */
+  int64_t tag;              /* caller's tag (explicit record); -1 for a step's own  */
+  float   loss;             /* the loss blob, as ddq_read_blob("loss") returns it   */
+  float   q_max_mean;       /* mean over the B images of max_a Q_out[b][a]          */
+  int32_t nonfinite[3];     /* count of non-finite values in theta_Q, theta_P, grads */
+  int32_t reserved;         /* 0 */
+  float   param_rms[2][10]; /* [Q,P][blob]: sqrt(sum x^2 / count), ddq_param_layout order */
+  float   grad_rms[10];     /* the gradient buffer's blobs (what ddq_get_grads returns)   */
+} ddq_monitor_record;       /* 160 bytes */
+
+/* Allocate a device ring of `capacity` records and reset the record count;
+ * capacity == 0 disables the monitor and frees the ring.  Invalidates graphs.
+ * period == 0: explicit records only (ddq_monitor_record_async).  period > 0:
+ * every single-ctx step (ddq_step_async, ddq_step_graph_async,
+ * ddq_step_pipelined_async, ddq_profile_step: kernel "monitor") ends with the
+ * monitor launch, which takes a record (tag -1) when the device iteration after
+ * the step's update satisfies iteration % period == 0; the kernel makes that
+ * test itself, so captured steps replay it.  Such a record holds the step's
+ * loss_t and gradient g_t and the parameters AFTER update t (theta_P after the
+ * step's P <- Q copy when one was due).  While period > 0 a step with
+ * DDQ_STEP_NO_GRAD_STORE is refused (DDQ_EINVAL: its gradient block would be
+ * stale) and so is ddq_async_begin (DDQ_ESTATE); ddq_group_step and the async
+ * ticks take no records of their own.  With the monitor off (the default)
+ * every step is launch for launch what it was. */
+int ddq_monitor_enable(ddq_ctx* ctx, int64_t capacity, int32_t period);
+/* One record now, with `tag`: enqueued on the ctx stream, no sync.  After a
+ * worker's forward_backward it holds the reference's quantities exactly (the
+ * fetched theta, this step's gradient and loss).  DDQ_ESTATE while disabled. */
+int ddq_monitor_record_async(ddq_ctx* ctx, int64_t tag);
+/* Synchronise; *total (nullable) = records taken since enable; copy records
+ * [first, first+n), which must be among the last `capacity` taken (DDQ_EINVAL
+ * otherwise).  out may be NULL with n == 0. */
+int ddq_monitor_read(ddq_ctx* ctx, int64_t first, int64_t n, ddq_monitor_record* out,
+                     int64_t* total);
 
 /* ---------------- measurement ------------------------------------------ */
 /* Kernel ids for ddq_profile_step. */
