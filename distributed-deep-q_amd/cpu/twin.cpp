@@ -92,6 +92,10 @@ struct ddq_ctx {
   std::vector<uint8_t> r_state, r_action, r_nonterm;
   std::vector<int16_t> r_reward;
   int64_t head = 0, valid = 0, capacity = 0;
+  // laned ring (ddq_replay_set_lanes): lanes rings of lane_len slots, head /
+  // valid per lane
+  int32_t lanes = 1;
+  int64_t lane_len = 0;
   int64_t steps = 0;
   // Snake actor (ddq_actor_*): 4-board history (oldest first), the start board,
   // the zoom maps and the RNG stream position
@@ -114,6 +118,14 @@ struct ddq_ctx {
   double e_eps = 0.0;
   int32_t e_max_moves = 0, e_max_ep = 0;
   int64_t e_moves = 0;
+  // actor pool (ddq_actors_*): one game per ring lane, in lock step
+  struct PoolGame {
+    uint64_t seed = 0, draws = 0;
+    int64_t steps = 0, games = 0, reward = 0;
+    int8_t boards[4][100], init[100];
+  };
+  std::vector<PoolGame> p_games;   // empty: no pool
+  std::vector<int32_t> p_row, p_col;
   // training monitor (ddq_monitor_*): the ring (empty: off) and the records taken
   std::vector<ddq_monitor_record> m_ring;
   int64_t m_total = 0;
@@ -445,7 +457,8 @@ void gather(ddq_ctx* c) {
   const size_t slot = (size_t)kC * SS;
   for (int b = 0; b < B; ++b) {
     const int64_t i = c->idx[b];
-    const int64_t nxt = i + 1 == c->capacity ? 0 : i + 1;   // replay.py:159-183
+    // replay.py:159-183, the next slot within the lane (one lane: the ring)
+    const int64_t nxt = (i + 1) % c->lane_len == 0 ? i + 1 - c->lane_len : i + 1;
     for (size_t e = 0; e < slot; ++e) {
       c->state[(size_t)b * slot + e] = c->r_state[(size_t)i * slot + e];
       c->next_state[(size_t)b * slot + e] = c->r_state[(size_t)nxt * slot + e];
@@ -612,12 +625,40 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->r_nonterm.assign(capacity, 0);
   c->capacity = capacity;
   c->head = c->valid = 0;
+  c->lanes = 1;
+  c->lane_len = capacity;
+  return DDQ_OK;
+}
+
+int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->valid != 0)
+    return fail(c, DDQ_ESTATE, "set_lanes needs an empty ring (valid = %lld)", (long long)c->valid);
+  if (lanes < 1 || c->capacity % lanes != 0 || c->capacity / lanes < 2)
+    return fail(c, DDQ_EINVAL, "lanes must divide capacity %lld into lanes of >= 2 slots (got %d)",
+                (long long)c->capacity, lanes);
+  if (lanes == c->lanes) return DDQ_OK;
+  c->lanes = lanes;
+  c->lane_len = c->capacity / lanes;
+  c->head = 0;
+  c->p_games.clear();                // a pool or an actor belongs to the lanes it was
+  c->actor = false;                  // created on
+  return DDQ_OK;
+}
+
+int ddq_replay_lanes(const ddq_ctx* c, int32_t* lanes, int64_t* lane_len) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->capacity) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  if (lanes) *lanes = c->lanes;
+  if (lane_len) *lane_len = c->lane_len;
   return DDQ_OK;
 }
 
 int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* state) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->lanes > 1) return fail(c, DDQ_ESTATE, "ddq_replay_add on a laned ring (%d lanes)", c->lanes);
   if (action < 0 || action > 255) return fail(c, DDQ_EINVAL, "action must fit uint8");
   if (reward < -32768 || reward > 32767) return fail(c, DDQ_EINVAL, "reward must fit int16");
   const size_t slot = (size_t)kC * c->S * c->S;
@@ -647,7 +688,7 @@ int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
   if (n != c->capacity)
     return fail(c, DDQ_EINVAL, "import size %lld != capacity %lld", (long long)n,
                 (long long)c->capacity);
-  if (head < 0 || head >= n || valid < 0 || valid > n)
+  if (head < 0 || head >= c->lane_len || valid < 0 || valid > c->lane_len)
     return fail(c, DDQ_EINVAL, "head/valid out of range");
   const size_t slot = (size_t)kC * c->S * c->S;
   std::copy(state, state + slot * n, c->r_state.begin());
@@ -674,17 +715,17 @@ int ddq_replay_export(ddq_ctx* c, uint8_t* state, uint8_t* action, int16_t* rewa
 int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   if (!c || !idx) return fail(c, DDQ_EINVAL, "null argument");
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer");
-  if (batch >= c->valid)
+  if (batch > c->lanes * (c->valid - 1))   // B < valid on a plain ring
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
-                batch, (long long)c->valid);
+                batch, (long long)(c->lanes * c->valid));
   if (batch != c->B) return fail(c, DDQ_EINVAL, "sample size %d != net batch %d", batch, c->B);
   for (int i = 0; i < batch; ++i) {
-    if (idx[i] < 0 || idx[i] >= c->valid)
+    if (idx[i] < 0 || idx[i] >= c->capacity || idx[i] % c->lane_len >= c->valid)
       return fail(c, DDQ_EINVAL, "index %d out of [0,valid)", idx[i]);
     if (i && idx[i] <= idx[i - 1]) return fail(c, DDQ_EINVAL, "indices must be sorted and distinct");
   }
   for (int i = 0; i < batch; ++i) {
-    const int64_t nxt = idx[i] + 1 == c->capacity ? 0 : idx[i] + 1;
+    const int64_t j = idx[i] + 1, nxt = j % c->lane_len == 0 ? j - c->lane_len : j;
     if (c->r_action[nxt] >= kA)
       return fail(c, DDQ_ERANGE, "stored action index out of range for %d actions", kA);
   }
@@ -721,16 +762,24 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
 
 int ddq_replay_fill_tiled(ddq_ctx* c, const uint8_t*, const uint8_t*, const int16_t*,
                           const uint8_t*, int64_t, int64_t, int64_t) {
+  if (c && c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "ddq_replay_fill_tiled on a laned ring (%d lanes)", c->lanes);
   return cpu_only(c, "ddq_replay_fill_tiled");
 }
 
 int ddq_replay_sample_batch_async(ddq_ctx* c, int32_t, uint64_t, int32_t*, float*, float*, float*,
                                   float*, float*) {
+  if (c && c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "the large-batch sampler does not read a laned ring (%d lanes)",
+                c->lanes);
   return cpu_only(c, "ddq_replay_sample_batch_async");
 }
 
 int ddq_replay_gather_batch_async(ddq_ctx* c, const int32_t*, int32_t, float*, float*, float*,
                                   float*, float*) {
+  if (c && c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "the large-batch sampler does not read a laned ring (%d lanes)",
+                c->lanes);
   return cpu_only(c, "ddq_replay_gather_batch_async");
 }
 
@@ -950,6 +999,9 @@ int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_ma
   if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
     return fail(c, DDQ_EINVAL, "init_board: head and neck are not neighbours");
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "ddq_actor_create on a laned ring (%d lanes): use ddq_actors_create",
+                c->lanes);
   memcpy(c->a_init, init_board, 100);
   for (auto& b : c->a_boards) memcpy(b, init_board, 100);
   c->a_row.assign(row_map, row_map + c->S);
@@ -1094,6 +1146,112 @@ int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, i
     if (draws) draws[g] = eg.draws;
   }
   if (stats) { stats[0] = c->e_moves; stats[1] = eps; stats[2] = rew; stats[3] = dr; }
+  return DDQ_OK;
+}
+
+// ---- actor pool: ngames lock-step actors, game g adding into ring lane g ----
+int ddq_actors_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards,
+                      const int32_t* row_map, const int32_t* col_map, uint64_t seed) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
+  if (ngames < 1 || ngames > c->B)
+    return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, c->B);
+  for (int i = 0; i < c->S; ++i)
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+  for (int g = 0; g < ngames; ++g) {
+    const int8_t* b = init_boards + 100 * g;
+    std::vector<Cell> body;
+    if (!snake_body(b, &body) || body.size() < 2)
+      return fail(c, DDQ_EINVAL, "init_boards[%d]: snake cells must be the codes 0..k-1, k >= 2", g);
+    if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
+      return fail(c, DDQ_EINVAL, "init_boards[%d]: head and neck are not neighbours", g);
+  }
+  if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (ngames != c->lanes)
+    return fail(c, DDQ_EINVAL, "ngames %d != the ring's %d lanes (ddq_replay_set_lanes)", ngames,
+                c->lanes);
+  c->p_games.assign(ngames, ddq_ctx::PoolGame{});
+  for (int g = 0; g < ngames; ++g) {
+    ddq_ctx::PoolGame& pg = c->p_games[g];
+    pg.seed = mix64(mix64(seed) ^ (uint64_t)g);
+    memcpy(pg.init, init_boards + 100 * g, 100);
+    for (auto& b : pg.boards) memcpy(b, pg.init, 100);
+  }
+  c->p_row.assign(row_map, row_map + c->S);
+  c->p_col.assign(col_map, col_map + c->S);
+  return DDQ_OK;
+}
+
+int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->p_games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
+  const double eps = actor_eps(iter_num);
+  const int n = (int)c->p_games.size(), S = c->S;
+  const size_t fs = (size_t)kC * S * S;
+  std::vector<uint8_t> frames(n * fs);
+  std::vector<int32_t> greedy(n);
+  auto render = [&](const ddq_ctx::PoolGame& pg, uint8_t* out) {
+    for (int f = 0; f < kC; ++f)
+      for (int i = 0; i < S; ++i)
+        for (int j = 0; j < S; ++j) {
+          const int v = pg.boards[f][c->p_row[i] * 10 + c->p_col[j]];
+          out[((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
+        }
+  };
+  for (int m = 0; m < nmoves; ++m) {
+    for (int g = 0; g < n; ++g) render(c->p_games[g], frames.data() + g * fs);
+    const int rc = ddq_select_action(c, frames.data(), n, greedy.data());
+    if (rc != DDQ_OK) return rc;
+    const int64_t h = c->head;
+    for (int g = 0; g < n; ++g) {
+      ddq_ctx::PoolGame& pg = c->p_games[g];
+      auto next_draw = [&pg]() { return mix64(pg.seed ^ mix64(pg.draws++)); };
+      auto randrange = [&](uint64_t k) {
+        return (uint64_t)(((unsigned __int128)next_draw() * k) >> 64);
+      };
+      int act = greedy[g];
+      if ((double)(next_draw() >> 11) * 0x1.0p-53 < eps) act = (int)randrange(kA);   // always a coin
+      int8_t next[100];
+      const int reward = snake_play(pg.boards[3], act, next, randrange);
+      const bool over = reward < 0;
+      // add_experience into lane g's slot h
+      const int64_t slot = (int64_t)g * c->lane_len + h;
+      c->r_action[slot] = (uint8_t)act;
+      c->r_reward[slot] = (int16_t)reward;
+      c->r_nonterm[slot] = over ? 0 : 1;
+      if (over) {   // the slot keeps its old frames
+        for (auto& b : pg.boards) memcpy(b, pg.init, 100);   // reset_game
+      } else {
+        memmove(pg.boards[0], pg.boards[1], 300);
+        memcpy(pg.boards[3], next, 100);
+        render(pg, c->r_state.data() + (size_t)slot * fs);
+      }
+      pg.steps += 1;
+      pg.games += over;
+      pg.reward += reward;
+    }
+    c->head = (h + 1) % c->lane_len;
+    c->valid = std::min(c->lane_len, c->valid + 1);
+  }
+  return DDQ_OK;
+}
+
+int ddq_actors_read(ddq_ctx* c, int8_t* boards, int64_t* stats, int64_t* totals) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->p_games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  int64_t tot[4] = {0, 0, 0, 0};
+  for (size_t g = 0; g < c->p_games.size(); ++g) {
+    const ddq_ctx::PoolGame& pg = c->p_games[g];
+    const int64_t st[4] = {pg.steps, pg.games, pg.reward, (int64_t)pg.draws};
+    for (int k = 0; k < 4; ++k) {
+      tot[k] += st[k];
+      if (stats) stats[4 * g + k] = st[k];
+    }
+    if (boards) memcpy(boards + 400 * g, pg.boards, 400);
+  }
+  if (totals) memcpy(totals, tot, sizeof(tot));
   return DDQ_OK;
 }
 

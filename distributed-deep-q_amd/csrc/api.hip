@@ -51,6 +51,8 @@ struct ddq_ctx {
   int32_t* r_blk = nullptr;
   uint64_t batch_ctr = 0;          // large-batch draws so far (RNG stream position)
   int64_t head = 0, valid = 0, capacity = 0;
+  int32_t lanes = 1;               // laned ring (ddq_replay_set_lanes): head / valid per lane
+  int64_t lane_len = 0;            // capacity / lanes
   // acting scratch
   uint8_t* act_u8 = nullptr;
   float *act_in = nullptr, *act_p3 = nullptr;
@@ -72,6 +74,13 @@ struct ddq_ctx {
   int e_n = 0, e_max_moves = 0, e_max_ep = 0;   // e_n = 0: no evaluator
   uint64_t e_thresh = 0;
   int64_t e_moves = 0;             // lock-step moves enqueued since create
+  // device actor pool (ddq_actors_create): B games' state and input, the zoom
+  // maps, the ring's per-lane head / valid at create
+  ActorState* p_games = nullptr;
+  uint8_t* p_maps = nullptr;
+  float* p_in = nullptr;
+  int p_n = 0;                     // 0: no pool
+  int64_t p_h0 = 0, p_v0 = 0, p_moves = 0;
   // index log (ddq_index_log_enable)
   int32_t* log_buf = nullptr;
   int64_t log_buf_cap = 0;
@@ -601,8 +610,12 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   TRY(dalloc(c, &c->r_nonterm, (size_t)capacity));
   c->capacity = capacity;
   c->head = c->valid = 0;
+  c->lanes = 1;
+  c->lane_len = capacity;
   ReplayMeta m{};
   m.capacity = capacity;
+  m.lanes = 1;
+  m.lane_len = capacity;
   HIP_TRY(c, scopy(c, c->r_meta, &m, sizeof(m), hipMemcpyHostToDevice));
   invalidate_graph(c);
   return DDQ_OK;
@@ -611,6 +624,7 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
 int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* state) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->lanes > 1) return fail(c, DDQ_ESTATE, "ddq_replay_add on a laned ring (%d lanes)", c->lanes);
   if (action < 0 || action > 255) return fail(c, DDQ_EINVAL, "action must fit uint8");
   if (reward < -32768 || reward > 32767) return fail(c, DDQ_EINVAL, "reward must fit int16");
   TRY(set_dev(c));
@@ -636,6 +650,41 @@ int ddq_replay_info(const ddq_ctx* c, int64_t* head, int64_t* valid, int64_t* ca
   return DDQ_OK;
 }
 
+// fewest filled, allowed slots a draw of B needs: B <= lanes * (valid - 1),
+// which is B < valid on a plain ring
+static bool too_few_slots(const ddq_ctx* c, int64_t batch) {
+  return batch > c->lanes * (c->valid - 1);
+}
+
+int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->valid != 0) return fail(c, DDQ_ESTATE, "set_lanes needs an empty ring (valid = %lld)",
+                                 (long long)c->valid);
+  if (lanes < 1 || c->capacity % lanes != 0 || c->capacity / lanes < 2)
+    return fail(c, DDQ_EINVAL, "lanes must divide capacity %lld into lanes of >= 2 slots (got %d)",
+                (long long)c->capacity, lanes);
+  if (lanes == c->lanes) return DDQ_OK;
+  TRY(set_dev(c));
+  c->lanes = lanes;
+  c->lane_len = c->capacity / lanes;
+  c->head = 0;
+  c->p_n = 0;                        // a pool or an actor belongs to the lanes it was
+  c->actor = false;                  // created on
+  char* m = reinterpret_cast<char*>(c->r_meta);
+  HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lanes), &c->lanes, 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lane_len), &c->lane_len, 8, hipMemcpyHostToDevice));
+  return push_meta(c);
+}
+
+int ddq_replay_lanes(const ddq_ctx* c, int32_t* lanes, int64_t* lane_len) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->r_state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  if (lanes) *lanes = c->lanes;
+  if (lane_len) *lane_len = c->lane_len;
+  return DDQ_OK;
+}
+
 int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
                       const int16_t* reward, const uint8_t* nonterm, int64_t n, int64_t head,
                       int64_t valid) {
@@ -643,7 +692,7 @@ int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (n != c->capacity) return fail(c, DDQ_EINVAL, "import size %lld != capacity %lld",
                                     (long long)n, (long long)c->capacity);
-  if (head < 0 || head >= n || valid < 0 || valid > n)
+  if (head < 0 || head >= c->lane_len || valid < 0 || valid > c->lane_len)
     return fail(c, DDQ_EINVAL, "head/valid out of range");
   TRY(set_dev(c));
   const size_t slot = (size_t)4 * c->nb.S * c->nb.S;
@@ -688,13 +737,14 @@ static int check_err_flag(ddq_ctx* c) {
 int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   if (!c || !idx) return fail(c, DDQ_EINVAL, "null argument");
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
-  if (batch >= c->valid)
+  if (too_few_slots(c, batch))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
-                batch, (long long)c->valid);
+                batch, (long long)(c->lanes * c->valid));
   if (batch != c->nb.B)
     return fail(c, DDQ_EINVAL, "sample size %d != net batch %d", batch, c->nb.B);
   for (int i = 0; i < batch; ++i) {
-    if (idx[i] < 0 || idx[i] >= c->valid) return fail(c, DDQ_EINVAL, "index %d out of [0,valid)", idx[i]);
+    if (idx[i] < 0 || idx[i] >= c->capacity || idx[i] % c->lane_len >= c->valid)
+      return fail(c, DDQ_EINVAL, "index %d out of [0,valid)", idx[i]);
     if (i && idx[i] <= idx[i - 1]) return fail(c, DDQ_EINVAL, "indices must be sorted and distinct");
   }
   TRY(set_dev(c));
@@ -707,9 +757,9 @@ int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
 int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
-  if (c->nb.B >= c->valid)
+  if (too_few_slots(c, c->nb.B))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
-                c->nb.B, (long long)c->valid);
+                c->nb.B, (long long)(c->lanes * c->valid));
   TRY(set_dev(c));
   HIP_TRY(c, launch_sample(c->nb, c->r_meta, seed, c->stream));
   HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
@@ -722,6 +772,8 @@ int ddq_replay_fill_tiled(ddq_ctx* c, const uint8_t* state, const uint8_t* actio
                           int64_t head, int64_t valid) {
   if (!c || !state || !action || !reward || !nonterm) return fail(c, DDQ_EINVAL, "null argument");
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "ddq_replay_fill_tiled on a laned ring (%d lanes)", c->lanes);
   const int64_t n = c->capacity;
   if (pool < 1 || pool > n) return fail(c, DDQ_EINVAL, "pool must be in [1, capacity]");
   if (head < 0 || head >= n || valid < 0 || valid > n)
@@ -750,6 +802,9 @@ static int check_batch_out(ddq_ctx* c, int32_t n, float* s0, float* a, float* r,
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!s0 || !a || !r || !s1 || !nt) return fail(c, DDQ_EINVAL, "null output buffer");
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "the large-batch sampler does not read a laned ring (%d lanes)",
+                c->lanes);
   if (n < 1) return fail(c, DDQ_EINVAL, "n must be >= 1");
   if ((int64_t)n * c->nb.S * c->nb.S >= (int64_t)1 << 31)
     return fail(c, DDQ_EINVAL, "n * S^2 must be < 2^31 (n=%d)", n);
@@ -1061,6 +1116,9 @@ int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_ma
   if (const char* why = actor_board_error(init_board))
     return fail(c, DDQ_EINVAL, "init_board: %s", why);
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->lanes > 1)
+    return fail(c, DDQ_ESTATE, "ddq_actor_create on a laned ring (%d lanes): use ddq_actors_create",
+                c->lanes);
   TRY(set_dev(c));
   if (!c->a_state) TRY(dalloc(c, &c->a_state, 1));
   if (!c->a_maps) TRY(dalloc(c, &c->a_maps, maps.size()));
@@ -1235,6 +1293,108 @@ int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, i
     if (draws) draws[g] = gs[g].draws;
   }
   if (stats) { stats[0] = c->e_moves; stats[1] = eps; stats[2] = rew; stats[3] = dr; }
+  return DDQ_OK;
+}
+
+// ---------------- device actor pool ----------------
+static PoolEnv pool_env(const ddq_ctx* c) {
+  PoolEnv e{};
+  e.games = c->p_games; e.maps = c->p_maps; e.pool_in = c->p_in; e.S = c->nb.S;
+  e.ngames = c->p_n; e.lane_len = c->lane_len; e.h0 = c->p_h0; e.v0 = c->p_v0;
+  e.r_state = c->r_state; e.r_action = c->r_action; e.r_reward = c->r_reward;
+  e.r_nonterm = c->r_nonterm; e.meta = c->r_meta;
+  return e;
+}
+
+int ddq_actors_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards,
+                      const int32_t* row_map, const int32_t* col_map, uint64_t seed) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
+  const int S = c->nb.S, B = c->nb.B;
+  if (ngames < 1 || ngames > B)
+    return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, B);
+  std::vector<uint8_t> maps(2 * (size_t)S);
+  for (int i = 0; i < S; ++i) {
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+    maps[i] = (uint8_t)row_map[i];
+    maps[S + i] = (uint8_t)col_map[i];
+  }
+  for (int g = 0; g < ngames; ++g)
+    if (const char* why = actor_board_error(init_boards + 100 * g))
+      return fail(c, DDQ_EINVAL, "init_boards[%d]: %s", g, why);
+  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (ngames != c->lanes)
+    return fail(c, DDQ_EINVAL, "ngames %d != the ring's %d lanes (ddq_replay_set_lanes)", ngames,
+                c->lanes);
+  TRY(set_dev(c));
+  c->p_n = 0;
+  if (!c->p_games) TRY(dalloc(c, &c->p_games, (size_t)B));
+  if (!c->p_maps) TRY(dalloc(c, &c->p_maps, maps.size()));
+  if (!c->p_in) TRY(dalloc(c, &c->p_in, (size_t)B * S * S * 4));
+  std::vector<ActorState> gs(ngames);
+  const uint64_t base = eval_mix64(seed);
+  for (int g = 0; g < ngames; ++g) {
+    gs[g] = ActorState{};
+    gs[g].seed = eval_mix64(base ^ (uint64_t)g);
+    for (int f = 0; f < 5; ++f) memcpy(gs[g].boards + f * 100, init_boards + 100 * g, 100);
+  }
+  HIP_TRY(c, scopy(c, c->p_games, gs.data(), gs.size() * sizeof(ActorState),
+                   hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->p_maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
+  c->p_n = ngames;
+  c->p_h0 = c->head;
+  c->p_v0 = c->valid;
+  c->p_moves = 0;
+  const hipError_t e = launch_pool_env(pool_env(c), c->act_q, 0, 0, c->stream);   // render only
+  if (e != hipSuccess) {
+    c->p_n = 0;
+    return fail(c, DDQ_EHIP, "pool render failed: %s", hipGetErrorString(e));
+  }
+  return DDQ_OK;
+}
+
+int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->p_n) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
+  // the games' slots come from (h0, v0) and their own step counters
+  if (c->head != (c->p_h0 + c->p_moves) % c->lane_len)
+    return fail(c, DDQ_ESTATE, "the ring's head moved since ddq_actors_create: create the pool again");
+  TRY(set_dev(c));
+  const uint64_t thresh = (uint64_t)std::ceil(actor_epsilon(iter_num) * 9007199254740992.0);
+  const PoolEnv e = pool_env(c);
+  for (int i = 0; i < nmoves; ++i) {
+    // the forward of ddq_select_action at n = ngames, on the pool's own input
+    HIP_TRY(c, launch_act(c->nb, c->p_in, c->p_n, c->act_p3, c->act_h4, c->act_part, c->act_q,
+                          nullptr, c->act_p1s, c->act_p2s, c->stream));
+    HIP_TRY(c, launch_pool_env(e, c->act_q, thresh, 1, c->stream));
+  }
+  // host mirror of the ring: one transition per lane and move
+  c->p_moves += nmoves;
+  c->head = (c->head + nmoves) % c->lane_len;
+  c->valid = std::min(c->lane_len, c->valid + nmoves);
+  return DDQ_OK;
+}
+
+int ddq_actors_read(ddq_ctx* c, int8_t* boards, int64_t* stats, int64_t* totals) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->p_n) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  TRY(set_dev(c));
+  const int n = c->p_n;
+  std::vector<ActorState> gs(n);
+  HIP_TRY(c, scopy(c, gs.data(), c->p_games, gs.size() * sizeof(ActorState),
+                   hipMemcpyDeviceToHost));
+  int64_t tot[4] = {0, 0, 0, 0};
+  for (int g = 0; g < n; ++g) {
+    const int64_t st[4] = {gs[g].steps, gs[g].games, gs[g].reward_sum, (int64_t)gs[g].draws};
+    for (int k = 0; k < 4; ++k) {
+      tot[k] += st[k];
+      if (stats) stats[4 * g + k] = st[k];
+    }
+    if (boards) memcpy(boards + 400 * g, gs[g].boards, 400);
+  }
+  if (totals) memcpy(totals, tot, sizeof(tot));
   return DDQ_OK;
 }
 
@@ -1610,9 +1770,9 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (!cfg) return fail(c, DDQ_EINVAL, "null step cfg");
   TRY(check_cfg(c, &cfg->update));
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
-  if (c->nb.B >= c->valid)
+  if (too_few_slots(c, c->nb.B))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
-                c->nb.B, (long long)c->valid);
+                c->nb.B, (long long)(c->lanes * c->valid));
   if (cfg->exchange < DDQ_EXCHANGE_NONE || cfg->exchange > DDQ_EXCHANGE_ASYNC)
     return fail(c, DDQ_EINVAL, "unknown exchange %d", cfg->exchange);
   if (cfg->flags & ~DDQ_STEP_NO_GRAD_STORE)

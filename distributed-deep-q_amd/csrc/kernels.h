@@ -24,12 +24,19 @@ ParamLayout make_layout(int S);
 
 // Replay ring bookkeeping kept in device memory so captured graphs see the
 // live head/valid and a fresh RNG counter on every replay.
+//
+// Laned ring (ddq_replay_set_lanes): lanes > 1 contiguous lanes of lane_len =
+// capacity / lanes slots, lane g = slots [g lane_len, (g + 1) lane_len), each a
+// ring of its own.  Lock-step writers fill it (pool.h), so the lanes share one
+// head in [0, lane_len) and one valid in [0, lane_len]: head / valid are then
+// the per-lane values.  lanes 0 or 1: one ring, lane_len == capacity.
 struct ReplayMeta {
-  int64_t head, valid, capacity;
+  int64_t head, valid, capacity;   // head, valid: the first 16 bytes (push_meta)
   uint64_t counter;        // device index-stream draws so far
   int32_t err;             // sticky: 1 = stored action >= num_actions seen,
                            //         2 = a draw found no distinct index set
-  int32_t pad;
+  int32_t lanes;
+  int64_t lane_len;
 };
 
 // Fused apply: the update rule of the step.  ext = 0 (exchange-free steps):
@@ -263,6 +270,30 @@ struct EvalEnv {
 // over or max_moves is reached, then the render of its next state into its
 // slice of eval_in.  A game whose log is full does nothing.
 hipError_t launch_eval_env(const EvalEnv& e, const float* q, uint64_t thresh, int play,
+                           hipStream_t s);
+// Device actor pool (pool.h): ngames == lanes Snake games in lock step, one
+// workgroup each, game g adding into lane g of a laned ring.  A game's state is
+// the actor's (ActorState); h0 / v0: the ring's per-lane head / valid when the
+// pool was created (launch constants: a game's slot comes from them and its
+// own step counter).
+struct PoolEnv {
+  ActorState* games;                // [ngames]
+  const uint8_t* maps;              // row_map[S] then col_map[S]
+  float* pool_in;                   // [ngames] states as f32 NHWC (S,S,4): the forward's input
+  int S, ngames;
+  int64_t lane_len, h0, v0;
+  uint8_t* r_state;
+  uint8_t* r_action;
+  int16_t* r_reward;
+  uint8_t* r_nonterm;
+  ReplayMeta* meta;
+};
+// ngames workgroups: (play != 0) game g's epsilon-greedy action from
+// q[4g..4g+4) and the coin against thresh, one game step, the transition into
+// slot g lane_len + (h0 + steps_g) mod lane_len, the render of its next state
+// into that slot (not after a game over) and into its slice of pool_in;
+// workgroup 0 publishes the per-lane head / valid.
+hipError_t launch_pool_env(const PoolEnv& e, const float* q, uint64_t thresh, int play,
                            hipStream_t s);
 // Device-resident training monitor (monitor.h).  MonitorRecord is
 // ddq_monitor_record (include/ddq_hip.h), field for field.

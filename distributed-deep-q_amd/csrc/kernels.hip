@@ -95,12 +95,22 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 // round; the process is symmetric in the population, so the final set is
 // uniform.  Deterministic in (seed, ctr): every workgroup that runs it gets
 // the same set, which lets the gather workgroups draw for themselves.
+// On a laned ring (ReplayMeta, lanes > 1): the same draw over [0, lanes * valid),
+// x forbidden iff head >= 1 and x mod valid == head - 1, and the final sorted x
+// mapped to slots (x div valid) * lane_len + x mod valid.
 constexpr int kDrawRounds = 4096;
 
 __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr,
                             int64_t* cand, int* bad_any) {
   const int t = threadIdx.x;
-  const int64_t valid = meta->valid;
+  // laned ring (ReplayMeta): draw x over the lanes' valid prefixes laid end to
+  // end, [0, lanes * valid); forbidden per lane; the final sorted x become
+  // slots.  lanes is wave-uniform, so the unlaned path below is the old one
+  // behind scalar branches.
+  const int32_t lanes = meta->lanes;
+  const bool laned = lanes > 1;
+  const int64_t lvalid = meta->valid;                       // per lane
+  const int64_t valid = laned ? lanes * lvalid : lvalid;
   const int64_t forbid = meta->head - 1;   // -1 when head == 0: nothing forbidden
   // draw for sorted position `pos` in redraw round `round`
   auto draw_at = [&](int round, int pos) -> int64_t {
@@ -131,13 +141,18 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
           eqlo += (o == v) & (k < t);
         }
         r = less + eqlo;
-        const bool bad = t < B && (v == fb || eqlo > 0);
+        const bool fbd = laned ? (forbid >= 0 && v % (uint32_t)lvalid == fb) : v == fb;
+        const bool bad = t < B && (fbd || eqlo > 0);
         if (__ballot(bad) == 0) { done = true; break; }
         if (round < kDrawRounds && bad) v = (uint32_t)draw_at(round, r);
       }
       // no distinct set after kDrawRounds checked rounds (valid barely above
       // B): flag it (ddq_replay_status) instead of gathering a bad set silently
       if (!done && t == 0) meta->err = 2;
+      if (laned) {   // x -> slot (x div v) L + x mod v: monotone, the set stays sorted
+        const uint32_t lane = v / (uint32_t)lvalid;
+        v = lane * (uint32_t)meta->lane_len + (v - lane * (uint32_t)lvalid);
+      }
       if (t < B) cand[r] = (int64_t)v;
     }
     __syncthreads();
@@ -165,7 +180,11 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
     if (t == 0) *bad_any = 0;
     __syncthreads();
     bool bad = false;
-    if (t < B) bad = (cand[t] == forbid) || (t > 0 && cand[t] == cand[t - 1]);
+    if (t < B) {
+      const bool fbd = laned ? (forbid >= 0 && (uint32_t)cand[t] % (uint32_t)lvalid == (uint32_t)forbid)
+                             : cand[t] == forbid;
+      bad = fbd || (t > 0 && cand[t] == cand[t - 1]);
+    }
     if (bad) *bad_any = 1;
     __syncthreads();
     if (!*bad_any) break;
@@ -174,6 +193,10 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
       break;
     }
     if (bad) cand[t] = draw(round);
+  }
+  if (laned && t < B) {
+    const uint32_t x = (uint32_t)cand[t], lane = x / (uint32_t)lvalid;
+    cand[t] = (int64_t)lane * meta->lane_len + (x - lane * (uint32_t)lvalid);
   }
   __syncthreads();
 }
@@ -198,7 +221,8 @@ __global__ __launch_bounds__(1024) void sample_kernel(ReplayMeta* meta, int B, u
 }
 
 // u8 (C,H,W) slot -> f32 NHWC, 4 pixels per thread; z = 0 -> state from
-// idx, z = 1 -> next_state from next_idx (wrap N-1 -> 0, replay.py:160-166);
+// idx, z = 1 -> next_state from next_idx (wrap N-1 -> 0, replay.py:160-166;
+// on a laned ring the lane's last slot wraps to the lane's first);
 // the z = 1 blocks with blockIdx.x == 0 also write action one-hot, reward and
 // non_terminal of next_idx (replay.py:172-183).
 __device__ __forceinline__ void gather_body(
@@ -206,8 +230,10 @@ __device__ __forceinline__ void gather_body(
     const int16_t* __restrict__ rew, const uint8_t* __restrict__ nt, ReplayMeta* meta, int64_t i,
     int S, float* __restrict__ sQ, float* __restrict__ sP, float* __restrict__ action,
     float* __restrict__ reward, float* __restrict__ nonterm, int bx, int b, int z) {
-  const int64_t N = meta->capacity;
-  const int64_t nxt = (i + 1 == N) ? 0 : i + 1;
+  // the next slot within the lane (ReplayMeta; unlaned: lane_len == capacity)
+  const int64_t L = meta->lane_len;
+  int64_t nxt = (i + 1 == L) ? 0 : i + 1;
+  if (meta->lanes > 1 && (uint32_t)(i + 1) % (uint32_t)L == 0) nxt = i + 1 - L;
   const int64_t slot = z ? nxt : i;
   const int SS = S * S;
   const int p4 = bx * 256 + threadIdx.x;             // group of 4 pixels
@@ -2313,5 +2339,7 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
 #include "actor.h"
 // the device-resident evaluator's environment step: one game per workgroup
 #include "eval.h"
+// the actor pool's environment step: one game per workgroup, one ring lane each
+#include "pool.h"
 // the training monitor's reduction: one workgroup per chunk, one record
 #include "monitor.h"

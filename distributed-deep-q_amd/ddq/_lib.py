@@ -124,6 +124,11 @@ _SIGS = {
     "ddq_eval_create": (ctypes.c_int, [_P, _i32, _P, _P, _P, _u64, ctypes.c_double, _i32, _i32]),
     "ddq_eval_run_async": (ctypes.c_int, [_P, _i32]),
     "ddq_eval_read": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ddq_replay_set_lanes": (ctypes.c_int, [_P, _i32]),
+    "ddq_replay_lanes": (ctypes.c_int, [_P, _P, _P]),
+    "ddq_actors_create": (ctypes.c_int, [_P, _i32, _P, _P, _P, _u64]),
+    "ddq_actors_step_async": (ctypes.c_int, [_P, _i32, _i64]),
+    "ddq_actors_read": (ctypes.c_int, [_P, _P, _P, _P]),
     "ddq_apply": (ctypes.c_int, [_P, ctypes.POINTER(UpdateCfg)]),
     "ddq_apply_async": (ctypes.c_int, [_P, ctypes.POINTER(UpdateCfg)]),
     "ddq_reset_optimizer": (ctypes.c_int, [_P]),

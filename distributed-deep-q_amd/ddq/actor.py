@@ -13,6 +13,8 @@ one draw per ``random()`` / ``randrange()`` / ``choice()``, in program order
 
 One actor per ctx, as one reference worker is one game + one ring + one net:
 ``sample_direct`` takes s' from slot idx+1, so a ring holds one trajectory.
+A laned ring (``replay_set_lanes``) holds one per lane: ``DeviceActorPool``
+plays N games in lock step, one lane each.
 """
 from __future__ import annotations
 
@@ -139,9 +141,62 @@ class DeviceActor:
         enqueued on the ctx stream; the caller synchronises.
 
         The training step is the plain graph step (``step_graph(cfg, 1)``), not
-        the pipelined one: the pipelined step gathers step t+1's minibatch
-        under step t, that is before the act between the two, so it would be
-        drawn against the ring as it was before that act's transition."""
+        the pipelined one: within a pipelined chain step t+1's minibatch is
+        gathered under step t, that is before an act between the two, so it
+        would be drawn against the ring as it was before that act's transition.
+        That holds per single act.  A chain's first step draws and gathers for
+        itself, so a whole chain can follow a move of N lock-step actors:
+        ``DeviceActorPool.act_and_train``."""
         for k in range(int(n)):
             self.net.actor_step(1, iter0 + k)
             self.net.step_graph(cfg, 1)
+
+
+class DeviceActorPool:
+    """N lock-step device actors on one ctx, actor i filling lane i of a laned
+    ring (``net.replay_set_lanes(N)`` on the empty ring first): one move is one
+    batched Q forward and one environment launch and adds N transitions.
+
+    ``init_states``: (N,10,10) start boards, one per game; game i draws from
+    ``ActorRng(game_seed(seed, i))`` and otherwise is ``DeviceActor``'s game."""
+
+    def __init__(self, net, init_states, seed, preprocessor=None):
+        self.net = getattr(net, "dqn", net)
+        S = self.net.frame
+        self.row_map, self.col_map = zoom_maps(preprocessor if preprocessor is not None
+                                               else (S, S), S)
+        self.init_states = np.array(init_states, np.int64).reshape(-1, BOARD, BOARD)
+        self.ngames = self.init_states.shape[0]
+        self.seed = int(seed) & _M64
+        self.net.actors_create(self.init_states, self.row_map, self.col_map, self.seed)
+
+    def get_epsilon(self, iter_num):
+        return eg.epsilon(iter_num)
+
+    def generate_experience(self, iter_num):
+        """One move of all games at ε(iter_num): N transitions; enqueued, no
+        synchronisation."""
+        self.net.actors_step(1, iter_num)
+
+    def fill(self, nmoves):
+        """The initial replay: nmoves moves (N · nmoves experiences) at ε(0)."""
+        if nmoves > 0:
+            self.net.actors_step(nmoves, 0)
+
+    def stats(self):
+        """Synchronises.  The games' totals (steps, games ended, reward sum,
+        RNG draws), the same per game (N,4), and the 4-board histories."""
+        boards, per_game, tot = self.net.actors_read()
+        return {"steps": int(tot[0]), "games": int(tot[1]), "reward_sum": int(tot[2]),
+                "draws": int(tot[3]), "per_game": per_game, "boards": boards}
+
+    def act_and_train(self, cfg, rounds, iter0):
+        """rounds x (one move at ε(iter0 + r·N), then N training steps as one
+        pipelined chain), all enqueued on the ctx stream; the caller
+        synchronises.  Act and train stay 1:1.  The chain's first step draws and
+        gathers after the move, so every minibatch of a round is drawn against
+        the ring as the round's move left it."""
+        n = self.ngames
+        for r in range(int(rounds)):
+            self.net.actors_step(1, iter0 + r * n)
+            self.net.step_pipelined(cfg, n)

@@ -252,6 +252,41 @@ class DeepQNet:
         self._check(self.lib.ddq_actor_read(self.ctx, ptr(boards), ptr(stats)))
         return boards, stats
 
+    # -------------------------------------------------------------- actor pool
+    def actors_create(self, init_boards, row_map, col_map, seed):
+        """Device actor pool (ddq_actors_create): one Snake actor per (10,10)
+        board of ``init_boards`` (n,10,10) in lock step, game i adding into lane
+        i of the ring (``replay_set_lanes(n)`` first) and drawing from
+        ``ActorRng(game_seed(seed, i))``."""
+        b = np.asarray(init_boards)
+        if b.size == 0 or b.size % 100:
+            raise ValueError("init_boards must hold (10,10) boards, got %d cells" % b.size)
+        if b.min() < -128 or b.max() > 127:
+            raise ValueError("init_boards codes must fit int8")
+        b = np.ascontiguousarray(b, np.int8).reshape(-1, 10, 10)
+        rm = np.ascontiguousarray(row_map, np.int32).ravel()
+        cm = np.ascontiguousarray(col_map, np.int32).ravel()
+        if rm.size != self.frame or cm.size != self.frame:
+            raise ValueError("row_map / col_map must have %d entries" % self.frame)
+        self._check(self.lib.ddq_actors_create(self.ctx, b.shape[0], ptr(b), ptr(rm), ptr(cm),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._pool_n = b.shape[0]
+
+    def actors_step(self, nmoves, iter_num):
+        """nmoves lock-step moves of all games at ε(iter_num): one transition
+        per game and move; enqueued, no sync."""
+        self._check(self.lib.ddq_actors_step_async(self.ctx, int(nmoves), int(iter_num)))
+
+    def actors_read(self):
+        """Synchronise; (boards (n,4,10,10) int8 oldest first, stats (n,4) int64
+        per game: steps, games ended, sum of rewards, RNG draws; totals int64[4])."""
+        n = getattr(self, "_pool_n", self.batch)
+        boards = np.zeros((n, NFRAME, 10, 10), np.int8)
+        stats = np.zeros((n, 4), np.int64)
+        totals = np.zeros(4, np.int64)
+        self._check(self.lib.ddq_actors_read(self.ctx, ptr(boards), ptr(stats), ptr(totals)))
+        return boards, stats, totals
+
     # -------------------------------------------------------------- evaluation
     def eval_create(self, init_boards, row_map, col_map, seed, epsilon=0.0, max_moves=0,
                     max_episodes=1):
@@ -359,6 +394,18 @@ class DeepQNet:
         self._check(self.lib.ddq_replay_info(self.ctx, ctypes.byref(h), ctypes.byref(v),
                                              ctypes.byref(c)))
         return int(h.value), int(v.value), int(c.value)
+
+    def replay_set_lanes(self, lanes):
+        """Split the (empty) ring into ``lanes`` contiguous lanes, each a ring
+        of its own for one trajectory (ddq_replay_set_lanes); head / valid are
+        per lane from then on."""
+        self._check(self.lib.ddq_replay_set_lanes(self.ctx, int(lanes)))
+
+    def replay_lanes(self):
+        """(lanes, lane_len)."""
+        n, ll = _lib._i32(), _lib._i64()
+        self._check(self.lib.ddq_replay_lanes(self.ctx, ctypes.byref(n), ctypes.byref(ll)))
+        return int(n.value), int(ll.value)
 
     def replay_import(self, state, action, reward, non_terminal, head, valid):
         st = np.ascontiguousarray(state, np.uint8)

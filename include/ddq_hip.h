@@ -45,7 +45,10 @@ extern "C" {
                               device evaluator (ddq_eval_create, ddq_eval_run_async,
                               ddq_eval_read), again new symbols only; and the
                               training monitor (ddq_monitor_enable,
-                              ddq_monitor_record_async, ddq_monitor_read), likewise */
+                              ddq_monitor_record_async, ddq_monitor_read), likewise;
+                              and the laned ring and actor pool (ddq_replay_set_lanes,
+                              ddq_replay_lanes, ddq_actors_create,
+                              ddq_actors_step_async, ddq_actors_read), likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -213,6 +216,25 @@ int ddq_replay_create(ddq_ctx* ctx, int64_t capacity);
  * leaves the slot stale.  state: 4*S*S uint8 (C,H,W). */
 int ddq_replay_add(ddq_ctx* ctx, int32_t action, int32_t reward, const uint8_t* state);
 int ddq_replay_info(const ddq_ctx* ctx, int64_t* head, int64_t* valid, int64_t* capacity);
+/* Laned ring: the capacity slots become `lanes` contiguous lanes of lane_len =
+ * capacity / lanes slots; lane g is slots [g lane_len, (g + 1) lane_len) and a
+ * ring of its own, so the ring holds `lanes` trajectories (s' of slot i is the
+ * next slot within i's lane, the lane's last slot wrapping to its first).
+ * Only lock-step writers fill a laned ring (ddq_actors_*), so all lanes share
+ * one head in [0, lane_len) and one valid in [0, lane_len]: on a laned ring
+ * ddq_replay_info returns these per-lane values (and the total capacity), and
+ * ddq_replay_import takes them (head < lane_len, valid <= lane_len; data in
+ * slot order, as ddq_replay_export writes it).  Sampling draws uniformly over
+ * the lanes * valid filled slots without every lane's slot head - 1 (head >= 1),
+ * and needs B <= lanes * (valid - 1) (DDQ_EINVAL otherwise; at lanes == 1 this
+ * is B < valid).  ddq_replay_sample accepts slot i iff i mod lane_len < valid.
+ * The ring must exist and be empty (DDQ_ESTATE); capacity % lanes == 0 and
+ * lane_len >= 2 (DDQ_EINVAL).  lanes == 1 is the plain ring and changes
+ * nothing.  With lanes > 1, ddq_replay_add, ddq_replay_fill_tiled,
+ * ddq_replay_sample_batch_async, ddq_replay_gather_batch_async and
+ * ddq_actor_create return DDQ_ESTATE. */
+int ddq_replay_set_lanes(ddq_ctx* ctx, int32_t lanes);
+int ddq_replay_lanes(const ddq_ctx* ctx, int32_t* lanes, int64_t* lane_len);
 /* Bulk load / store of the ring (the HDF5 datasets of replay.py:48-61,
  * persisted by __del__ :185-192). */
 int ddq_replay_import(ddq_ctx* ctx, const uint8_t* state, const uint8_t* action,
@@ -355,6 +377,29 @@ int ddq_eval_run_async(ddq_ctx* ctx, int32_t nmoves);
  * pointer may be NULL. */
 int ddq_eval_read(ddq_ctx* ctx, int64_t* stats, int32_t* episodes, int32_t* log,
                   int8_t* boards, uint64_t* draws);
+
+/* ---------------- device actor pool: N lock-step actors, one ring lane each -- */
+/* ngames actors (each ddq_actor_create's game, rules and draws: the coin is
+ * always drawn) play in lock step and add into a laned ring, game g into lane
+ * g.  One move of all games is the Q forward of their states at n = ngames and
+ * one environment kernel (one workgroup per game): ngames transitions for about
+ * the price of one; no copy, no synchronisation.  Game i's stream is the
+ * actor's on game_seed(seed, i), as the evaluator's.  Needs a ring with
+ * lanes == ngames (DDQ_EINVAL otherwise; DDQ_ESTATE without a ring) and
+ * ngames <= B.  init_boards: ngames * 100 board codes; boards and maps as
+ * ddq_actor_create's, checked alike.  The games write from the ring's per-lane
+ * head / valid at this call.  Calling it again resets the games and leaves the
+ * ring as it is. */
+int ddq_actors_create(ddq_ctx* ctx, int32_t ngames, const int8_t* init_boards,
+                      const int32_t* row_map, const int32_t* col_map, uint64_t seed);
+/* nmoves lock-step moves at epsilon(iter_num), enqueued on the ctx stream, no
+ * sync; the ring's per-lane head / valid (ddq_replay_info) advance by nmoves
+ * at once. */
+int ddq_actors_step_async(ddq_ctx* ctx, int32_t nmoves, int64_t iter_num);
+/* Synchronise.  boards: ngames * 4 * 100 int8, oldest frame first; stats:
+ * ngames * 4, per game ddq_actor_read's (steps, games ended, reward sum, RNG
+ * draws); totals[4]: their sums over the games.  Every pointer may be NULL. */
+int ddq_actors_read(ddq_ctx* ctx, int8_t* boards, int64_t* stats, int64_t* totals);
 
 /* ---------------- apply (param server) --------------------------------- */
 /* apply_descent + update_fn (server.py:49-124) on the Q tower with the
