@@ -87,7 +87,10 @@ struct ddq_ctx {
   // blobs of the last forward
   std::vector<float> q_out, p_out, q_sa, p_sa, target;
   float loss = 0.f;
-  Tower tw[2];
+  Tower tw[3];                   // Q on state, P on next_state, Q on next_state (DOUBLE)
+  // selectable objective (ddq_set_objective) and its two blobs
+  ddq_objective obj{DDQ_TARGET_MAX, DDQ_LOSS_EUCLIDEAN, 0.f, 0};
+  std::vector<float> qn_out, dq_out;
   // replay ring (replay.py:23-68)
   std::vector<uint8_t> r_state, r_action, r_nonterm;
   std::vector<int16_t> r_reward;
@@ -218,9 +221,10 @@ void dense(const float* x, int B, int K, int N, const float* W, const float* bia
     }
 }
 
-void tower_fwd(ddq_ctx* c, int z, const float* frames, int B) {
+// tower slot z with the weights of tower zw (slot 2: Q's weights on next_state)
+void tower_fwd(ddq_ctx* c, int z, const float* frames, int B, int zw = -1) {
   const Layout& L = c->L;
-  const float* th = c->theta[z].data();
+  const float* th = c->theta[zw < 0 ? z : zw].data();
   Tower& t = c->tw[z];
   int H = c->S;
   t.x[0].assign(frames, frames + (size_t)B * kC * H * H);
@@ -338,10 +342,17 @@ int forward_backward(ddq_ctx* c) {
   const Layout& L = c->L;
   tower_fwd(c, 0, c->state.data(), B);
   tower_fwd(c, 1, c->next_state.data(), B);
+  const bool dbl = c->obj.target == DDQ_TARGET_DOUBLE, huber = c->obj.loss == DDQ_LOSS_HUBER;
+  if (dbl) {   // Q(s', .) under theta_Q: the Double-DQN action choice
+    tower_fwd(c, 2, c->next_state.data(), B, 0);
+    c->qn_out = c->tw[2].out;
+  }
   const Tower& q = c->tw[0];
   const Tower& p = c->tw[1];
   c->q_out = q.out;
   c->p_out = p.out;
+  c->dq_out.assign((size_t)B * kA, 0.f);
+  const double delta = c->obj.huber_delta;
   c->q_sa.assign(B, 0.f); c->p_sa.assign(B, 0.f); c->target.assign(B, 0.f);
   // head: ELTWISE PROD + SLICE + SUM (Q(s,a)), SLICE + MAX * non_terminal (max_a
   // P), SUM with coefficients (gamma, 1), EUCLIDEAN_LOSS (train_val.prototxt:385-483)
@@ -353,13 +364,30 @@ int forward_backward(ddq_ctx* c) {
       qs += (double)q.out[(size_t)b * kA + a] * c->action[(size_t)b * kA + a];
       pm = std::max(pm, (double)p.out[(size_t)b * kA + a]);
     }
+    if (dbl) {   // P at the first maximum of Qn_out[b] (argmax rule: first max wins)
+      const float* qn = c->qn_out.data() + (size_t)b * kA;
+      int best = 0;
+      for (int a = 1; a < kA; ++a)
+        if (qn[a] > qn[best]) best = a;
+      pm = p.out[(size_t)b * kA + best];
+    }
     const float qsf = (float)qs;
     const float psf = (float)(pm * c->nonterm[b]);
     const float tg = (float)((double)c->gamma * psf + 1.0 * c->reward[b]);
     c->q_sa[b] = qsf; c->p_sa[b] = psf; c->target[b] = tg;
     const double diff = (double)qsf - tg;
-    loss += diff * diff;
-    for (int a = 0; a < kA; ++a) dq[(size_t)b * kA + a] = c->action[(size_t)b * kA + a] * diff / B;
+    double dc = diff;
+    if (huber) {   // h(d) scaled by 2: d^2 inside the band, delta (2|d| - delta) outside
+      const double ad = std::fabs(diff);
+      dc = std::min(std::max(diff, -delta), delta);
+      loss += ad <= delta ? diff * diff : delta * (2.0 * ad - delta);
+    } else {
+      loss += diff * diff;
+    }
+    for (int a = 0; a < kA; ++a) {
+      dq[(size_t)b * kA + a] = c->action[(size_t)b * kA + a] * dc / B;
+      c->dq_out[(size_t)b * kA + a] = (float)dq[(size_t)b * kA + a];
+    }
   }
   c->loss = (float)(loss / B / 2.0);
   float* g = c->grad.data();
@@ -504,6 +532,7 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* d) {
   c->idx.assign(c->B, 0);
   c->q_out.assign((size_t)c->B * kA, 0.f); c->p_out.assign((size_t)c->B * kA, 0.f);
   c->q_sa.assign(c->B, 0.f); c->p_sa.assign(c->B, 0.f); c->target.assign(c->B, 0.f);
+  c->qn_out.assign((size_t)c->B * kA, 0.f); c->dq_out.assign((size_t)c->B * kA, 0.f);
   *out = c;
   return DDQ_OK;
 }
@@ -812,6 +841,28 @@ int ddq_forward_backward(ddq_ctx* c, float* loss) {
   return rc;
 }
 
+// ---- selectable objective ----
+int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!o) return fail(c, DDQ_EINVAL, "null objective");
+  if (o->target != DDQ_TARGET_MAX && o->target != DDQ_TARGET_DOUBLE)
+    return fail(c, DDQ_EINVAL, "unknown target %d", o->target);
+  if (o->loss != DDQ_LOSS_EUCLIDEAN && o->loss != DDQ_LOSS_HUBER)
+    return fail(c, DDQ_EINVAL, "unknown loss %d", o->loss);
+  if (o->loss == DDQ_LOSS_HUBER && !(std::isfinite(o->huber_delta) && o->huber_delta > 0.f))
+    return fail(c, DDQ_EINVAL, "huber_delta must be finite and > 0 (got %g)", (double)o->huber_delta);
+  if (o->reserved != 0) return fail(c, DDQ_EINVAL, "reserved must be 0");
+  c->obj = *o;
+  if (o->loss != DDQ_LOSS_HUBER) c->obj.huber_delta = 0.f;
+  return DDQ_OK;
+}
+
+int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
+  if (!c || !o) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *o = c->obj;
+  return DDQ_OK;
+}
+
 int ddq_forward_q(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   tower_fwd(c, 0, c->state.data(), c->B);
@@ -824,10 +875,13 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
   struct { const char* nm; const float* p; int64_t cnt; } t[] = {
       {"Q_out", c->q_out.data(), 4ll * c->B}, {"P_out", c->p_out.data(), 4ll * c->B},
       {"Q_sa", c->q_sa.data(), c->B},         {"P_sa", c->p_sa.data(), c->B},
-      {"target_Q_sa", c->target.data(), c->B}, {"loss", &c->loss, 1}};
+      {"target_Q_sa", c->target.data(), c->B}, {"loss", &c->loss, 1},
+      {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B}};
   for (auto& e : t)
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
+      if (e.p == c->qn_out.data() && c->obj.target != DDQ_TARGET_DOUBLE)
+        return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
       std::copy(e.p, e.p + n, dst);
       return DDQ_OK;
     }

@@ -965,10 +965,35 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
 }
 
 // ---------------- compute ----------------
+// Double target (ddq_set_objective): Q(s',.) under theta_Q for the minibatch view
+// the pass trains on, the pass's first launch group -- ddq_forward_q's kernels
+// at n = B over nb.next_state in the acting scratch (the actor, pool and
+// evaluator are serial on the same stream), into the ctx's Qn_out buffer.  It
+// depends on theta_Q and the bound view only: stream order after the previous
+// step's apply is enough.  Profile names: "qn_<kernel>".
+struct QnMark {
+  void (*mark)(void*, const char*);
+  void* arg;
+};
+static void qn_mark(void* a, const char* name) {
+  const QnMark* m = reinterpret_cast<const QnMark*>(a);
+  const std::string s = std::string("qn_") + name;
+  m->mark(m->arg, s.c_str());
+}
+static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
+                              void* marg) {
+  if (nb.obj_target != DDQ_TARGET_DOUBLE) return DDQ_OK;
+  QnMark qm{mark, marg};
+  HIP_TRY(c, launch_act(nb, nb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
+                        nullptr, c->act_p1s, c->act_p2s, c->stream, mark ? qn_mark : nullptr, &qm));
+  return DDQ_OK;
+}
+
 // book >= 0: this backward feeds a step's apply; its slab reduce also does
 // the apply bookkeeping with target period `book` (saves a launch).
 static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
                            void* marg, int book = -1, ReplayMeta* bump = nullptr) {
+  TRY(enqueue_qn_forward(c, nb, mark, marg));
   if (nb.small) {
     HIP_TRY(c, launch_small_fwd_head(nb, c->stream, mark, marg));
   } else {
@@ -1003,6 +1028,44 @@ int ddq_forward_backward(ddq_ctx* c, float* loss) {
   return DDQ_OK;
 }
 
+// ---------------- selectable objective ----------------
+int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!o) return fail(c, DDQ_EINVAL, "null objective");
+  if (o->target != DDQ_TARGET_MAX && o->target != DDQ_TARGET_DOUBLE)
+    return fail(c, DDQ_EINVAL, "unknown target %d", o->target);
+  if (o->loss != DDQ_LOSS_EUCLIDEAN && o->loss != DDQ_LOSS_HUBER)
+    return fail(c, DDQ_EINVAL, "unknown loss %d", o->loss);
+  if (o->loss == DDQ_LOSS_HUBER && !(std::isfinite(o->huber_delta) && o->huber_delta > 0.f))
+    return fail(c, DDQ_EINVAL, "huber_delta must be finite and > 0 (got %g)", (double)o->huber_delta);
+  if (o->reserved != 0) return fail(c, DDQ_EINVAL, "reserved must be 0");
+  if (c->async_on)
+    return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: set the objective "
+                               "before ddq_async_begin");
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);   // captured steps hold (or lack) the extra forward and the head's objective
+  NetBuffers& nb = c->nb;
+  if (o->target == DDQ_TARGET_DOUBLE) {
+    if (!nb.qn_out) TRY(dalloc(c, &nb.qn_out, (size_t)nb.B * 4));
+    // one run of the extra forward now: its kernels' function attributes are set
+    // outside any capture (the result is overwritten by the first pass)
+    HIP_TRY(c, launch_act(nb, nb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
+                          nullptr, c->act_p1s, c->act_p2s, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  nb.obj_target = o->target;
+  nb.obj_loss = o->loss;
+  nb.huber_delta = o->loss == DDQ_LOSS_HUBER ? o->huber_delta : 0.f;
+  return DDQ_OK;
+}
+
+int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
+  if (!c || !o) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *o = ddq_objective{c->nb.obj_target, c->nb.obj_loss, c->nb.huber_delta, 0};
+  return DDQ_OK;
+}
+
 int ddq_forward_q(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(set_dev(c));
@@ -1018,10 +1081,13 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
   struct { const char* nm; float* p; int64_t cnt; } t[] = {
       {"Q_out", c->nb.q_out, 4ll * B}, {"P_out", c->nb.p_out, 4ll * B},
       {"Q_sa", c->nb.q_sa, B},         {"P_sa", c->nb.p_sa, B},
-      {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1}};
+      {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1},
+      {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
+      if (!strcmp(name, "Qn_out") && c->nb.obj_target != DDQ_TARGET_DOUBLE)
+        return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
       TRY(set_dev(c));
       return copy_out(c, dst, e.p, n, 0);
     }
@@ -1542,6 +1608,7 @@ static hipError_t fc4_bucket_start(void* arg) {
 static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
                              void* marg, int book, ReplayMeta* bump, bool overlap,
                              const Prefetch* pf = nullptr) {
+  TRY(enqueue_qn_forward(c, nb, mark, marg));
   if (nb.small) {
     HIP_TRY(c, launch_small_fwd_head(nb, c->stream, mark, marg, bump, nb.fa.on ? pf : nullptr));
   } else {

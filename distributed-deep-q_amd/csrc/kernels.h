@@ -108,6 +108,12 @@ struct NetBuffers {
   int book_inc;                     // param-server iterations per apply (1, or W: server mode)
   int head_bump;                    // the head kernel advances the draw counter without a
                                     // fused apply (async gradients: sample_gather draws)
+  // selectable objective (ddq_set_objective): target 0 = max_a P, 1 = P at the
+  // first maximum of qn_out (Q(s',.) under theta_Q, (B,4), the pass's first
+  // launch group); loss 0 = Euclidean, 1 = Huber with band huber_delta
+  int obj_target = 0, obj_loss = 0;
+  float huber_delta = 0.f;
+  float* qn_out = nullptr;
   // deepq16 step (small.h, small_bwd.h): fc4 chain partials and its fan-in words
   int small;                        // S == 16, B <= 256: the four-launch step
   int small_G = 1;                  // its fc4 chain's image chunks (B > 32: ceil(B / 32))
@@ -218,9 +224,11 @@ hipError_t launch_book(const NetBuffers& nb, int period, hipStream_t s);
 hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, int64_t slice,
                              hipStream_t s);
 // Q-tower forward of n states (NHWC f32 in `in`) into scratch, argmax into out.
+// mark: the launches' profile names (ddq_profile_step).
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s);
+                      __bf16* pool2s, hipStream_t s,
+                      void (*mark)(void*, const char*) = nullptr, void* mark_arg = nullptr);
 // Device-resident Snake actor (actor.h).  boards: the 4-frame history of 10x10
 // board codes [x*10+y] (SnakeGame.encode_state), oldest first, then init_board;
 // draws: position in the actor's RNG stream splitmix64(seed ^ splitmix64(k)).

@@ -646,6 +646,9 @@ __global__ __launch_bounds__(512) void fc4_reduce_out_kernel(
 //   h4 = ReLU(sum_s part + b4), Q/P = W5 h4 + b5,
 //   Q_sa = sum_a Q*act, P_sa = max_a P * nt, target = 0.85 P_sa + r,
 //   dQ = act (Q_sa-target)/B, dh4 = (dQ W5) * (h4>0).
+// Selectable objective: the double target takes P at the first maximum of
+// Qn_out[b] instead of the max; the Huber loss clamps Q_sa-target to the band
+// before the division by B and keeps 2 h(d) where the squared error goes.
 // The cross-sample sums (loss, dW5, db5, db4) are finished by the head blocks
 // of the wgrad slab reduce (per-sample dQ and squared error kept in dqbuf /
 // lpart), so the head costs no launch of its own.
@@ -697,6 +700,10 @@ struct HeadArgs {
   uint64_t dseed;
   int32_t* dlog;
   int64_t dlog_cap;
+  // selectable objective (NetBuffers::obj_*), uniform over the launch
+  int obj_target, obj_loss;
+  float huber_delta;
+  const float* qn;
 };
 
 __device__ __forceinline__ void head_draw(const HeadArgs& H) {
@@ -766,7 +773,10 @@ hipError_t launch_tower_fwd16(const TowerArgs& t, hipStream_t s) {
 }
 }  // namespace sm16
 
-// One head block b
+// One head block b.  OBJ: the selectable objective's branches are compiled in
+// (fc4_head_obj_kernel); without it this is the reference objective's code and
+// nothing else, so the default launch keeps its instruction stream
+template <bool OBJ>
 __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) {
   const float* __restrict__ part = H.part;
   const int splits = H.splits, B = H.B;
@@ -887,17 +897,34 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
   qs += qp[1] * ac[1];
   qs += qp[2] * ac[2];
   qs += qp[3] * ac[3];
-  float ps = fmaxf(fmaxf(qp[4], qp[5]), fmaxf(qp[6], qp[7]));   // SLICE + MAX
+  float ps;
+  if (!OBJ || H.obj_target == 0) {
+    ps = fmaxf(fmaxf(qp[4], qp[5]), fmaxf(qp[6], qp[7]));       // SLICE + MAX
+  } else {                                                       // P at argmax_a Q(s',a)
+    const float* qn = H.qn + b * 4;
+    int best = 0;
+    for (int a = 1; a < 4; ++a)
+      if (qn[a] > qn[best]) best = a;                            // argmax_kernel: first max
+    ps = qp[4 + best];
+  }
   ps = ps * ntb;                                                 // P_sa_or_term
   const float tg = gamma * ps + 1.0f * rwb;                      // SUM coeff {0.85, 1}
   const float diff = qs - tg;
-  const float gsc = diff / (float)B;                             // EUCLIDEAN_LOSS diff
+  float gsc, le;
+  if (!OBJ || H.obj_loss == 0) {
+    gsc = diff / (float)B;                                       // EUCLIDEAN_LOSS diff
+    le = diff * diff;
+  } else {                                                       // Huber: 2 h(diff)
+    const float dl = H.huber_delta, ad = fabsf(diff);
+    gsc = fminf(fmaxf(diff, -dl), dl) / (float)B;
+    le = ad <= dl ? diff * diff : dl * (2.f * ad - dl);
+  }
   float dq[4];
 #pragma unroll
   for (int a = 0; a < 4; ++a) dq[a] = ac[a] * gsc;
   if (n == 0) {
     q_sa_o[b] = qs; p_sa_o[b] = ps; target_o[b] = tg;
-    lpart[b] = diff * diff;
+    lpart[b] = le;
 #pragma unroll
     for (int a = 0; a < 4; ++a) dqbuf[b * 4 + a] = dq[a];
   }
@@ -908,8 +935,11 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
 
 __global__ __launch_bounds__(512) void fc4_head_kernel(const HeadArgs H) {
   __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
-  head_body(H, blockIdx.x, smem);
+  head_body<false>(H, blockIdx.x, smem);
 }
+// a non-default objective (HeadArgs::obj_*): the same body with its branches
+// (defined after the step's other kernels, below launch_act)
+__global__ void fc4_head_obj_kernel(const HeadArgs H);
 
 // Cross-sample head sums, run by the 8 trailing blocks of the wgrad slab
 // reduce: block hb owns fc4 units j = 64 hb + lane, 4 sample groups.
@@ -1102,7 +1132,9 @@ static HeadArgs head_args(const NetBuffers& nb, ReplayMeta* bump) {
                   nb.fa.on ? nb.opt_init : nullptr, nb.iter, nb.fa.period, nb.book_inc,
                   (nb.fa.on || nb.head_bump) ? bump : nullptr, nb.wks[0], L.wks_total,
                   L.wks_off[1], L.wkst_off,
-                  L.wks_off[2], L.wkst3_off};
+                  L.wks_off[2], L.wkst3_off,
+                  nullptr, nullptr, 0, nullptr, 0,
+                  nb.obj_target, nb.obj_loss, nb.huber_delta, nb.qn_out};
 }
 
 static Fc4DgradArgs fc4_dgrad_args(const NetBuffers& nb, bool& narrow, int& ndx, int& nd) {
@@ -1121,6 +1153,7 @@ static Fc4DgradArgs fc4_dgrad_args(const NetBuffers& nb, bool& narrow, int& ndx,
 
 hipError_t launch_head(const NetBuffers& nb, hipStream_t s, ReplayMeta* bump, const Prefetch* pf) {
   HeadArgs H = head_args(nb, bump);
+  if (H.obj_target && !H.qn) return hipErrorInvalidValue;
   int extra = 0;
   if (pf && pf->ng > 0 && H.bump && nb.B <= 256) {   // the next step's draw moves here
     H.dmeta = H.bump;
@@ -1128,7 +1161,8 @@ hipError_t launch_head(const NetBuffers& nb, hipStream_t s, ReplayMeta* bump, co
     H.didx = pf->idx; H.dseed = pf->seed; H.dlog = pf->idx_log; H.dlog_cap = pf->log_cap;
     extra = 1;
   }
-  ddq_launch(fc4_head_kernel, dim3(nb.B + 25 + 9 + extra), dim3(kFc4), 0, s, H);
+  ddq_launch(H.obj_target || H.obj_loss ? fc4_head_obj_kernel : fc4_head_kernel,
+             dim3(nb.B + 25 + 9 + extra), dim3(kFc4), 0, s, H);
   return hipGetLastError();
 }
 
@@ -2002,6 +2036,10 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   c.qpart = nb.qpart; c.dpart = nb.dpart; c.sync = nb.csync;
   c.q_out = nb.q_out; c.p_out = nb.p_out; c.q_sa = nb.q_sa; c.p_sa = nb.p_sa;
   c.target = nb.target; c.loss = nb.loss; c.grad = nb.grad;
+  c.dq_out = nb.dqbuf;
+  c.obj_target = nb.obj_target; c.obj_loss = nb.obj_loss; c.huber_delta = nb.huber_delta;
+  c.qn = nb.qn_out;
+  if (c.obj_target && !c.qn) return hipErrorInvalidValue;
   c.apply = nb.fa.on && !nb.fa.ext;
   c.store_grad = nb.fa.store_grad;
   c.aa = apply_args(nb, nb.fa.rule, nb.fa.lr, nb.fa.decay, nb.fa.eps, nb.fa.momentum, nb.fa.wd,
@@ -2011,10 +2049,11 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   if (c.G > 8 || (c.G > 1 && (!c.upart || !c.w4part))) return hipErrorInvalidValue;
   // B <= 32: one tower a workgroup (kFcBlk of the P tower, then kFcBlk of
   // Q); B > 32: both towers a workgroup, kFcBlk G (all resident)
-  const bool one = c.G == 1;
-  auto kern = one ? sm16::fc4_chain16_kernel<1> : sm16::fc4_chain16_kernel<2>;
-  static std::atomic<uint64_t> attr1{0}, attr2{0};
-  CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), one ? attr1 : attr2,
+  const bool one = c.G == 1, obj = c.obj_target || c.obj_loss;
+  auto kern = obj ? (one ? sm16::fc4_chain16_obj_kernel<1> : sm16::fc4_chain16_obj_kernel<2>)
+                  : (one ? sm16::fc4_chain16_kernel<1> : sm16::fc4_chain16_kernel<2>);
+  static std::atomic<uint64_t> attr[4] = {{0}, {0}, {0}, {0}};
+  CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr[(obj ? 2 : 0) + (one ? 0 : 1)],
                               sm16::kChainSmem));
   M("fc4_chain");
   ddq_launch(kern, dim3((one ? 2 : 1) * sm16::kFcBlk * c.G - (nb.fault_k2_short ? 1 : 0)), dim3(512),
@@ -2062,6 +2101,10 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
       // K2: every fc4 workgroup meets (one tower a workgroup at B <= 32)
       {"fc4_chain16", G == 1 ? reinterpret_cast<const void*>(sm16::fc4_chain16_kernel<1>)
                              : reinterpret_cast<const void*>(sm16::fc4_chain16_kernel<2>),
+       512, sm16::kChainSmem, (G == 1 ? 2 : 1) * sm16::kFcBlk * G},
+      // and its build with a non-default objective's branches (ddq_set_objective)
+      {"fc4_chain16_obj", G == 1 ? reinterpret_cast<const void*>(sm16::fc4_chain16_obj_kernel<1>)
+                                 : reinterpret_cast<const void*>(sm16::fc4_chain16_obj_kernel<2>),
        512, sm16::kChainSmem, (G == 1 ? 2 : 1) * sm16::kFcBlk * G},
       // K4: a tile's groups meet when it has more than one
       {"wgrad16", reinterpret_cast<const void*>(sm16::wgrad16_kernel), 256, wgrad16_lds(),
@@ -2311,7 +2354,8 @@ __global__ void argmax_kernel(int n, const float* __restrict__ qout, int32_t* __
 
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s) {
+                      __bf16* pool2s, hipStream_t s, void (*mark)(void*, const char*),
+                      void* marg) {
   NetBuffers a = nb;
   a.B = n;
   a.state = const_cast<float*>(in);
@@ -2325,12 +2369,18 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
   a.mask1 = a.mask2 = a.mask3 = nullptr;
   a.fc4_part = part;
   a.q_out = qout; a.p_out = qout;
-  CHECK_LAUNCH(launch_forward(a, 1, s, nullptr, nullptr));
+  CHECK_LAUNCH(launch_forward(a, 1, s, mark, marg));
   if (actions) {
+    if (mark) mark(marg, "argmax");
     ddq_launch(argmax_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, qout, actions);
     CHECK_LAUNCH(hipGetLastError());
   }
   return hipSuccess;
+}
+
+__global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
+  __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
+  head_body<true>(H, blockIdx.x, smem);
 }
 
 }  // namespace ddq

@@ -74,6 +74,12 @@ struct ChainArgs {
   float* upart;
   float* w4part;
   int store_grad;                  // (unused: W4's gradient is always stored -- K4 applies it)
+  // selectable objective (NetBuffers::obj_*), uniform over the launch; dq_out:
+  // the "Q_out.diff" blob (B,4), stored by the unit block 0 workgroups
+  int obj_target, obj_loss;
+  float huber_delta;
+  const float* qn;
+  float* dq_out;
   ApplyArgs aa;
   ApplyTail at;
 };
@@ -96,8 +102,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 // NZ towers a workgroup: 1 (B <= 32: 64 workgroups, below) or 2 (B > 32: G
 // chunks of 32 images, 32 G workgroups -- all resident with the launch's
 // 159 KB of LDS only if each carries both towers)
-template <int NZ>
-__global__ __launch_bounds__(512) void fc4_chain16_kernel(const ChainArgs c) {
+// OBJ: the selectable objective's branches are compiled in (fc4_chain16_obj_kernel);
+// without it the head loop is the reference objective's code and nothing else
+template <int NZ, bool OBJ>
+__device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int bid = blockIdx.x;
@@ -298,16 +306,37 @@ __global__ __launch_bounds__(512) void fc4_chain16_kernel(const ChainArgs c) {
     qs += qp[1] * ac[1];
     qs += qp[2] * ac[2];
     qs += qp[3] * ac[3];
-    float ps = fmaxf(fmaxf(pp[0], pp[1]), fmaxf(pp[2], pp[3]));
+    float ps;
+    if (!OBJ || c.obj_target == 0) {
+      ps = fmaxf(fmaxf(pp[0], pp[1]), fmaxf(pp[2], pp[3]));
+    } else {                                       // P at the first maximum of Qn_out[b]
+      const float4 qn = *reinterpret_cast<const float4*>(c.qn + b * 4);
+      const float qv[4] = {qn.x, qn.y, qn.z, qn.w};
+      int best = 0;
+#pragma unroll
+      for (int a = 1; a < 4; ++a)
+        if (qv[a] > qv[best]) best = a;
+      ps = pp[best];
+    }
     ps = ps * csm[CH_MB + 5 * B + b];
     const float tg = c.gamma * ps + 1.0f * csm[CH_MB + 4 * B + b];
     const float diff = qs - tg;
-    const float gsc = diff / (float)B;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) DQ[b * 4 + a] = ac[a] * gsc;
-    TMP[b] = diff * diff;
+    float gsc, le;
+    if (!OBJ || c.obj_loss == 0) {
+      gsc = diff / (float)B;
+      le = diff * diff;
+    } else {                                       // Huber: clamp, 2 h(diff)
+      const float dl = c.huber_delta, ad = fabsf(diff);
+      gsc = fminf(fmaxf(diff, -dl), dl) / (float)B;
+      le = ad <= dl ? diff * diff : dl * (2.f * ad - dl);
+    }
+    float4 dqv;
+    dqv.x = ac[0] * gsc; dqv.y = ac[1] * gsc; dqv.z = ac[2] * gsc; dqv.w = ac[3] * gsc;
+    *reinterpret_cast<float4*>(DQ + b * 4) = dqv;
+    TMP[b] = le;
     if (jb == 0) {
       c.q_sa[b] = qs; c.p_sa[b] = ps; c.target[b] = tg;
+      *reinterpret_cast<float4*>(c.dq_out + b * 4) = dqv;
       *reinterpret_cast<float4*>(c.q_out + b * 4) = *reinterpret_cast<const float4*>(qp);
       *reinterpret_cast<float4*>(c.p_out + b * 4) = *reinterpret_cast<const float4*>(pp);
     }
@@ -454,6 +483,15 @@ __global__ __launch_bounds__(512) void fc4_chain16_kernel(const ChainArgs c) {
   DDQ_STAMP(23);
 }
 
+template <int NZ>
+__global__ __launch_bounds__(512) void fc4_chain16_kernel(const ChainArgs c) {
+  fc4_chain16_body<NZ, false>(c);
+}
+// a non-default objective (ChainArgs::obj_*): the same body with its branches
+template <int NZ>
+__global__ __launch_bounds__(512) void fc4_chain16_obj_kernel(const ChainArgs c) {
+  fc4_chain16_body<NZ, true>(c);
+}
 
 // ---------------------------------------------------------------------------
 // K3: the Q tower's data gradients, one workgroup per image (train_val.

@@ -65,6 +65,14 @@ class MonitorRecord(ctypes.Structure):
                 ("param_rms", (ctypes.c_float * 10) * 2), ("grad_rms", ctypes.c_float * 10)]
 
 
+class Objective(ctypes.Structure):
+    """include/ddq_hip.h ddq_objective (16 bytes)."""
+    _fields_ = [("target", ctypes.c_int32), ("loss", ctypes.c_int32),
+                ("huber_delta", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+TARGETS = {"max": 0, "double": 1}          # include/ddq_hip.h enum ddq_target
+LOSSES = {"euclidean": 0, "huber": 1}      # include/ddq_hip.h enum ddq_loss
 STEP_NO_GRAD_STORE = 1     # include/ddq_hip.h DDQ_STEP_NO_GRAD_STORE
 FAULT_NONE, FAULT_MEET_TIMEOUT = 0, 1   # include/ddq_hip.h enum ddq_fault
 
@@ -115,6 +123,8 @@ _SIGS = {
     "ddq_forward_backward": (ctypes.c_int, [_P, _fp]),
     "ddq_forward_backward_async": (ctypes.c_int, [_P]),
     "ddq_forward_q": (ctypes.c_int, [_P]),
+    "ddq_set_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
+    "ddq_get_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
     "ddq_read_blob": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _i64]),
     "ddq_read_pool_mask": (ctypes.c_int, [_P, _i32, _P, _i64]),
     "ddq_select_action": (ctypes.c_int, [_P, _P, _i32, _P]),

@@ -2,7 +2,7 @@
 with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
-reset_log=False)``:
+reset_log=False, objective=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -10,7 +10,10 @@ reset_log=False)``:
 * ``model`` -- ``.npz`` file of {name: W, name + "/1": b} blobs, or None for the
   prototxt fillers;
 * ``driver`` -- "host:port" of the parameter server, or None (dummy pull/push,
-  baristanet.py:99-103, :125-133).
+  baristanet.py:99-103, :125-133);
+* ``objective`` -- None (the reference's max target and Euclidean loss) or a dict
+  of ``DeepQNet.set_objective`` arguments, e.g. ``{"target": "double", "loss":
+  "huber", "huber_delta": 1.0}``.
 
 The input buffers ``state``, ``action``, ``reward``, ``next_state``,
 ``non_terminal`` have the reference's shapes (baristanet.py:30-34).  They are
@@ -62,11 +65,13 @@ class _Blob:
 
 class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
-                 reset_log=False, device=0, mode="gpu"):
+                 reset_log=False, device=0, mode="gpu", objective=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
         self.dqn = DeepQNet(batch=batch, frame=frame, device=device, gamma=gamma, mode=mode)
+        if objective is not None:
+            self.dqn.set_objective(**objective)
         if model is not None and os.path.exists(str(model)):
             with np.load(model, allow_pickle=False) as f:
                 blobs = {k: f[k] for k in f.files}

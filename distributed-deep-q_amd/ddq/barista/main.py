@@ -8,6 +8,7 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
         [--port 50001] [--driver 127.0.0.1:5500|None] [--dataset replay-dataset.hdf5]
         [--dset-size 1000] [--overwrite] [--debug] [--initial-replay 20000]
         [--device-actor [--actor-seed N]] [--logpath PREFIX]
+        [--double-q] [--huber-delta D]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
 step on the host through the CPU twin libddq_cpu.so (main.py:128,149-151, the
@@ -17,6 +18,11 @@ reference's Caffe CPU mode: BASELINE configs[0]).
 ``ddq.actor.DeviceActor``: the game, the preprocessing, the ε-greedy choice and
 the replay add run inside the net's context (ddq_actor_step_async), so
 ``generate_experience`` only enqueues.
+
+``--double-q`` and ``--huber-delta D`` (both off by default) select the TD
+objective the gradients are computed for (``DeepQNet.set_objective``): the
+Double-DQN target r + gamma P(s', argmax_a Q(s',a)) in place of the max, and the
+Huber loss with band D in place of the Euclidean one.  Both work in either mode.
 
 ``--logpath PREFIX`` (off by default) makes ``net.log()`` append the step's loss
 and every blob's gradient / parameter RMS to files under ``PREFIX-<date>``
@@ -97,16 +103,35 @@ def get_args(argv=None):
                     help="seed of the device actor's random stream (default: random)")
     ap.add_argument("--logpath", default=None,
                     help="prefix of the per-step loss / norm log directory (default: no log)")
+    ap.add_argument("--double-q", dest="double_q", action="store_true",
+                    help="Double-DQN target: P at argmax_a Q(s',a) instead of max_a P")
+    ap.add_argument("--huber-delta", dest="huber_delta", type=float, default=None,
+                    help="Huber loss with this band instead of the Euclidean loss")
     args = ap.parse_args(argv)
+    if args.huber_delta is not None and not args.huber_delta > 0:
+        ap.error("--huber-delta must be > 0")
     if args.driver == "None":
         args.driver = None
     return args
 
 
+def objective_of(args):
+    """BaristaNet's ``objective`` for --double-q / --huber-delta (None: neither)."""
+    double, delta = getattr(args, "double_q", False), getattr(args, "huber_delta", None)
+    if not double and delta is None:
+        return None
+    obj = {"target": "double" if double else "max",
+           "loss": "euclidean" if delta is None else "huber"}
+    if delta is not None:
+        obj["huber_delta"] = delta
+    return obj
+
+
 def build_worker(args):
     model = None if args.model in ("none", "None") else args.model
     net = BaristaNet(args.architecture, model, args.driver,
-                     logpath=getattr(args, "logpath", None), mode=args.mode)
+                     logpath=getattr(args, "logpath", None), mode=args.mode,
+                     objective=objective_of(args))
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
                            overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode)
     net.add_dataset(replay)

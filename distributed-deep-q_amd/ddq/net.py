@@ -20,7 +20,8 @@ GAMMA = 0.85        # models/deepq/train_val.prototxt:473
 NUM_ACTIONS = 4     # barista/constants.py:8
 NFRAME = 4          # expgain.py:9
 
-BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0}
+BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0,
+         "Qn_out": 4, "Q_out.diff": 4}
 
 # include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
 MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
@@ -191,6 +192,27 @@ class DeepQNet:
         """net.forward(end='Q_out') on the bound minibatch."""
         self._check(self.lib.ddq_forward_q(self.ctx))
 
+    def set_objective(self, target="max", loss="euclidean", huber_delta=1.0):
+        """The TD objective every later gradient is computed for
+        (ddq_set_objective): target "max" (the reference's r + gamma max_a P) or
+        "double" (P at argmax_a Q(s',a): blob "Qn_out"); loss "euclidean" or
+        "huber" (the TD error clipped to +-huber_delta in the backward pass)."""
+        if target not in _lib.TARGETS:
+            raise ValueError("target must be one of %s" % (tuple(_lib.TARGETS),))
+        if loss not in _lib.LOSSES:
+            raise ValueError("loss must be one of %s" % (tuple(_lib.LOSSES),))
+        o = _lib.Objective(_lib.TARGETS[target], _lib.LOSSES[loss],
+                           float(huber_delta) if loss == "huber" else 0.0, 0)
+        self._check(self.lib.ddq_set_objective(self.ctx, ctypes.byref(o)))
+
+    def objective(self):
+        """{"target", "loss", "huber_delta"} as set_objective takes them."""
+        o = _lib.Objective()
+        self._check(self.lib.ddq_get_objective(self.ctx, ctypes.byref(o)))
+        names = lambda d, v: next(k for k, x in d.items() if x == v)  # noqa: E731
+        return {"target": names(_lib.TARGETS, o.target), "loss": names(_lib.LOSSES, o.loss),
+                "huber_delta": float(o.huber_delta)}
+
     def blob(self, name):
         if name not in BLOBS:
             raise KeyError(name)
@@ -198,7 +220,7 @@ class DeepQNet:
         n = B * BLOBS[name] if BLOBS[name] else 1
         out = np.empty(n, np.float32)
         self._check(self.lib.ddq_read_blob(self.ctx, name.encode(), ptr(out), n))
-        if name in ("Q_out", "P_out"):
+        if BLOBS[name] == 4:
             return out.reshape(B, 4, 1, 1)
         if name == "loss":
             return out.reshape(())

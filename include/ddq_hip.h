@@ -48,7 +48,10 @@ extern "C" {
                               ddq_monitor_record_async, ddq_monitor_read), likewise;
                               and the laned ring and actor pool (ddq_replay_set_lanes,
                               ddq_replay_lanes, ddq_actors_create,
-                              ddq_actors_step_async, ddq_actors_read), likewise */
+                              ddq_actors_step_async, ddq_actors_read), likewise;
+                              and the selectable objective (ddq_set_objective,
+                              ddq_get_objective; blobs "Qn_out", "Q_out.diff"),
+                              likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -303,7 +306,11 @@ int ddq_forward_backward_async(ddq_ctx* ctx);
 /* forward(end='Q_out') over the bound minibatch (baristanet.py:144). */
 int ddq_forward_q(ddq_ctx* ctx);
 /* net.blobs[name].data for name in {"Q_out","P_out","Q_sa","P_sa",
- * "target_Q_sa","loss"} (B*4, B*4, B, B, B, 1 floats). */
+ * "target_Q_sa","loss"} (B*4, B*4, B, B, B, 1 floats); and, with no reference
+ * counterpart, "Q_out.diff" (B*4): the head's dQ of the last pass (the diff the
+ * loss layer hands to Q_out), and "Qn_out" (B*4): Q(s',.) under theta_Q of the
+ * last pass with the double target (DDQ_ESTATE under DDQ_TARGET_MAX: nothing
+ * computed it). */
 int ddq_read_blob(ddq_ctx* ctx, const char* name, float* dst, int64_t n);
 /* Argmax/ReLU routing bytes of pool layer 1..3 of the Q tower for the last
  * forward_backward, in Caffe (B,C,H/2,W/2) order: 0..3 = first-max position
@@ -312,6 +319,41 @@ int ddq_read_pool_mask(ddq_ctx* ctx, int32_t layer, uint8_t* dst, int64_t n);
 /* select_action (baristanet.py:142-146) for n states (n <= B, uint8 C,H,W):
  * argmax_a Q(s,a), first max wins.  Does not touch the bound minibatch. */
 int ddq_select_action(ddq_ctx* ctx, const uint8_t* states, int32_t n, int32_t* actions);
+
+/* ---------------- selectable TD objective (no reference counterpart) ------- */
+/* The reference trains on target = r + gamma max_a P(s',a) nt under a Euclidean
+ * loss (train_val.prototxt:385-483); that is the default, {MAX, EUCLIDEAN}, and
+ * with it every launch and every bit is what it is without this section.
+ * Per image b, in fp32 as the head computes:
+ *   MAX     P_sa = max_a P_out[b][a] * nt
+ *   DOUBLE  a* = first maximum of Qn_out[b][0..3] (select_action's rule), where
+ *           Qn_out = Q(s',.) under theta_Q; P_sa = P_out[b][a*] * nt
+ *   target = gamma P_sa + r,  d = Q_sa - target
+ *   EUCLIDEAN  dQ[b][a] = act[b][a] d / B;  loss = sum_b d^2 / (2B)
+ *   HUBER      dQ[b][a] = act[b][a] clamp(d, -delta, delta) / B;
+ *              loss = sum_b h(d_b) / B, h(d) = d^2/2 for |d| <= delta, else
+ *              delta (|d| - delta/2)
+ * With DOUBLE every pass begins with a forward-only run of the Q tower over the
+ * minibatch's next_state (ddq_forward_q's kernels at n = B, on the ctx stream,
+ * in the acting scratch) into a buffer of its own, "Qn_out".  The objective is a
+ * property of the ctx, honoured by every call that computes a gradient
+ * (ddq_forward_backward[_async], the step modes, ddq_profile_step -- the extra
+ * forward's kernels are listed as "qn_<name>" --, the group and exchanged steps,
+ * and the async exchange for an objective set before ddq_async_begin). */
+enum ddq_target { DDQ_TARGET_MAX = 0, DDQ_TARGET_DOUBLE = 1 };
+enum ddq_loss   { DDQ_LOSS_EUCLIDEAN = 0, DDQ_LOSS_HUBER = 1 };
+typedef struct ddq_objective {      /* 16 bytes */
+  int32_t target;        /* enum ddq_target */
+  int32_t loss;          /* enum ddq_loss */
+  float   huber_delta;   /* HUBER: finite, > 0; ignored otherwise */
+  int32_t reserved;      /* 0 */
+} ddq_objective;
+/* Synchronises, invalidates graphs, and does the extra forward's one-time
+ * set-up (so none of it happens inside a capture).  DDQ_EINVAL: unknown enum
+ * value, huber_delta not finite or <= 0 with HUBER, reserved != 0.  DDQ_ESTATE:
+ * the async exchange has begun on the ctx. */
+int ddq_set_objective(ddq_ctx* ctx, const ddq_objective* obj);
+int ddq_get_objective(const ddq_ctx* ctx, ddq_objective* obj);
 
 /* ---------------- device-resident actor (expgain.py, gamesim/SnakeGame.py) -- */
 /* The worker's "act once, add the transition" (main.py:61-103) without the
