@@ -42,7 +42,7 @@ inline void ddq_launch(F kern, const dim3& grid, const dim3& block, uint32_t sme
 // ddq_debug_stamps / tools/gpu/stamps.py): lane 0 of a workgroup records the
 // 100 MHz real-time clock at a kernel's phase boundaries.  Empty otherwise.
 #ifdef DDQ_STAMPS
-constexpr int kStampSlots = 56, kStampBlocks = 512;
+constexpr int kStampSlots = 58, kStampBlocks = 640;
 extern __device__ uint64_t g_stamps[kStampBlocks * kStampSlots];
 #define DDQ_STAMP(slot)                                                        \
   do {                                                                         \

@@ -844,6 +844,9 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
 #pragma unroll
   for (int a = 0; a < 4; ++a) acv[a] = action[b * 4 + a];
   const float ntb = nonterm[b], rwb = reward[b];
+  // fc5's bias, for the n < 8 threads that add it between the two barriers
+  // (loaded there, its latency sat on the kernel's chain)
+  const float b5v = n < 8 ? (n < 4 ? thq : thp)[b5_off + (n & 3)] : 0.f;
   // split-K partial sums of both towers, summed in split order
   float acc2[2] = {0.f, 0.f};
   {
@@ -885,8 +888,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) t += red[i][n];
-    const float* th = n < 4 ? thq : thp;
-    t += th[b5_off + (n & 3)];
+    t += b5v;
     qp[n] = t;
     (n < 4 ? outq : outp)[b * 4 + (n & 3)] = t;
   }

@@ -18,7 +18,9 @@
 // in fixed order and stored as the group's fp32 slab in the wgrad reducer's
 // layout ([group][co][NP], bias at n = KC; deterministic, no atomics).  The
 // bias column is summed on the VALU (fp32, from the staged split values) by
-// the ky == 0 workgroups.
+// the ky == 0 workgroups (BIAS), or by bias units of its own (the pair's
+// conv2: wgrads_bias_body).  A row whose input row y+ky-P lies outside the
+// image adds nothing to the tiles: it is neither staged nor multiplied.
 #pragma once
 #include "split.h"
 
@@ -72,10 +74,74 @@ struct WgradSGeom {
 
 
 
+// Bias column: the 8 channels of one staged 16-byte vector of bf16 pairs
+// (pair e = channels 2e, 2e + 1) added to bsum, low half before high half.
+// Every bias sum goes through here (the tile workgroups' and the bias
+// units'), so the order of the adds is one piece of code.
+__device__ __forceinline__ void wgrads_bias_add(float (&bsum)[8], const u32x4& o) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    bsum[2 * e] += __builtin_bit_cast(float, o[e] << 16);
+    bsum[2 * e + 1] += __builtin_bit_cast(float, o[e] & 0xffff0000u);
+  }
+}
+
+// One pooled 8-channel chunk of a row of parity qy = (row & 1) << 1: its two
+// expanded pixels (dx = d2 ^ (dpx & 1), the staging's store order), each
+// plane masked by the routing bytes, then added
+__device__ __forceinline__ void wgrads_bias_pooled(float (&bsum)[8], const u32x4& d0,
+                                                   const u32x4& d1, const u32x4& d2v,
+                                                   const u32x2& m, uint32_t qy, int dpx) {
+#pragma unroll
+  for (int d2 = 0; d2 < 2; ++d2) {
+    const int dx = d2 ^ (dpx & 1);
+    const uint32_t qd = qy | dx;
+    uint32_t keep[4];
+    route_keep(m[0], qd * 0x01010101u, keep[0], keep[1]);
+    route_keep(m[1], qd * 0x01010101u, keep[2], keep[3]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      const u32x4& v = p == 0 ? d0 : (p == 1 ? d1 : d2v);
+      u32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = v[e] & keep[e];
+      wgrads_bias_add(bsum, o);
+    }
+  }
+}
+
+// The bias column's end: the waves' sums as a [wave][lane][8] LDS image
+// (lanes with equal lane & 3 share 8 channels), 32 threads add the 64 values
+// of their channel in (wave, lane) order, one write-through store each to
+// column KC of the group's slab
+template <int KC>
+__device__ __forceinline__ void wgrads_bias_tail(const float (&bsum)[8], float* red, int w, int lane,
+                                                 __amdgpu_buffer_rsrc_t srs, uint32_t sbase, int NP) {
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 8; ++j) red[(w * 64 + lane) * 8 + j] = bsum[j];
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    const int co = threadIdx.x, c8 = co >> 3, j = co & 7;
+    // all 64 values (wave, then lane order) first, then the adds in that
+    // order: as one loop every add waited for its own LDS read, and the
+    // ky == 0 workgroups ended ~4.6 us after the others -- the launch's
+    // last (profiles/r07_pair_stamps_before.txt)
+    float x[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) x[i] = red[((i >> 4) * 64 + c8 + 4 * (i & 15)) * 8 + j];
+    float v = 0.f;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) v += x[i];
+    wt_store(srs, sbase + (uint32_t)((co * NP + KC) * 4), v);
+  }
+}
+
 // DSRC: the dconv rows' source -- 0: pooled split + routing bytes (conv2's),
 // 1: pooled fp32 + routing bytes, split while staged, 2: expanded split
-// (dfull: pure 16-byte copies, no VALU per element)
-template <int CIN, int COUT, int KS, int PAD, int WMAX, int DSRC>
+// (dfull: pure 16-byte copies, no VALU per element).  BIAS: the ky == 0
+// workgroups also sum the bias column
+template <int CIN, int COUT, int KS, int PAD, int WMAX, int DSRC, bool BIAS>
 __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int L) {
   constexpr bool DF32 = DSRC == 1;
   constexpr int NCB = CIN / 32;
@@ -97,7 +163,7 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
   const int r0 = g * a.RPG;
   const int r1 = min(a.B * H, r0 + a.RPG);
   // stamp slots (DDQ_STAMPS builds): conv2's unit 48..50, conv3's 51..53 --
-  // body entry, wave 0's last row done, exit
+  // body entry, wave 0's last row done, exit (a bias unit's: 55, 56)
   [[maybe_unused]] constexpr int SB = CIN == 32 ? 48 : 51;
   DDQ_STAMP(SB);
 
@@ -150,6 +216,7 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
     u32x4 d[3][NPD];
     float4 f[2][NPD];    // DF32: the 8 fp32 values of the chunk
     u32x2 m[NPD];
+    bool zin;            // live row whose input row is outside the image
   };
   // Every load is issued unconditionally as a bounds-checked buffer load: an
   // out-of-range vector gets the offset kOOB and reads 0, so there is no
@@ -183,6 +250,7 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
     const bool live = row < r1;
     const int yi = ly + ky - PAD;
     const bool vin = live && (unsigned)yi < (unsigned)H;
+    R.zin = __builtin_amdgcn_readfirstlane((int)(live && !vin)) != 0;   // wave-uniform
     const uint32_t i0 = (uint32_t)(((lb * H + yi) * W + ipx) * CIN + 8 * ic8);
 #pragma unroll
     for (int u = 0; u < NPI; ++u) {
@@ -230,7 +298,13 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
     ly += 4;
     if (ly >= H) { ly -= H; ++lb; }
   };
+  // A row whose input row is outside the image (R.zin) is not staged unless
+  // its dconv row feeds the bias sum, and never multiplied: its products are
+  // all zero, and every later compute() reads only what that row's own
+  // store() wrote (all W pixels of the six planes; the halo and tails are
+  // zeroed once above and never written by a row)
   auto store = [&](Regs& R, int row) {
+    if (R.zin && !(BIAS && ky == 0)) return;
     const uint32_t qy = (row & 1) << 1;   // H is even: row and y have one parity
     if (DF32) {   // split the fp32 chunk into the three planes (split.h split3)
 #pragma unroll
@@ -267,13 +341,7 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           *reinterpret_cast<u32x4*>(rd + p * dpl + px * Geo::PSD + 8 * dc8) = R.d[p][u];
-          if (ky == 0) {   // bias: fp32 value = sum of the three planes
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              bsum[2 * e] += __builtin_bit_cast(float, R.d[p][u][e] << 16);
-              bsum[2 * e + 1] += __builtin_bit_cast(float, R.d[p][u][e] & 0xffff0000u);
-            }
-          }
+          if (BIAS && ky == 0) wgrads_bias_add(bsum, R.d[p][u]);   // fp32 value = sum of the three planes
         }
       }
     }
@@ -298,13 +366,7 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = R.d[p][u][e] & keep[e];
           *reinterpret_cast<u32x4*>(rd + p * dpl + (2 * px + dx) * Geo::PSD + 8 * dc8) = o;
-          if (ky == 0) {   // bias: fp32 value = sum of the three planes
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              bsum[2 * e] += __builtin_bit_cast(float, o[e] << 16);
-              bsum[2 * e + 1] += __builtin_bit_cast(float, o[e] & 0xffff0000u);
-            }
-          }
+          if (BIAS && ky == 0) wgrads_bias_add(bsum, o);   // fp32 value = sum of the three planes
         }
       }
     }
@@ -366,9 +428,10 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
     if (row < r1) load(g, row);
     for (; row < r1; row += 4) {
       store(g, row);
+      const bool zin = g.zin;
       load(g, row + 4);             // rows past r1 read nothing (live = false)
       __builtin_amdgcn_sched_barrier(0);
-      compute();
+      if (!zin) compute();
     }
   }
   DDQ_STAMP(SB + 1);
@@ -400,27 +463,84 @@ __device__ __forceinline__ void wgrads_body(const WgradSArgs& a, char* smem, int
       wt_store4(srs, sbase + (uint32_t)((co * a.NP + nbase + (l0 & 31)) * 4), v);
     }
   }
-  if (ky == 0) {   // bias column n = KC: lanes with equal lane & 3 share 8 channels
-    __syncthreads();
+  if (BIAS && ky == 0) wgrads_bias_tail<KC>(bsum, red, w, lane, srs, sbase, a.NP);
+  DDQ_STAMP(SB + 2);
+}
+
+// A bias unit: column KC of one (row group g, co block cb) slab of a DSRC 0
+// weight gradient, and nothing else -- what a ky == 0 tile workgroup does for
+// that column: the four waves walk the rows r0 + w, r0 + w + 4, ... with the
+// tile body's lane -> (pooled pixel, 8-channel chunk) mapping, bounds-checked
+// loads and routing masks, and add in its order.  No input rows, no row
+// staging, no MFMAs; LDS only for the tail's 8 KB image.
+template <int CIN, int COUT, int KS, int WMAX>
+__device__ __forceinline__ void wgrads_bias_body(const WgradSArgs& a, char* smem, int L) {
+  constexpr int KC = KS * KS * CIN;
+  constexpr int NCO = COUT / 32;
+  constexpr int NPD = (WMAX / 2 + 15) / 16;
+  const int W = a.W, H = a.H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  // XCD-aware decode: both co blocks of row group g get the same L % 8
+  const int xcd = L & 7, q = L >> 3;
+  const int cb = q % NCO, g = xcd + 8 * (q / NCO);
+  if (g >= a.G) return;
+  const int r0 = g * a.RPG;
+  const int r1 = min(a.B * H, r0 + a.RPG);
+  DDQ_STAMP(55);   // stamp slots 55, 56: a bias unit's entry and exit
+
+  constexpr uint32_t kOOB = 0x80000000u;
+  const uint32_t db = (uint32_t)(a.B * (H >> 1) * (W >> 1) * COUT);
+  const __amdgpu_buffer_rsrc_t rd_g[3] = {
+      __builtin_amdgcn_make_buffer_rsrc((void*)a.dpool, (short)0, (int)(db * 2), 0x00020000),
+      __builtin_amdgcn_make_buffer_rsrc((void*)(a.dpool + a.d_elems), (short)0, (int)(db * 2),
+                                        0x00020000),
+      __builtin_amdgcn_make_buffer_rsrc((void*)(a.dpool + 2 * a.d_elems), (short)0, (int)(db * 2),
+                                        0x00020000)};
+  const __amdgpu_buffer_rsrc_t rm_g =
+      __builtin_amdgcn_make_buffer_rsrc((void*)a.droute, (short)0, (int)db, 0x00020000);
+  const int dc8 = lane & 3, dpx = lane >> 2;
+  struct Regs {
+    u32x4 d[3][NPD];
+    u32x2 m[NPD];
+  };
+  int lb = (r0 + w) / H, ly = (r0 + w) - lb * H;   // (image, y) of the next row to load
+  auto load = [&](Regs& R, int row) {
+    const bool live = row < r1;
+    const uint32_t o0 =
+        (uint32_t)(((lb * (H >> 1) + (ly >> 1)) * (W >> 1) + dpx) * COUT + cb * 32 + 8 * dc8);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) red[(w * 64 + lane) * 8 + j] = bsum[j];
-    __syncthreads();
-    if (threadIdx.x < 32) {
-      const int co = threadIdx.x, c8 = co >> 3, j = co & 7;
-      // all 64 values (wave, then lane order) first, then the adds in that
-      // order: as one loop every add waited for its own LDS read, and the
-      // ky == 0 workgroups ended ~4.6 us after the others -- the launch's
-      // last (profiles/r07_pair_stamps_before.txt)
-      float x[64];
+    for (int u = 0; u < NPD; ++u) {
+      const bool ok = live && dpx + 16 * u < (W >> 1);
+      const uint32_t o = ok ? o0 + (uint32_t)(u * 16 * COUT) : 0u;
+      R.m[u] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rm_g, (int)(ok ? o : kOOB), 0, 0));
 #pragma unroll
-      for (int i = 0; i < 64; ++i) x[i] = red[((i >> 4) * 64 + c8 + 4 * (i & 15)) * 8 + j];
-      float v = 0.f;
+      for (int p = 0; p < 3; ++p)
+        R.d[p][u] = __builtin_bit_cast(
+            u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd_g[p], (int)(ok ? o * 2 : kOOB), 0, 0));
+    }
+    ly += 4;
+    if (ly >= H) { ly -= H; ++lb; }
+  };
+  float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // channels 8*(lane&3) + j of cb
+  {   // two register sets: the next row's loads fly under this row's adds
+    Regs c, n;
+    int row = r0 + w;
+    if (row < r1) load(c, row);
+    for (; row < r1; row += 4) {
+      load(n, row + 4);             // rows past r1 read nothing (live = false)
+      const uint32_t qy = (row & 1) << 1;   // H is even: row and y have one parity
 #pragma unroll
-      for (int i = 0; i < 64; ++i) v += x[i];
-      wt_store(srs, sbase + (uint32_t)((co * a.NP + KC) * 4), v);
+      for (int u = 0; u < NPD; ++u) {
+        if (dpx + 16 * u >= (W >> 1)) continue;
+        wgrads_bias_pooled(bsum, c.d[0][u], c.d[1][u], c.d[2][u], c.m[u], qy, dpx);
+      }
+      c = n;
     }
   }
-  DDQ_STAMP(SB + 2);
+  const __amdgpu_buffer_rsrc_t srs = wt_rsrc(a.part, (uint32_t)((size_t)a.G * COUT * a.NP * 4));
+  const uint32_t sbase = (uint32_t)(((size_t)g * COUT + (size_t)cb * 32) * a.NP * 4);
+  wgrads_bias_tail<KC>(bsum, reinterpret_cast<float*>(smem), w, lane, srs, sbase, a.NP);
+  DDQ_STAMP(56);
 }
 
 template <int CIN, int PAD>
@@ -441,16 +561,27 @@ inline size_t wgrads_smem_bytes(int W) {
 // takes their slots, so the SIMDs hold two waves for 44 % of the CUs' time,
 // one for 37 % (profiles/r07_pair_stamps_before.txt; DESIGN section 6 for the
 // eight-lane form that was measured against this and not kept).
+// The first's bias column has units of its own in a third range behind the
+// second's, one per (row group, co block): dispatched last, they take the
+// free slots and those the second's workgroups leave, and end before the
+// first's tiles (profiles/r08_pair_stamps_after.txt), whose ky == 0
+// workgroups -- the launch's last while they carried it
+// (r08_pair_stamps_before.txt) -- now end with the others.  The second's bias
+// stays with its ky == 0 workgroups.
 template <int CIN0, int COUT0, int KS0, int PAD0, int WMAX0, int DSRC0, int CIN1, int COUT1,
           int KS1, int PAD1, int WMAX1, int DSRC1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrads_pair_kernel(
-    const WgradSArgs a0, const WgradSArgs a1, int n0) {
+    const WgradSArgs a0, const WgradSArgs a1, int n0, int n1) {
+  static_assert(DSRC0 == 0, "bias units read the split pooled gradient");
   extern __shared__ __attribute__((aligned(16))) char sm_wgp[];
   DDQ_STAMP_HWID(54);
-  if ((int)blockIdx.x < n0)
-    wgrads_body<CIN0, COUT0, KS0, PAD0, WMAX0, DSRC0>(a0, sm_wgp, blockIdx.x);
+  const int L = blockIdx.x;
+  if (L < n0)
+    wgrads_body<CIN0, COUT0, KS0, PAD0, WMAX0, DSRC0, false>(a0, sm_wgp, L);
+  else if (L < n0 + n1)
+    wgrads_body<CIN1, COUT1, KS1, PAD1, WMAX1, DSRC1, true>(a1, sm_wgp, L - n0);
   else
-    wgrads_body<CIN1, COUT1, KS1, PAD1, WMAX1, DSRC1>(a1, sm_wgp, blockIdx.x - n0);
+    wgrads_bias_body<CIN0, COUT0, KS0, WMAX0>(a0, sm_wgp, L - n0 - n1);
 }
 
 template <int CIN0, int COUT0, int KS0, int PAD0, int WMAX0, int DSRC0, int CIN1, int COUT1,
@@ -466,7 +597,8 @@ inline hipError_t launch_wgrads_pair_w(const WgradSArgs& a0, const WgradSArgs& a
     return e;
   const int n0 = (a0.G + 7) / 8 * 8 * (COUT0 / 32) * KS0;
   const int n1 = (a1.G + 7) / 8 * 8 * (COUT1 / 32) * KS1;
-  ddq_launch(kern, dim3(n0 + n1), dim3(256), shm, st, a0, a1, n0);
+  const int n2 = (a0.G + 7) / 8 * 8 * (COUT0 / 32);   // the first's bias units
+  ddq_launch(kern, dim3(n0 + n1 + n2), dim3(256), shm, st, a0, a1, n0, n1);
   return hipGetLastError();
 }
 

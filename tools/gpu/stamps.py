@@ -18,7 +18,7 @@ S = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 mode = sys.argv[4] if len(sys.argv) > 4 else "fb"
-SLOTS, BLOCKS = 56, 512
+SLOTS, BLOCKS = 58, 640
 
 net = ddq.DeepQNet(batch=B, frame=S)
 rng = np.random.default_rng(0)
@@ -75,7 +75,8 @@ for r, t in enumerate(runs):
               "since launch start (us): %s" % (r, lo, len(tt), (tt[:, used].max() - t0) * 10 / 1000,
                                             " ".join("%d:%.2f/%.2f" % (k, a, b) for k, (a, b) in rel.items())))
 # the conv2 + conv3 weight-gradient pair (wgrads.h): per unit kind (conv2's
-# slots 48..50, conv3's 51..53: entry, wave 0's last row done, exit) the times
+# slots 48..50, conv3's 51..53: entry, wave 0's last row done, exit; conv2's
+# bias units 55, 56: entry, exit) the times
 # since the launch's first entry, and from slot 54 (the hardware id) how the
 # units share the CUs and how many waves a SIMD holds over the launch
 for r, t in enumerate(runs):
@@ -84,7 +85,7 @@ for r, t in enumerate(runs):
     if not any(len(b) for _, _, b in kinds):
         continue
     t0 = min(t[b, lo].min() for _, lo, b in kinds if len(b))
-    t1 = max(t[b, lo + 2].max() for _, lo, b in kinds if len(b))
+    t1 = max(max(t[b, lo + 2].max() for _, lo, b in kinds if len(b)), t[:, 56].max())
     us = lambda v: (v - t0) * 10 / 1000
     print("pair run %d: launch span %.2f us" % (r, us(t1)))
     for name, lo, b in kinds:
@@ -95,6 +96,22 @@ for r, t in enumerate(runs):
               "exit min %.2f median %.2f max %.2f; own length median %.2f us"
               % (name, len(b), np.median(e), e.max(), np.median(d), d.max(), x.min(),
                  np.median(x), x.max(), np.median(x - e)))
+    # conv2's units by tap row (block L: ky = ((L >> 3) % (2 * 5)) % 5): which of
+    # them set the launch's end
+    b2 = kinds[0][2]
+    for ky in range(5 if len(b2) else 0):
+        bk = b2[((b2 >> 3) % 10) % 5 == ky]
+        d, x = us(t[bk, 49]), us(t[bk, 50])
+        print("  conv2 ky %d: %d units; rows done median %.2f max %.2f; exit min %.2f median %.2f "
+              "max %.2f" % (ky, len(bk), np.median(d), d.max(), x.min(), np.median(x), x.max()))
+    # conv2's bias units (slots 55, 56: entry, exit), dispatched behind conv3's
+    bb = np.nonzero(t[:, 55] > 0)[0]
+    if len(bb):
+        e, x = us(t[bb, 55]), us(t[bb, 56])
+        print("  conv2 bias units: %d; entry min %.2f median %.2f max %.2f; exit min %.2f median "
+              "%.2f max %.2f; own length median %.2f us"
+              % (len(bb), e.min(), np.median(e), e.max(), x.min(), np.median(x), x.max(),
+                 np.median(x - e)))
     hw = u[:, 54]
     has = np.nonzero((hw >> np.uint64(62)) & np.uint64(1))[0]
     if not len(has):
@@ -117,8 +134,8 @@ for r, t in enumerate(runs):
     for bl in per_cu.values():
         ev = []
         for b in bl:
-            ent = min(t[b, lo] for lo in (48, 51) if t[b, lo] > 0)
-            ext = max(t[b, lo + 2] for lo in (48, 51) if t[b, lo] > 0)
+            ent = min(t[b, lo] for lo in (48, 51, 55) if t[b, lo] > 0)
+            ext = max(t[b, lo + (1 if lo == 55 else 2)] for lo in (48, 51, 55) if t[b, lo] > 0)
             ev += [(ent, waves[b] / 4.0), (ext, -waves[b] / 4.0)]
         ev.sort()
         cur, last = 0.0, t0
