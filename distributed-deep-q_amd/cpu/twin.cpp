@@ -99,6 +99,7 @@ struct ddq_ctx {
   // valid per lane
   int32_t lanes = 1;
   int64_t lane_len = 0;
+  int32_t nstep = 1;               // n-step returns (ddq_replay_set_nstep)
   int64_t steps = 0;
   // Snake actor (ddq_actor_*): 4-board history (oldest first), the start board,
   // the zoom maps and the RNG stream position
@@ -480,21 +481,55 @@ float apply_rule(const ddq_update_cfg& u, bool first, bool is_bias, float th, fl
   }
 }
 
+// n-step returns (include/ddq_hip.h): forbidden start slots, the allowed count
+// per lane
+bool slot_forbidden(const ddq_ctx* c, int64_t x) {
+  int64_t d = c->head - 1 - x;
+  if (d < 0 && c->nstep >= 2 && c->valid == c->lane_len) d += c->lane_len;
+  return d >= 0 && d < c->nstep;
+}
+
+int64_t allowed_slots(const ddq_ctx* c) {
+  if (c->nstep < 2) return c->valid - 1;
+  if (c->valid == c->lane_len) return c->lane_len - c->nstep;
+  const int64_t lo = std::max<int64_t>(0, c->head - c->nstep);
+  const int64_t hi = std::min(c->head - 1, c->valid - 1);
+  return c->valid - std::max<int64_t>(0, hi - lo + 1);
+}
+
 void gather(ddq_ctx* c) {
   const int B = c->B, SS = c->S * c->S;
   const size_t slot = (size_t)kC * SS;
+  const int64_t L = c->lane_len;
+  const int n = c->nstep;
   for (int b = 0; b < B; ++b) {
     const int64_t i = c->idx[b];
-    // replay.py:159-183, the next slot within the lane (one lane: the ring)
-    const int64_t nxt = (i + 1) % c->lane_len == 0 ? i + 1 - c->lane_len : i + 1;
+    // replay.py:159-183 at n = 1; the n-step window s_k = base + (x + k) mod L
+    // within the lane (one lane: the ring), cut at its first terminal slot
+    const int64_t base = i - i % L, x = i - base;
+    auto sk = [&](int k) { return base + (x + k) % L; };
+    const int64_t nxt = sk(1);
+    int m = n;
+    bool term = false;
+    for (int k = 1; k <= n; ++k)
+      if (!c->r_nonterm[sk(k)]) { m = k; term = true; break; }
+    const int64_t sm = sk(m);
     for (size_t e = 0; e < slot; ++e) {
       c->state[(size_t)b * slot + e] = c->r_state[(size_t)i * slot + e];
-      c->next_state[(size_t)b * slot + e] = c->r_state[(size_t)nxt * slot + e];
+      c->next_state[(size_t)b * slot + e] = c->r_state[(size_t)sm * slot + e];
     }
     const int a = c->r_action[nxt];
     for (int k = 0; k < kA; ++k) c->action[(size_t)b * kA + k] = k == a ? 1.f : 0.f;
-    c->reward[b] = (float)c->r_reward[nxt];
-    c->nonterm[b] = c->r_nonterm[nxt] ? 1.f : 0.f;
+    // fp32, each * and + rounded on its own (-ffp-contract=off), in the device's order
+    float g = 1.0f, w = 1.0f, R = (float)c->r_reward[nxt];
+    for (int k = 2; k <= n; ++k) w = w * c->gamma;
+    for (int k = 2; k <= m; ++k) {
+      g = g * c->gamma;
+      const float gr = g * (float)c->r_reward[sk(k)];
+      R = R + gr;
+    }
+    c->reward[b] = R;
+    c->nonterm[b] = term ? 0.0f : w;
   }
 }
 
@@ -656,6 +691,7 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->head = c->valid = 0;
   c->lanes = 1;
   c->lane_len = capacity;
+  c->nstep = 1;
   return DDQ_OK;
 }
 
@@ -667,6 +703,9 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   if (lanes < 1 || c->capacity % lanes != 0 || c->capacity / lanes < 2)
     return fail(c, DDQ_EINVAL, "lanes must divide capacity %lld into lanes of >= 2 slots (got %d)",
                 (long long)c->capacity, lanes);
+  if (c->capacity / lanes <= c->nstep)
+    return fail(c, DDQ_EINVAL, "%d lanes of %lld slots cannot hold the ring's %d-step windows",
+                lanes, (long long)(c->capacity / lanes), c->nstep);
   if (lanes == c->lanes) return DDQ_OK;
   c->lanes = lanes;
   c->lane_len = c->capacity / lanes;
@@ -681,6 +720,23 @@ int ddq_replay_lanes(const ddq_ctx* c, int32_t* lanes, int64_t* lane_len) {
   if (!c->capacity) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
   if (lanes) *lanes = c->lanes;
   if (lane_len) *lane_len = c->lane_len;
+  return DDQ_OK;
+}
+
+int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (n < 1 || n > DDQ_NSTEP_MAX || n >= c->lane_len)
+    return fail(c, DDQ_EINVAL, "n-step length must be in [1, %d] and below lane_len %lld (got %d)",
+                DDQ_NSTEP_MAX, (long long)c->lane_len, n);
+  c->nstep = n;
+  return DDQ_OK;
+}
+
+int ddq_replay_nstep(const ddq_ctx* c, int32_t* n) {
+  if (!c || !n) return fail(nullptr, DDQ_EINVAL, "null argument");
+  if (!c->capacity) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  *n = c->nstep;
   return DDQ_OK;
 }
 
@@ -744,13 +800,16 @@ int ddq_replay_export(ddq_ctx* c, uint8_t* state, uint8_t* action, int16_t* rewa
 int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   if (!c || !idx) return fail(c, DDQ_EINVAL, "null argument");
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer");
-  if (batch > c->lanes * (c->valid - 1))   // B < valid on a plain ring
+  if (batch > c->lanes * allowed_slots(c))   // B < valid on a plain ring at n = 1
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 batch, (long long)(c->lanes * c->valid));
   if (batch != c->B) return fail(c, DDQ_EINVAL, "sample size %d != net batch %d", batch, c->B);
   for (int i = 0; i < batch; ++i) {
     if (idx[i] < 0 || idx[i] >= c->capacity || idx[i] % c->lane_len >= c->valid)
       return fail(c, DDQ_EINVAL, "index %d out of [0,valid)", idx[i]);
+    if (c->nstep >= 2 && slot_forbidden(c, idx[i] % c->lane_len))
+      return fail(c, DDQ_EINVAL, "index %d: its %d-step window reaches the write head", idx[i],
+                  c->nstep);
     if (i && idx[i] <= idx[i - 1]) return fail(c, DDQ_EINVAL, "indices must be sorted and distinct");
   }
   for (int i = 0; i < batch; ++i) {

@@ -53,6 +53,7 @@ struct ddq_ctx {
   int64_t head = 0, valid = 0, capacity = 0;
   int32_t lanes = 1;               // laned ring (ddq_replay_set_lanes): head / valid per lane
   int64_t lane_len = 0;            // capacity / lanes
+  int32_t nstep = 1;               // n-step returns (ddq_replay_set_nstep)
   // acting scratch
   uint8_t* act_u8 = nullptr;
   float *act_in = nullptr, *act_p3 = nullptr;
@@ -612,10 +613,14 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->head = c->valid = 0;
   c->lanes = 1;
   c->lane_len = capacity;
+  c->nstep = 1;
+  c->nb.nstep = 1;
   ReplayMeta m{};
   m.capacity = capacity;
   m.lanes = 1;
   m.lane_len = capacity;
+  m.nstep = 1;
+  m.gamma = c->nb.gamma;
   HIP_TRY(c, scopy(c, c->r_meta, &m, sizeof(m), hipMemcpyHostToDevice));
   invalidate_graph(c);
   return DDQ_OK;
@@ -650,10 +655,26 @@ int ddq_replay_info(const ddq_ctx* c, int64_t* head, int64_t* valid, int64_t* ca
   return DDQ_OK;
 }
 
-// fewest filled, allowed slots a draw of B needs: B <= lanes * (valid - 1),
-// which is B < valid on a plain ring
+// n-step returns (include/ddq_hip.h): forbidden start slots and the allowed
+// count A per lane, on the host mirror of head / valid
+static bool slot_forbidden(const ddq_ctx* c, int64_t x) {
+  int64_t d = c->head - 1 - x;
+  if (d < 0 && c->nstep >= 2 && c->valid == c->lane_len) d += c->lane_len;
+  return d >= 0 && d < c->nstep;
+}
+
+static int64_t allowed_slots(const ddq_ctx* c) {
+  if (c->nstep < 2) return c->valid - 1;
+  if (c->valid == c->lane_len) return c->lane_len - c->nstep;
+  const int64_t lo = std::max<int64_t>(0, c->head - c->nstep);
+  const int64_t hi = std::min(c->head - 1, c->valid - 1);
+  return c->valid - std::max<int64_t>(0, hi - lo + 1);
+}
+
+// fewest filled, allowed slots a draw of B needs: B <= lanes * A, which is
+// B <= lanes * (valid - 1) at n = 1 (B < valid on a plain ring)
 static bool too_few_slots(const ddq_ctx* c, int64_t batch) {
-  return batch > c->lanes * (c->valid - 1);
+  return batch > c->lanes * allowed_slots(c);
 }
 
 int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
@@ -664,6 +685,9 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   if (lanes < 1 || c->capacity % lanes != 0 || c->capacity / lanes < 2)
     return fail(c, DDQ_EINVAL, "lanes must divide capacity %lld into lanes of >= 2 slots (got %d)",
                 (long long)c->capacity, lanes);
+  if (c->capacity / lanes <= c->nstep)
+    return fail(c, DDQ_EINVAL, "%d lanes of %lld slots cannot hold the ring's %d-step windows",
+                lanes, (long long)(c->capacity / lanes), c->nstep);
   if (lanes == c->lanes) return DDQ_OK;
   TRY(set_dev(c));
   c->lanes = lanes;
@@ -682,6 +706,34 @@ int ddq_replay_lanes(const ddq_ctx* c, int32_t* lanes, int64_t* lane_len) {
   if (!c->r_state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
   if (lanes) *lanes = c->lanes;
   if (lane_len) *lane_len = c->lane_len;
+  return DDQ_OK;
+}
+
+static_assert(kNstepMax == DDQ_NSTEP_MAX, "the window loops unroll to DDQ_NSTEP_MAX");
+
+int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->async_on)
+    return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: set the n-step "
+                               "length before ddq_async_begin");
+  if (n < 1 || n > DDQ_NSTEP_MAX || n >= c->lane_len)
+    return fail(c, DDQ_EINVAL, "n-step length must be in [1, %d] and below lane_len %lld (got %d)",
+                DDQ_NSTEP_MAX, (long long)c->lane_len, n);
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);   // a pipelined chain holds a minibatch gathered under the old n
+  c->nstep = n;
+  c->nb.nstep = n;   // n >= 2: the n-step instantiations of the drawing / gathering kernels
+  HIP_TRY(c, scopy(c, reinterpret_cast<char*>(c->r_meta) + offsetof(ReplayMeta, nstep), &c->nstep,
+                   4, hipMemcpyHostToDevice));
+  return DDQ_OK;
+}
+
+int ddq_replay_nstep(const ddq_ctx* c, int32_t* n) {
+  if (!c || !n) return fail(nullptr, DDQ_EINVAL, "null argument");
+  if (!c->r_state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  *n = c->nstep;
   return DDQ_OK;
 }
 
@@ -745,6 +797,9 @@ int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   for (int i = 0; i < batch; ++i) {
     if (idx[i] < 0 || idx[i] >= c->capacity || idx[i] % c->lane_len >= c->valid)
       return fail(c, DDQ_EINVAL, "index %d out of [0,valid)", idx[i]);
+    if (c->nstep >= 2 && slot_forbidden(c, idx[i] % c->lane_len))
+      return fail(c, DDQ_EINVAL, "index %d: its %d-step window reaches the write head", idx[i],
+                  c->nstep);
     if (i && idx[i] <= idx[i - 1]) return fail(c, DDQ_EINVAL, "indices must be sorted and distinct");
   }
   TRY(set_dev(c));
@@ -808,7 +863,7 @@ static int check_batch_out(ddq_ctx* c, int32_t n, float* s0, float* a, float* r,
   if (n < 1) return fail(c, DDQ_EINVAL, "n must be >= 1");
   if ((int64_t)n * c->nb.S * c->nb.S >= (int64_t)1 << 31)
     return fail(c, DDQ_EINVAL, "n * S^2 must be < 2^31 (n=%d)", n);
-  if (n >= c->valid)
+  if (too_few_slots(c, n))   // n > A; n >= valid at nstep == 1
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 n, (long long)c->valid);
   return DDQ_OK;
@@ -829,10 +884,10 @@ int ddq_replay_sample_batch_async(ddq_ctx* c, int32_t n, uint64_t seed, int32_t*
     TRY(dalloc(c, &c->r_blk, (size_t)nblk));
   }
   HIP_TRY(c, launch_sample_batch(c->r_meta, c->valid, n, seed, c->batch_ctr++, c->r_bitmap,
-                                 c->r_blk, idx, c->stream));
+                                 c->r_blk, idx, c->stream, c->nstep));
   HIP_TRY(c, launch_gather_nchw(c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
                                 idx, n, c->nb.S, state, next_state, action, reward, nonterm,
-                                c->stream));
+                                c->stream, c->nstep));
   return DDQ_OK;
 }
 
@@ -844,7 +899,7 @@ int ddq_replay_gather_batch_async(ddq_ctx* c, const int32_t* idx, int32_t n, flo
   TRY(set_dev(c));
   HIP_TRY(c, launch_gather_nchw(c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
                                 idx, n, c->nb.S, state, next_state, action, reward, nonterm,
-                                c->stream));
+                                c->stream, c->nstep));
   return DDQ_OK;
 }
 

@@ -30,6 +30,7 @@ ParamLayout make_layout(int S);
 // ring of its own.  Lock-step writers fill it (pool.h), so the lanes share one
 // head in [0, lane_len) and one valid in [0, lane_len]: head / valid are then
 // the per-lane values.  lanes 0 or 1: one ring, lane_len == capacity.
+constexpr int kNstepMax = 8;   // DDQ_NSTEP_MAX
 struct ReplayMeta {
   int64_t head, valid, capacity;   // head, valid: the first 16 bytes (push_meta)
   uint64_t counter;        // device index-stream draws so far
@@ -37,6 +38,11 @@ struct ReplayMeta {
                            //         2 = a draw found no distinct index set
   int32_t lanes;
   int64_t lane_len;
+  // n-step returns (ddq_replay_set_nstep): the window length in [1, DDQ_NSTEP_MAX]
+  // and ddq_net_desc.gamma.  Here, not in a launch argument, so a captured
+  // graph's draw and gather workgroups read them like head / valid.
+  int32_t nstep;
+  float gamma;
 };
 
 // Fused apply: the update rule of the step.  ext = 0 (exchange-free steps):
@@ -105,6 +111,8 @@ struct NetBuffers {
                                     // one workgroup short, so its fan-in meeting times out
   FusedApplyCfg fa;                 // on: head latches the apply flags, the slab reduce
                                     // applies (FusedApplyCfg)
+  int nstep = 1;                    // the ring's n-step length: >= 2 launches the n-step
+                                    // instantiations of the kernels that draw or gather
   int book_inc;                     // param-server iterations per apply (1, or W: server mode)
   int head_bump;                    // the head kernel advances the draw counter without a
                                     // fused apply (async gradients: sample_gather draws)
@@ -347,11 +355,11 @@ hipError_t launch_monitor(const MonitorEnv& e, int32_t period, int64_t tag, hipS
 // and the Caffe-layout (n,4,S,S) f32 gather of replay.py:167-183
 hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t seed,
                                uint64_t ctr, uint32_t* bm, int32_t* blk, int32_t* idx,
-                               hipStream_t s);
+                               hipStream_t s, int nstep);
 hipError_t launch_gather_nchw(const uint8_t* st, const uint8_t* act, const int16_t* rew,
                               const uint8_t* nt, ReplayMeta* meta, const int32_t* idx, int n,
                               int S, float* s0, float* s1, float* action, float* reward,
-                              float* nonterm, hipStream_t s);
+                              float* nonterm, hipStream_t s, int nstep);
 hipError_t launch_tile(uint8_t* dst, const uint8_t* src, uint64_t pool_bytes, uint64_t total,
                        hipStream_t s);
 hipError_t launch_u8_to_nhwc(const uint8_t* src, int n, int S, float* dst, hipStream_t s);

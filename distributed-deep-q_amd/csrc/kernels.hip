@@ -100,6 +100,71 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 // mapped to slots (x div valid) * lane_len + x mod valid.
 constexpr int kDrawRounds = 4096;
 
+// n-step returns (ddq_replay_set_nstep, include/ddq_hip.h): may a sample start
+// at lane-local slot x of a lane with head h, v of L slots filled?  Not when
+// one of its n window slots x+1..x+n is the write head's or a later, unwritten
+// one: d = h - 1 - x in [0, n), d taken mod L on a full ring.  n = 1: x == h - 1.
+// (slots fit 32 bits: capacity < 2^31)
+__device__ __forceinline__ bool replay_forbidden(int x, int h, int v, int L, int n) {
+  int d = h - 1 - x;
+  if (d < 0 && n >= 2 && v == L) d += L;
+  return (uint32_t)d < (uint32_t)n;
+}
+
+// The n-step window of slot i: s_k = base + (x + k) mod L within i's lane,
+// m = the first k in 1..n whose slot is terminal (else n), s1, sm, and -- for
+// the one thread that writes a sample's scalars (`scalars`) -- the discounted
+// reward sum R and the remaining discount w (0 after a terminal), fp32 without
+// FMA contraction.  `next` false (a workgroup that only reads S[i]): no load.
+// The n non_terminal loads are independent (workgroup-uniform addresses, the
+// loop unrolled to kNstepMax), not a chain.  Only the n-step instantiations of
+// the kernels (NS, launched at nstep >= 2) contain it; n = 1 would give the
+// single-step scalars.  Slots fit 32 bits (capacity < 2^31).
+struct ReplayWindow {
+  int m;
+  float R, w;
+  uint32_t s1, sm;
+};
+
+__device__ __forceinline__ ReplayWindow replay_window(const int16_t* __restrict__ rew,
+                                                      const uint8_t* __restrict__ nt,
+                                                      const ReplayMeta* meta, int64_t i,
+                                                      bool next, bool scalars) {
+  const uint32_t Lu = (uint32_t)meta->lane_len, iu = (uint32_t)i;
+  const uint32_t base = meta->lanes > 1 ? iu - iu % Lu : 0u;
+  const uint32_t x = iu - base;
+  auto slot = [=](int k) -> uint32_t {   // k <= n < L: one conditional subtract
+    const uint32_t xk = x + (uint32_t)k;
+    return base + (xk >= Lu ? xk - Lu : xk);
+  };
+  ReplayWindow W{1, 0.f, 0.f, slot(1), slot(1)};
+  if (!next && !scalars) return W;
+  const int n = meta->nstep;
+  uint32_t term = 0;                    // bit k-1: s_k is terminal
+#pragma unroll
+  for (int k = 1; k <= kNstepMax; ++k)
+    if (k <= n) term |= (nt[slot(k)] == 0 ? 1u : 0u) << (k - 1);
+  W.m = term ? __ffs(term) : n;
+  W.sm = slot(W.m);
+  if (scalars) {   // one thread a sample: plain loops
+#pragma clang fp contract(off)
+    const float gamma = meta->gamma;
+    float g = 1.0f, w = 1.0f, R = (float)rew[W.s1];
+    for (int k = 2; k <= W.m; ++k) {
+      g = g * gamma;
+      const float gr = g * (float)rew[slot(k)];
+      R = R + gr;
+    }
+    for (int k = 2; k <= n; ++k) w = w * gamma;
+    W.R = R;
+    W.w = term ? 0.0f : w;
+  }
+  return W;
+}
+
+// NS: the n-step instantiation, in kernels launched only at nstep >= 2.  NS =
+// false is the single-step draw, the code it was before n-step returns.
+template <bool NS>
 __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr,
                             int64_t* cand, int* bad_any) {
   const int t = threadIdx.x;
@@ -112,6 +177,9 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
   const int64_t lvalid = meta->valid;                       // per lane
   const int64_t valid = laned ? lanes * lvalid : lvalid;
   const int64_t forbid = meta->head - 1;   // -1 when head == 0: nothing forbidden
+  // n-step ring: replay_forbidden on the lane-local x
+  const int ns = NS ? meta->nstep : 1;
+  const int llen = NS ? (int)meta->lane_len : 0, head = (int)forbid + 1;
   // draw for sorted position `pos` in redraw round `round`
   auto draw_at = [&](int round, int pos) -> int64_t {
     uint64_t r = splitmix64(seed ^ splitmix64(ctr * 0x100000001B3ull + (uint64_t)pos * 0x9E37ull +
@@ -141,7 +209,12 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
           eqlo += (o == v) & (k < t);
         }
         r = less + eqlo;
-        const bool fbd = laned ? (forbid >= 0 && v % (uint32_t)lvalid == fb) : v == fb;
+        bool fbd;
+        if (NS)
+          fbd = replay_forbidden((int)(laned ? v % (uint32_t)lvalid : v), head, (int)lvalid, llen,
+                                 ns);
+        else
+          fbd = laned ? (forbid >= 0 && v % (uint32_t)lvalid == fb) : v == fb;
         const bool bad = t < B && (fbd || eqlo > 0);
         if (__ballot(bad) == 0) { done = true; break; }
         if (round < kDrawRounds && bad) v = (uint32_t)draw_at(round, r);
@@ -181,8 +254,14 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
     __syncthreads();
     bool bad = false;
     if (t < B) {
-      const bool fbd = laned ? (forbid >= 0 && (uint32_t)cand[t] % (uint32_t)lvalid == (uint32_t)forbid)
-                             : cand[t] == forbid;
+      bool fbd;
+      if (!NS)
+        fbd = laned ? (forbid >= 0 && (uint32_t)cand[t] % (uint32_t)lvalid == (uint32_t)forbid)
+                    : cand[t] == forbid;
+      else
+        fbd = replay_forbidden(
+            (int)(laned ? (uint32_t)cand[t] % (uint32_t)lvalid : (uint32_t)cand[t]), head,
+            (int)lvalid, llen, ns);
       bad = fbd || (t > 0 && cand[t] == cand[t - 1]);
     }
     if (bad) *bad_any = 1;
@@ -207,13 +286,14 @@ __device__ __forceinline__ void log_draw(int32_t* log, int64_t cap, uint64_t ctr
   if (log && t < B) log[(int64_t)(ctr % (uint64_t)cap) * B + t] = v;
 }
 
+template <bool NS>
 __global__ __launch_bounds__(1024) void sample_kernel(ReplayMeta* meta, int B, uint64_t seed,
                                                       int32_t* idx_out, int32_t* log,
                                                       int64_t log_cap) {
   __shared__ int64_t cand[1024];
   __shared__ int bad_any;
   const uint64_t ctr = meta->counter;
-  draw_sorted(meta, B, seed, ctr, cand, &bad_any);
+  draw_sorted<NS>(meta, B, seed, ctr, cand, &bad_any);
   const int t = threadIdx.x;
   if (t < B) idx_out[t] = (int32_t)cand[t];
   log_draw(log, log_cap, ctr, B, t, (int32_t)cand[t < B ? t : 0]);
@@ -224,17 +304,29 @@ __global__ __launch_bounds__(1024) void sample_kernel(ReplayMeta* meta, int B, u
 // idx, z = 1 -> next_state from next_idx (wrap N-1 -> 0, replay.py:160-166;
 // on a laned ring the lane's last slot wraps to the lane's first);
 // the z = 1 blocks with blockIdx.x == 0 also write action one-hot, reward and
-// non_terminal of next_idx (replay.py:172-183).
+// non_terminal of next_idx (replay.py:172-183).  On an n-step ring
+// (replay_window): next_state from s_m, the action of s_1, reward = R,
+// non_terminal = w.
+template <bool NS>
 __device__ __forceinline__ void gather_body(
     const uint8_t* __restrict__ st, const uint8_t* __restrict__ act,
     const int16_t* __restrict__ rew, const uint8_t* __restrict__ nt, ReplayMeta* meta, int64_t i,
     int S, float* __restrict__ sQ, float* __restrict__ sP, float* __restrict__ action,
     float* __restrict__ reward, float* __restrict__ nonterm, int bx, int b, int z) {
-  // the next slot within the lane (ReplayMeta; unlaned: lane_len == capacity)
-  const int64_t L = meta->lane_len;
-  int64_t nxt = (i + 1 == L) ? 0 : i + 1;
-  if (meta->lanes > 1 && (uint32_t)(i + 1) % (uint32_t)L == 0) nxt = i + 1 - L;
-  const int64_t slot = z ? nxt : i;
+  ReplayWindow W{1, 0.f, 0.f, 0u, 0u};
+  int64_t nxt, slot;
+  if (NS) {
+    // s' = S[s_m] and the scalars of the n-step window
+    W = replay_window(rew, nt, meta, i, z == 1, z == 1 && bx == 0 && threadIdx.x == 0);
+    nxt = W.s1;
+    slot = z ? (int64_t)W.sm : i;
+  } else {
+    // the next slot within the lane (ReplayMeta; unlaned: lane_len == capacity)
+    const int64_t L = meta->lane_len;
+    nxt = (i + 1 == L) ? 0 : i + 1;
+    if (meta->lanes > 1 && (uint32_t)(i + 1) % (uint32_t)L == 0) nxt = i + 1 - L;
+    slot = z ? nxt : i;
+  }
   const int SS = S * S;
   const int p4 = bx * 256 + threadIdx.x;             // group of 4 pixels
   if (p4 * 4 < SS) {
@@ -254,19 +346,20 @@ __device__ __forceinline__ void gather_body(
     if (a >= kActions) meta->err = 1;
     action[b * 4 + threadIdx.x] = (threadIdx.x == a) ? 1.f : 0.f;
     if (threadIdx.x == 0) {
-      reward[b] = (float)rew[nxt];
-      nonterm[b] = nt[nxt] ? 1.f : 0.f;
+      reward[b] = NS ? W.R : (float)rew[nxt];
+      nonterm[b] = NS ? W.w : (nt[nxt] ? 1.f : 0.f);
     }
   }
 }
 
 // grid (ceil(S*S/4/256), B, 2), indices from idx (host draw or sample_kernel)
+template <bool NS>
 __global__ __launch_bounds__(256) void gather_kernel(
     const uint8_t* __restrict__ st, const uint8_t* __restrict__ act,
     const int16_t* __restrict__ rew, const uint8_t* __restrict__ nt, ReplayMeta* meta,
     const int32_t* __restrict__ idx, int S, float* __restrict__ sQ, float* __restrict__ sP,
     float* __restrict__ action, float* __restrict__ reward, float* __restrict__ nonterm) {
-  gather_body(st, act, rew, nt, meta, idx[blockIdx.y], S, sQ, sP, action, reward, nonterm,
+  gather_body<NS>(st, act, rew, nt, meta, idx[blockIdx.y], S, sQ, sP, action, reward, nonterm,
               blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
@@ -274,6 +367,7 @@ __global__ __launch_bounds__(256) void gather_kernel(
 // draws the same sorted index set (draw_sorted) and gathers its own sample.
 // The device counter is NOT advanced here (every workgroup must read the
 // same value); the step's apply bookkeeping advances it.
+template <bool NS>
 __global__ __launch_bounds__(256) void sample_gather_kernel(
     const uint8_t* __restrict__ st, const uint8_t* __restrict__ act,
     const int16_t* __restrict__ rew, const uint8_t* __restrict__ nt, ReplayMeta* meta, int B,
@@ -283,19 +377,20 @@ __global__ __launch_bounds__(256) void sample_gather_kernel(
   __shared__ int64_t cand[256];
   __shared__ int bad_any;
   const uint64_t ctr = meta->counter;
-  draw_sorted(meta, B, seed, ctr, cand, &bad_any);
+  draw_sorted<NS>(meta, B, seed, ctr, cand, &bad_any);
   if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < B) {
     idx_out[threadIdx.x] = (int32_t)cand[threadIdx.x];
     log_draw(log, log_cap, ctr, B, threadIdx.x, (int32_t)cand[threadIdx.x]);
   }
-  gather_body(st, act, rew, nt, meta, cand[blockIdx.y], S, sQ, sP, action, reward, nonterm,
+  gather_body<NS>(st, act, rew, nt, meta, cand[blockIdx.y], S, sQ, sP, action, reward, nonterm,
               blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 hipError_t launch_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s) {
   int threads = 64;                 // one wave for B <= 64: cheap barriers
   while (threads < nb.B) threads <<= 1;
-  ddq_launch(sample_kernel, dim3(1), dim3(threads), 0, s, meta, nb.B, seed, nb.idx,
+  auto kern = nb.nstep > 1 ? sample_kernel<true> : sample_kernel<false>;
+  ddq_launch(kern, dim3(1), dim3(threads), 0, s, meta, nb.B, seed, nb.idx,
                      nb.idx_log, nb.log_cap);
   return hipGetLastError();
 }
@@ -305,7 +400,8 @@ hipError_t launch_sample_gather(const NetBuffers& nb, const uint8_t* st, const u
                                 uint64_t seed, hipStream_t s) {
   const int SS = nb.S * nb.S;
   dim3 grid((SS / 4 + 255) / 256, nb.B, 2);
-  ddq_launch(sample_gather_kernel, grid, dim3(256), 0, s, st, act, rew, nt, meta, nb.B,
+  auto kern = nb.nstep > 1 ? sample_gather_kernel<true> : sample_gather_kernel<false>;
+  ddq_launch(kern, grid, dim3(256), 0, s, st, act, rew, nt, meta, nb.B,
                      seed, nb.idx, nb.S, nb.state, nb.next_state, nb.action, nb.reward,
                      nb.nonterm, nb.idx_log, nb.log_cap);
   return hipGetLastError();
@@ -316,7 +412,8 @@ hipError_t launch_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t*
                          hipStream_t s) {
   const int SS = nb.S * nb.S;
   dim3 grid((SS / 4 + 255) / 256, nb.B, 2);
-  ddq_launch(gather_kernel, grid, dim3(256), 0, s, st, act, rew, nt, meta, nb.idx, nb.S,
+  auto kern = nb.nstep > 1 ? gather_kernel<true> : gather_kernel<false>;
+  ddq_launch(kern, grid, dim3(256), 0, s, st, act, rew, nt, meta, nb.idx, nb.S,
                      nb.state, nb.next_state, nb.action, nb.reward, nb.nonterm);
   return hipGetLastError();
 }
@@ -331,17 +428,20 @@ hipError_t launch_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t*
 // n-subset of [0,valid) \ {head-1} -- the distribution of the reference's
 // whole-list redraw.  The bitmap is then compacted in index order, which is
 // the sort of replay.py:159 for free.
+template <bool NS>
 __global__ __launch_bounds__(256) void claim_kernel(ReplayMeta* meta, int n, uint64_t seed,
                                                    uint64_t ctr, uint32_t* __restrict__ bm) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n) return;
   const int64_t valid = meta->valid, forbid = meta->head - 1;
+  const int ns = NS ? meta->nstep : 1;      // replay_forbidden (plain ring)
+  const int cap = NS ? (int)meta->capacity : 0;
   for (int round = 0; round < 4096; ++round) {
     const uint64_t r = splitmix64(seed ^ splitmix64(ctr * 0x100000001B3ull +
                                                     (uint64_t)t * 0x9E3779B1ull +
                                                     ((uint64_t)round << 44)));
     const int64_t x = (int64_t)__umul64hi(r, (uint64_t)valid);
-    if (x == forbid) continue;
+    if (NS ? replay_forbidden((int)x, (int)forbid + 1, (int)valid, cap, ns) : x == forbid) continue;
     const uint32_t bit = 1u << (x & 31);
     if (!(atomicOr(&bm[x >> 5], bit) & bit)) return;
   }
@@ -439,6 +539,7 @@ __global__ __launch_bounds__(256) void bm_emit_kernel(const uint32_t* __restrict
 // only the last sorted index can, replay.py:160-166) plus one-hot action,
 // reward, non_terminal of idx+1.
 constexpr int kGatherWpt = 2;
+template <bool NS>
 __global__ __launch_bounds__(256) void gather_nchw_kernel(
     const uint8_t* __restrict__ st, const uint8_t* __restrict__ act,
     const int16_t* __restrict__ rew, const uint8_t* __restrict__ nt, ReplayMeta* meta,
@@ -451,7 +552,8 @@ __global__ __launch_bounds__(256) void gather_nchw_kernel(
   uint32_t b, part;
   cpr.divmod(blockIdx.x, b, part);
   const int64_t i = idx[b];
-  const int64_t slot = z ? ((i + 1 == N) ? 0 : i + 1) : i;
+  const int64_t slot = !z ? i : NS ? (int64_t)replay_window(rew, nt, meta, i, true, false).sm
+                                   : ((i + 1 == N) ? 0 : i + 1);
   const uint32_t* src = reinterpret_cast<const uint32_t*>(st) + (uint64_t)slot * wps;
   fv4* dst = reinterpret_cast<fv4*>(z ? s1 : s0) + (uint64_t)b * wps;
   uint32_t v[kGatherWpt];
@@ -473,24 +575,27 @@ __global__ __launch_bounds__(256) void gather_nchw_kernel(
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;   // first blocks: per-row scalars
     if ((int)r < n) {
       const int64_t j = idx[r];
-      const int64_t nxt = (j + 1 == N) ? 0 : j + 1;
+      ReplayWindow W{1, 0.f, 0.f, 0u, 0u};
+      if (NS) W = replay_window(rew, nt, meta, j, true, true);
+      const int64_t nxt = NS ? (int64_t)W.s1 : ((j + 1 == N) ? 0 : j + 1);
       const int a = act[nxt];
       if (a >= kActions) meta->err = 1;
 #pragma unroll
       for (int k = 0; k < 4; ++k) action[(size_t)r * 4 + k] = (k == a) ? 1.f : 0.f;
-      reward[r] = (float)rew[nxt];
-      nonterm[r] = nt[nxt] ? 1.f : 0.f;
+      reward[r] = NS ? W.R : (float)rew[nxt];
+      nonterm[r] = NS ? W.w : (nt[nxt] ? 1.f : 0.f);
     }
   }
 }
 
 hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t seed,
                                uint64_t ctr, uint32_t* bm, int32_t* blk, int32_t* idx,
-                               hipStream_t s) {
+                               hipStream_t s, int nstep) {
   const int64_t nwords = (valid + 31) / 32;
   const int nblk = (int)((nwords + 1023) / 1024);
   CHECK_LAUNCH(hipMemsetAsync(bm, 0, (size_t)nblk * 1024 * 4, s));
-  ddq_launch(claim_kernel, dim3((n + 255) / 256), dim3(256), 0, s, meta, n, seed, ctr, bm);
+  auto kern = nstep > 1 ? claim_kernel<true> : claim_kernel<false>;
+  ddq_launch(kern, dim3((n + 255) / 256), dim3(256), 0, s, meta, n, seed, ctr, bm);
   ddq_launch(bm_count_kernel, dim3(nblk), dim3(256), 0, s, bm, nwords, blk);
   ddq_launch(bm_scan_kernel, dim3(1), dim3(256), 0, s, blk, nblk);
   ddq_launch(bm_emit_kernel, dim3(nblk), dim3(256), 0, s, bm, nwords, blk, idx, n);
@@ -500,11 +605,12 @@ hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t 
 hipError_t launch_gather_nchw(const uint8_t* st, const uint8_t* act, const int16_t* rew,
                               const uint8_t* nt, ReplayMeta* meta, const int32_t* idx, int n,
                               int S, float* s0, float* s1, float* action, float* reward,
-                              float* nonterm, hipStream_t s) {
+                              float* nonterm, hipStream_t s, int nstep) {
   const uint32_t wps = (uint32_t)(S * S);          // 4-byte words per slot
   const uint32_t per = 256u * kGatherWpt;
   const uint32_t cpr = (wps + per - 1) / per;       // n * cpr < 2^31 (n <= 2^31 / S^2 checked)
-  ddq_launch(gather_nchw_kernel, dim3((uint32_t)n * cpr, 2), dim3(256), 0, s, st, act, rew, nt,
+  auto kern = nstep > 1 ? gather_nchw_kernel<true> : gather_nchw_kernel<false>;
+  ddq_launch(kern, dim3((uint32_t)n * cpr, 2), dim3(256), 0, s, st, act, rew, nt,
              meta, idx, n, wps, FastDiv(cpr), s0, s1, action, reward, nonterm);
   return hipGetLastError();
 }
@@ -706,11 +812,12 @@ struct HeadArgs {
   const float* qn;
 };
 
+template <bool NS>
 __device__ __forceinline__ void head_draw(const HeadArgs& H) {
   __shared__ int64_t cand[256];
   __shared__ int bad_any;
   const uint64_t ctr = H.dmeta->counter + 1;     // the advance this launch makes, below
-  draw_sorted(H.dmeta, H.B, H.dseed, ctr, cand, &bad_any);
+  draw_sorted<NS>(H.dmeta, H.B, H.dseed, ctr, cand, &bad_any);
   const int t = threadIdx.x;
   if (t < H.B) {
     H.didx[t] = (int32_t)cand[t];
@@ -723,6 +830,7 @@ __device__ __forceinline__ void head_draw(const HeadArgs& H) {
 // K1's extra workgroup (small.h): the fused apply's latch, then the draw
 // counter's advance or the next step's draw (launch_head's, for S = 16)
 namespace sm16 {
+template <bool NS>
 __device__ void book_block(const BookArgs& k) {
   if (k.latch && threadIdx.x == 0) {
     k.latch[2] = (k.latch[0] == 0);
@@ -732,7 +840,7 @@ __device__ void book_block(const BookArgs& k) {
     __shared__ int64_t cand[256];
     __shared__ int bad_any;
     const uint64_t ctr = k.dmeta->counter + 1;
-    draw_sorted(k.dmeta, k.B, k.dseed, ctr, cand, &bad_any);
+    draw_sorted<NS>(k.dmeta, k.B, k.dseed, ctr, cand, &bad_any);
     const int t = threadIdx.x;
     if (t < k.B) {
       k.didx[t] = (int32_t)cand[t];
@@ -750,7 +858,8 @@ __device__ void tower_transpose(const TowerArgs& a, int x, char* smem) {
   else wkst_tap<64, 9>(a.wks[0], a.wks_plane, a.wks3_off, a.wkst3_off, x - 25, smem);
 }
 
-hipError_t launch_tower_fwd16(const TowerArgs& t, hipStream_t s) {
+template <bool NS>
+static hipError_t launch_tower_fwd16_t(const TowerArgs& t, hipStream_t s) {
   const bool book = t.bk.latch || t.bk.bump || t.bk.dmeta;
   const int extra = (book ? 1 : 0) + t.ntr;
   if (t.xchg && 2 * t.B * t.nz <= 256) {
@@ -758,25 +867,30 @@ hipError_t launch_tower_fwd16(const TowerArgs& t, hipStream_t s) {
     // once (<= 256 workgroups of one per CU: their meet cannot wait on an
     // undispatched partner)
     constexpr int K2 = 5, K3 = 4;   // (tap pairs in flight)
-    auto kern = tower_fwd16s_kernel<K2, K3>;
+    auto kern = tower_fwd16s_kernel<K2, K3, NS>;
     static std::atomic<uint64_t> attr{0};
     if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr, kFwdSmemS)) return e;
     ddq_launch(kern, dim3(2 * t.B * t.nz + extra), dim3(kThreads), kFwdSmemS, s, t);
     return hipGetLastError();
   }
   constexpr int K2 = 6, K3 = 5;
-  auto kern = tower_fwd16_kernel<K2, K3>;
+  auto kern = tower_fwd16_kernel<K2, K3, NS>;
   static std::atomic<uint64_t> attr{0};
   if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr, kFwdSmem)) return e;
   ddq_launch(kern, dim3(t.B * t.nz + extra), dim3(kThreads), kFwdSmem, s, t);
   return hipGetLastError();
+}
+
+// ns: the ring's n-step length is >= 2 (the n-step instantiation draws)
+hipError_t launch_tower_fwd16(const TowerArgs& t, hipStream_t s, bool ns) {
+  return ns ? launch_tower_fwd16_t<true>(t, s) : launch_tower_fwd16_t<false>(t, s);
 }
 }  // namespace sm16
 
 // One head block b.  OBJ: the selectable objective's branches are compiled in
 // (fc4_head_obj_kernel); without it this is the reference objective's code and
 // nothing else, so the default launch keeps its instruction stream
-template <bool OBJ>
+template <bool OBJ, bool NS>
 __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) {
   const float* __restrict__ part = H.part;
   const int splits = H.splits, B = H.B;
@@ -803,7 +917,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
   __shared__ float qp[8];
   const int n = threadIdx.x, w = n >> 6;
   if (b == B + 34) {                              // (launched only with dmeta)
-    head_draw(H);
+    head_draw<NS>(H);
     return;
   }
   if (b >= B + 25) {
@@ -935,13 +1049,15 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
   dh4[(size_t)b * kFc4 + n] = dv;
 }
 
+template <bool NS>
 __global__ __launch_bounds__(512) void fc4_head_kernel(const HeadArgs H) {
   __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
-  head_body<false>(H, blockIdx.x, smem);
+  head_body<false, NS>(H, blockIdx.x, smem);
 }
 // a non-default objective (HeadArgs::obj_*): the same body with its branches
 // (defined after the step's other kernels, below launch_act)
-__global__ void fc4_head_obj_kernel(const HeadArgs H);
+template <bool NS>
+__global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H);
 
 // Cross-sample head sums, run by the 8 trailing blocks of the wgrad slab
 // reduce: block hb owns fc4 units j = 64 hb + lane, 4 sample groups.
@@ -1163,7 +1279,9 @@ hipError_t launch_head(const NetBuffers& nb, hipStream_t s, ReplayMeta* bump, co
     H.didx = pf->idx; H.dseed = pf->seed; H.dlog = pf->idx_log; H.dlog_cap = pf->log_cap;
     extra = 1;
   }
-  ddq_launch(H.obj_target || H.obj_loss ? fc4_head_obj_kernel : fc4_head_kernel,
+  const bool obj = H.obj_target || H.obj_loss;
+  ddq_launch(nb.nstep > 1 ? (obj ? fc4_head_obj_kernel<true> : fc4_head_kernel<true>)
+                          : (obj ? fc4_head_obj_kernel<false> : fc4_head_kernel<false>),
              dim3(nb.B + 25 + 9 + extra), dim3(kFc4), 0, s, H);
   return hipGetLastError();
 }
@@ -1353,22 +1471,23 @@ __device__ __forceinline__ void fc4_apply_tile(const ApplyTail& t, const ApplyAr
 
 // Prefetch block g: every block draws the (same) sorted index set of the next
 // step with the already-advanced counter, then gathers its slice.
+template <bool NS>
 __device__ __forceinline__ void prefetch_body(const Prefetch& pf, int g) {
   __shared__ int64_t cand[256];
   __shared__ int bad_any;
   const int bx = g % pf.gx, b = (g / pf.gx) % pf.B, z = g / (pf.gx * pf.B);
   if (pf.predrawn) {   // the head launch drew the set (head_draw): gather only
-    gather_body(pf.st, pf.act, pf.rew, pf.nt, pf.meta, (int64_t)pf.idx[b], pf.S, pf.sQ, pf.sP,
+    gather_body<NS>(pf.st, pf.act, pf.rew, pf.nt, pf.meta, (int64_t)pf.idx[b], pf.S, pf.sQ, pf.sP,
                 pf.action, pf.reward, pf.nonterm, bx, b, z);
     return;
   }
   const uint64_t ctr = pf.meta->counter;
-  draw_sorted(pf.meta, pf.B, pf.seed, ctr, cand, &bad_any);
+  draw_sorted<NS>(pf.meta, pf.B, pf.seed, ctr, cand, &bad_any);
   if (g == 0 && threadIdx.x < pf.B) {
     pf.idx[threadIdx.x] = (int32_t)cand[threadIdx.x];
     log_draw(pf.idx_log, pf.log_cap, ctr, pf.B, threadIdx.x, (int32_t)cand[threadIdx.x]);
   }
-  gather_body(pf.st, pf.act, pf.rew, pf.nt, pf.meta, cand[b], pf.S, pf.sQ, pf.sP, pf.action,
+  gather_body<NS>(pf.st, pf.act, pf.rew, pf.nt, pf.meta, cand[b], pf.S, pf.sQ, pf.sP, pf.action,
               pf.reward, pf.nonterm, bx, b, z);
 }
 
@@ -1457,6 +1576,7 @@ __device__ __forceinline__ void wred_block(const float* __restrict__ part, float
 // block 0 also latches the apply bookkeeping.  Fused steps (fat.rest) update
 // every parameter here, where its gradient becomes final -- no separate apply
 // launch.
+template <bool NS>
 __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
     const float* __restrict__ part, float* __restrict__ grad, WredDims d0, WredDims d1,
     WredDims d2, int nub, int64_t* iter, int32_t* opt_init, int book_period,
@@ -1470,7 +1590,7 @@ __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
   // (the longest HBM streams start before the slab units: the other order
   // measured 16.6 -> 22.6 us), then the slab units
   if (bid < pf.ng) {
-    prefetch_body(pf, bid);
+    prefetch_body<NS>(pf, bid);
     return;
   }
   bid -= pf.ng;
@@ -1505,9 +1625,10 @@ __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
 // serial latency-bound launch at the head of the next step.  The counter it
 // draws with was advanced by this step's bookkeeping (the reduce kernel), so
 // the draws are the ones sequential steps make.
+template <bool NS>
 __global__ __launch_bounds__(256) void apply_kernel(ApplyTail t, ApplyArgs a, Prefetch pf) {
   if ((int)blockIdx.x < pf.ng) {
-    prefetch_body(pf, blockIdx.x);
+    prefetch_body<NS>(pf, blockIdx.x);
     return;
   }
   // (two float4 per thread with every load first measured 12.0 us against 11.3)
@@ -1565,13 +1686,14 @@ struct RefreshOut {
   int mode;   // 0 off; 1 sync = the latched flag; 2 / 3 sync decided by the host: no / yes
 };
 
+template <bool NS>
 __global__ __launch_bounds__(256) void apply_shard_kernel(
     float* __restrict__ theta, const float* __restrict__ gsl, float* __restrict__ opt,
     int32_t* __restrict__ opt_init, int64_t off, int64_t len, int64_t slice, int W,
     ApplyArgs a, int first_host, int64_t* iter, Prefetch pf, float* __restrict__ mirror,
     RefreshOut ro, int own_w, const float* __restrict__ own_g) {
   if ((int)blockIdx.x < pf.ng) {
-    prefetch_body(pf, blockIdx.x);
+    prefetch_body<NS>(pf, blockIdx.x);
     return;
   }
   const int bid = (int)blockIdx.x - pf.ng;
@@ -1679,8 +1801,9 @@ hipError_t launch_apply_shard(const NetBuffers& nb, int rule, float lr, float de
   const RefreshOut ro{nb.theta[1], nb.wks[0], nb.wks[1], nb.L.wks_total,
                       refresh_own < 0 ? 1 : refresh_own == 0 ? 0 : refresh_own == 1 ? 2 : 3};
   const int64_t blocks = (len / 4 + 255) / 256;
+  auto kern = nb.nstep > 1 ? apply_shard_kernel<true> : apply_shard_kernel<false>;
   if (blocks + pf.ng > 0)
-    ddq_launch(apply_shard_kernel, dim3((uint32_t)(blocks + pf.ng)), dim3(256), 0, s,
+    ddq_launch(kern, dim3((uint32_t)(blocks + pf.ng)), dim3(256), 0, s,
                        theta ? theta : nb.theta[0], gsl, nb.opt, nb.opt_init, off, len, slice, W,
                        a, first, nb.iter, pf, mirror, ro, own_g ? own_w : -1, own_g);
   return hipGetLastError();
@@ -1736,7 +1859,8 @@ hipError_t launch_apply(const NetBuffers& nb, int rule, float lr, float decay, f
   if (nb.fa.on && nb.fa.ext) { a.skip_lo = nb.L.w[3]; a.skip_len = nb.L.wn[3]; }
   const int blocks = (nb.fa.on && !nb.fa.ext) ? 0 : (int)(((a.n - a.skip_len) / 4 + 255) / 256);
   if (blocks + pf.ng == 0) return hipSuccess;
-  ddq_launch(apply_kernel, dim3(blocks + pf.ng), dim3(256), 0, s, apply_tail(nb), a, pf);
+  auto kern = nb.nstep > 1 ? apply_kernel<true> : apply_kernel<false>;
+  ddq_launch(kern, dim3(blocks + pf.ng), dim3(256), 0, s, apply_tail(nb), a, pf);
   return hipGetLastError();
 }
 
@@ -1930,7 +2054,7 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
   const bool tower = !nb.fwd_only && nb.small;
   if (tower) {
     M("tower_fwd");
-    CHECK_LAUNCH(sm16::launch_tower_fwd16(tower_args(nb, nz, nullptr), s));
+    CHECK_LAUNCH(sm16::launch_tower_fwd16(tower_args(nb, nz, nullptr), s, nb.nstep > 1));
   }
   if (!tower && (!nb.fwd_only || nb.fwd_only == 1)) {
     // conv1 (train_val.prototxt:39-78): bf16 matrix cores, fp32-exact
@@ -2027,7 +2151,7 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
     bk.bump = hb;
   }
   M("tower_fwd");
-  CHECK_LAUNCH(sm16::launch_tower_fwd16(tower_args(nb, 2, &bk), s));
+  CHECK_LAUNCH(sm16::launch_tower_fwd16(tower_args(nb, 2, &bk), s, nb.nstep > 1));
   sm16::ChainArgs c{};
   c.B = nb.B;
   c.x[0] = nb.pool3[0]; c.x[1] = nb.pool3[1];
@@ -2109,7 +2233,7 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
                                  : reinterpret_cast<const void*>(sm16::fc4_chain16_obj_kernel<2>),
        512, sm16::kChainSmem, (G == 1 ? 2 : 1) * sm16::kFcBlk * G},
       // K4: a tile's groups meet when it has more than one
-      {"wgrad16", reinterpret_cast<const void*>(sm16::wgrad16_kernel), 256, wgrad16_lds(),
+      {"wgrad16", reinterpret_cast<const void*>(sm16::wgrad16_kernel<false>), 256, wgrad16_lds(),
        (G3 > 1 ? sm16::kT3 * G3 : 0) + (G2 > 1 ? sm16::kT2 * G2 : 0)},
   };
   for (const Launch& l : ls) {
@@ -2201,11 +2325,13 @@ hipError_t launch_small_bwd(const NetBuffers& nb, hipStream_t s,
     const int r3 = (w.ipg3 + sm16::Wg3::NI - 1) / sm16::Wg3::NI;
     (void)r2; (void)r3;   // (two buffers always: the staging's dummy slot follows them)
     const int lds = wgrad16_lds();
-    static std::atomic<uint64_t> attr{0};
-    CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(sm16::wgrad16_kernel), attr,
+    static std::atomic<uint64_t> attr{0}, attr_ns{0};
+    const bool ns = nb.nstep > 1;
+    auto kern = ns ? sm16::wgrad16_kernel<true> : sm16::wgrad16_kernel<false>;
+    CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), ns ? attr_ns : attr,
                                 sm16::kWgSmem));
     M("wgrad_apply");
-    ddq_launch(sm16::wgrad16_kernel,
+    ddq_launch(kern,
                dim3(sm16::kT3 * w.G3 + sm16::kT2 * w.G2 + sm16::kW1Blocks + w.pf.ng + w.nw4 +
                     w.nus),
                dim3(256),
@@ -2331,7 +2457,8 @@ hipError_t launch_backward(const NetBuffers& nb, hipStream_t s, void (*mark)(voi
       pf = *pre;
       pf.predrawn = bump != nullptr && nb.B <= 256;   // launch_head drew it (head_draw)
     }
-    ddq_launch(wgrad_reduce_kernel, dim3(pf.ng + nub + kFc4 / 64 + nfa), dim3(256), 0, s,
+    auto kern = nb.nstep > 1 ? wgrad_reduce_kernel<true> : wgrad_reduce_kernel<false>;
+    ddq_launch(kern, dim3(pf.ng + nub + kFc4 / 64 + nfa), dim3(256), 0, s,
                        nb.wpart, nb.grad, d[0], d[1], d[2], nub, nb.iter,
                        book ? nb.opt_init : nullptr, book_period,
                        book && !nb.fa.on ? bump : nullptr, nb.book_inc, hs, fat, faa, pf,
@@ -2380,9 +2507,10 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
   return hipSuccess;
 }
 
+template <bool NS>
 __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
   __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
-  head_body<true>(H, blockIdx.x, smem);
+  head_body<true, NS>(H, blockIdx.x, smem);
 }
 
 }  // namespace ddq

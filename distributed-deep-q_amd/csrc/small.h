@@ -171,6 +171,7 @@ struct W3Tap {
   }
 };
 
+template <bool NS>
 __device__ void book_block(const BookArgs& k);
 __device__ void tower_transpose(const TowerArgs& a, int x, char* smem);
 
@@ -232,7 +233,7 @@ __device__ __forceinline__ bool step_poisoned(const int32_t* w0, const int32_t* 
 // barrier and MFMA), issues tap t's MFMAs, stores tap t + 2 into the slot tap
 // t - 1 used, and meets the others at one barrier.
 // ---------------------------------------------------------------------------
-template <int K2, int K3>
+template <int K2, int K3, bool NSTEP = false>
 __global__ __launch_bounds__(kThreads) void tower_fwd16_kernel(const TowerArgs a) {
   static_assert(K2 >= 3 && K3 >= 3, "ring: tap t + 2 is stored from registers at tap t");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16_kernel(const TowerArgs a
   const int bid = blockIdx.x;
   if (bid >= a.B * a.nz) {
     if (bid - a.B * a.nz < a.ntr) tower_transpose(a, bid - a.B * a.nz, smem);
-    else book_block(a.bk);
+    else book_block<NSTEP>(a.bk);
     return;
   }
   DDQ_STAMP(0);
@@ -611,7 +612,7 @@ struct WH3Pair {
   }
 };
 
-template <int K2, int K3>
+template <int K2, int K3, bool NSTEP = false>
 __global__ __launch_bounds__(kThreads) void tower_fwd16s_kernel(const TowerArgs a) {
   static_assert(K2 >= 3 && K3 >= 3, "ring: step t + 2 is stored from registers at step t");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -620,7 +621,7 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16s_kernel(const TowerArgs 
   const int bid = blockIdx.x;
   if (bid >= 2 * a.B * a.nz) {
     if (bid - 2 * a.B * a.nz < a.ntr) tower_transpose(a, bid - 2 * a.B * a.nz, smem);
-    else book_block(a.bk);
+    else book_block<NSTEP>(a.bk);
     return;
   }
   DDQ_STAMP(0);

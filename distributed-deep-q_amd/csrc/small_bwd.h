@@ -1794,6 +1794,7 @@ __device__ __forceinline__ void units_apply(const WgArgs& a, bool first, bool sy
 // Block order: conv3's tiles (the longest chains) first, conv2's, then
 // conv1's slab sums and the next step's gather (short, no meeting) -- every
 // meeting workgroup is dispatched before any block that could hold a CU.
+template <bool NS>
 __global__ __launch_bounds__(256) void wgrad16_kernel(const WgArgs a) {
   extern __shared__ __attribute__((aligned(16))) char wsm[];
   int bid = blockIdx.x;
@@ -1819,7 +1820,7 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgArgs a) {
       if (x == 0 && a.G == 1) b5_apply(a, first, sync, ap);
     }
     else if (x < a.nw4 + a.nus) units_apply(a, first, sync, ap);
-    else prefetch_body(a.pf, x - a.nw4 - a.nus);
+    else prefetch_body<NS>(a.pf, x - a.nw4 - a.nus);
     return;
   }
   DDQ_STAMP(40);

@@ -75,6 +75,7 @@ TARGETS = {"max": 0, "double": 1}          # include/ddq_hip.h enum ddq_target
 LOSSES = {"euclidean": 0, "huber": 1}      # include/ddq_hip.h enum ddq_loss
 STEP_NO_GRAD_STORE = 1     # include/ddq_hip.h DDQ_STEP_NO_GRAD_STORE
 FAULT_NONE, FAULT_MEET_TIMEOUT = 0, 1   # include/ddq_hip.h enum ddq_fault
+NSTEP_MAX = 8              # include/ddq_hip.h DDQ_NSTEP_MAX
 
 ABI_VERSION = 6
 EXCHANGES = {"none": 0, "allreduce": 1, "sharded": 2, "server": 3, "async": 4}
@@ -136,6 +137,8 @@ _SIGS = {
     "ddq_eval_read": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "ddq_replay_set_lanes": (ctypes.c_int, [_P, _i32]),
     "ddq_replay_lanes": (ctypes.c_int, [_P, _P, _P]),
+    "ddq_replay_set_nstep": (ctypes.c_int, [_P, _i32]),
+    "ddq_replay_nstep": (ctypes.c_int, [_P, _P]),
     "ddq_actors_create": (ctypes.c_int, [_P, _i32, _P, _P, _P, _u64]),
     "ddq_actors_step_async": (ctypes.c_int, [_P, _i32, _i64]),
     "ddq_actors_read": (ctypes.c_int, [_P, _P, _P, _P]),

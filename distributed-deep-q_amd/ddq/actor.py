@@ -106,7 +106,11 @@ class DeviceActor:
 
     ``net``: a ``DeepQNet`` (or a ``BaristaNet``) whose ctx already holds the
     replay ring; ``init_state``: the (10,10) start board
-    (``SnakeGame.encode_state()``), to which every game resets."""
+    (``SnakeGame.encode_state()``), to which every game resets.
+
+    The actor writes the ring the same at any n-step length
+    (``net.replay_set_nstep``): the ring is its one trajectory, which is what
+    the n-step windows run along, so it needs nothing for them."""
 
     def __init__(self, net, init_state, seed, preprocessor=None):
         self.net = getattr(net, "dqn", net)
@@ -158,7 +162,11 @@ class DeviceActorPool:
     batched Q forward and one environment launch and adds N transitions.
 
     ``init_states``: (N,10,10) start boards, one per game; game i draws from
-    ``ActorRng(game_seed(seed, i))`` and otherwise is ``DeviceActor``'s game."""
+    ``ActorRng(game_seed(seed, i))`` and otherwise is ``DeviceActor``'s game.
+
+    Nothing here depends on the ring's n-step length (``net.replay_set_nstep``):
+    a lane holds one game's trajectory, an n-step window stays inside its lane,
+    and ``act_and_train``'s chains draw against the head the round's move left."""
 
     def __init__(self, net, init_states, seed, preprocessor=None):
         self.net = getattr(net, "dqn", net)

@@ -2,7 +2,7 @@
 with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
-reset_log=False, objective=None)``:
+reset_log=False, objective=None, n_step=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -13,7 +13,10 @@ reset_log=False, objective=None)``:
   baristanet.py:99-103, :125-133);
 * ``objective`` -- None (the reference's max target and Euclidean loss) or a dict
   of ``DeepQNet.set_objective`` arguments, e.g. ``{"target": "double", "loss":
-  "huber", "huber_delta": 1.0}``.
+  "huber", "huber_delta": 1.0}``;
+* ``n_step`` -- None (the dataset's own n-step length, 1 unless it was made with
+  ``ReplayDataset(n_step=)``) or the n of the n-step returns the minibatches are
+  gathered for (``DeepQNet.replay_set_nstep``), set on every dataset added.
 
 The input buffers ``state``, ``action``, ``reward``, ``next_state``,
 ``non_terminal`` have the reference's shapes (baristanet.py:30-34).  They are
@@ -65,7 +68,7 @@ class _Blob:
 
 class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
-                 reset_log=False, device=0, mode="gpu", objective=None):
+                 reset_log=False, device=0, mode="gpu", objective=None, n_step=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
@@ -84,6 +87,7 @@ class BaristaNet:
             self.dqn.set_flat(0, P.init_params_flat(frame))
         self.dqn.sync_target()
         self.dataset = None
+        self.n_step = None if n_step is None else int(n_step)
         self.driver = driver
         # logpath: the reference's per-step loss / norm files (baristanet.py:45-46,
         # netutils.NetLogger), from records of the device-resident monitor; None
@@ -121,6 +125,8 @@ class BaristaNet:
 
     def add_dataset(self, dset):
         dset.attach(self.dqn)
+        if self.n_step is not None:
+            dset.set_n_step(self.n_step)
         self.dataset = dset
 
     # --------------------------------------------------------------- inputs

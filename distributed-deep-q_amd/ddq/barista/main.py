@@ -24,6 +24,10 @@ objective the gradients are computed for (``DeepQNet.set_objective``): the
 Double-DQN target r + gamma P(s', argmax_a Q(s',a)) in place of the max, and the
 Huber loss with band D in place of the Euclidean one.  Both work in either mode.
 
+``--n-step N`` (default 1) gathers the minibatches for N-step returns
+(``DeepQNet.replay_set_nstep``): the discounted sum of up to N rewards and
+gamma^N P(s_{t+N}, .), cut at the first terminal step.  Either mode.
+
 ``--logpath PREFIX`` (off by default) makes ``net.log()`` append the step's loss
 and every blob's gradient / parameter RMS to files under ``PREFIX-<date>``
 (netutils.NetLogger), from one record of the device-resident monitor.
@@ -37,6 +41,7 @@ import socket
 import time
 
 from .. import expgain as eg
+from .._lib import NSTEP_MAX
 from ..replay import ReplayDataset
 from ..snake import SnakeGame, gray_scale
 from . import GRAD_UPDATE, DARWIN_UPDATE, MSG_LENGTH, netutils
@@ -107,7 +112,13 @@ def get_args(argv=None):
                     help="Double-DQN target: P at argmax_a Q(s',a) instead of max_a P")
     ap.add_argument("--huber-delta", dest="huber_delta", type=float, default=None,
                     help="Huber loss with this band instead of the Euclidean loss")
+    ap.add_argument("--n-step", dest="n_step", type=int, default=1,
+                    help="N-step returns: the replay gathers N-step windows (default 1)")
     args = ap.parse_args(argv)
+    if not 1 <= args.n_step <= NSTEP_MAX:
+        ap.error("--n-step must be in [1, %d]" % NSTEP_MAX)
+    if args.n_step >= args.dset_size:
+        ap.error("--n-step must be below --dset-size (%d)" % args.dset_size)
     if args.huber_delta is not None and not args.huber_delta > 0:
         ap.error("--huber-delta must be > 0")
     if args.driver == "None":
@@ -133,7 +144,8 @@ def build_worker(args):
                      logpath=getattr(args, "logpath", None), mode=args.mode,
                      objective=objective_of(args))
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
-                           overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode)
+                           overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode,
+                           n_step=getattr(args, "n_step", 1))
     net.add_dataset(replay)
     game = SnakeGame()
     pre = eg.generate_preprocessor(net.state.shape[2:], gray_scale)

@@ -429,6 +429,21 @@ class DeepQNet:
         self._check(self.lib.ddq_replay_lanes(self.ctx, ctypes.byref(n), ctypes.byref(ll)))
         return int(n.value), int(ll.value)
 
+    def replay_set_nstep(self, n):
+        """n-step returns (ddq_replay_set_nstep): every later draw picks only
+        start slots whose n-slot window stays behind the write head, and the
+        gather hands the head the discounted reward sum as ``reward``, the
+        remaining discount gamma^(n-1) (0 after a terminal) as ``non_terminal``
+        and s_{t+m} as ``next_state``.  n = 1 (the default) is the single-step
+        gather, bit for bit."""
+        self._check(self.lib.ddq_replay_set_nstep(self.ctx, int(n)))
+
+    def replay_nstep(self):
+        """The ring's n-step length."""
+        n = _lib._i32()
+        self._check(self.lib.ddq_replay_nstep(self.ctx, ctypes.byref(n)))
+        return int(n.value)
+
     def replay_import(self, state, action, reward, non_terminal, head, valid):
         st = np.ascontiguousarray(state, np.uint8)
         ac = np.ascontiguousarray(action, np.uint8)

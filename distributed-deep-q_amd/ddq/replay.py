@@ -13,9 +13,16 @@ head, valid -- replay.py:48-68) in GPU memory; ``add_experience`` and
   reward and non_terminal of idx+1; bit-exact against the reference.
 
 When the dataset is attached to a ``BaristaNet`` (``net.add_dataset``) the
-ring moves into that net's GPU context and ``sample_direct`` on the net's own
-minibatch arrays gathers straight into the network's device input (no host
+ring (and its n-step length) moves into that net's GPU context and
+``sample_direct`` on the net's own minibatch arrays gathers straight into the network's device input (no host
 round trip), which is what the reference's zero-copy MEMORY_DATA binding did.
+``n_step`` (default 1, the reference) turns the samples into n-step returns
+(``DeepQNet.replay_set_nstep``, include/ddq_hip.h): ``draw_indices`` keeps the
+reference's whole-list redraw, now "while any drawn index is forbidden" (a
+start slot whose n-slot window would reach the write head), and the gather
+returns the discounted reward sum as ``reward``, gamma^(n-1) or 0 as
+``non_terminal`` and s_{t+m} as ``next_state``.  n is a property of sampling,
+not of the data: the file does not hold it.
 Persistence (replay.py:23-45 reopen, :185-192 persist on ``__del__``):
 ``save()`` / ``close()`` / ``__del__`` write ``filename`` as the reference's
 HDF5 file (``ddq.h5lite``: same datasets, dtypes and head/valid attributes,
@@ -38,9 +45,14 @@ from .net import DeepQNet
 
 
 class ReplayDataset:
+    # the default for an object made without __init__ (tests build one around a
+    # stub ring to check draw_indices against the reference's recorded draws)
+    n_step = 1
+
     def __init__(self, filename, state_shape, dset_size=1000, overwrite=False, batch_size=32,
-                 device=0, net=None, mode="gpu"):
+                 device=0, net=None, mode="gpu", n_step=1):
         self.filename = filename
+        self.n_step = int(n_step)
         self.state_shape = tuple(int(x) for x in state_shape)
         if len(self.state_shape) != 3 or self.state_shape[0] != 4 or \
                 self.state_shape[1] != self.state_shape[2]:
@@ -66,6 +78,13 @@ class ReplayDataset:
             self._net.replay_import(loaded["state"], loaded["action"], loaded["reward"],
                                     loaded["non_terminal"].astype(np.uint8),
                                     int(loaded["head"]), int(loaded["valid"]))
+        if self.n_step != 1:
+            self._net.replay_set_nstep(self.n_step)
+
+    def set_n_step(self, n):
+        """Change the n-step length of the ring (legal on a filled ring)."""
+        self._net.replay_set_nstep(int(n))
+        self.n_step = int(n)
 
     # -- reference attributes (replay.py:63-68) --------------------------------
     @property
@@ -85,6 +104,8 @@ class ReplayDataset:
         head, valid, _ = self._net.replay_info()
         net.replay_create(self.dset_size)
         net.replay_import(st, ac, rw, nt.astype(np.uint8), head, valid)
+        if self.n_step != 1:
+            net.replay_set_nstep(self.n_step)
         if self._own_net:
             self._net.close()
         self._net, self._own_net = net, False
@@ -96,12 +117,32 @@ class ReplayDataset:
 
     def draw_indices(self, sample_size):
         """replay.py:147-159: the reference's index draw, on Python ``random``."""
-        head, valid, _ = self._net.replay_info()
-        if sample_size >= valid:
+        head, valid, cap = self._net.replay_info()
+        n = self.n_step
+        if n == 1:
+            if sample_size >= valid:
+                raise ValueError("Can't draw sample of size %d from replay dataset of size %d"
+                                 % (sample_size, valid))
+            idx = random.sample(range(0, valid), sample_size)
+            while (head - 1) in idx:
+                idx = random.sample(range(0, valid), sample_size)
+            idx.sort()
+            return idx
+        # n-step: the same whole-list redraw, while any drawn index is forbidden
+        # (d = head - 1 - x in [0, n), taken mod the capacity on a full ring)
+        full = valid == cap
+
+        def forbidden(x):
+            d = head - 1 - x
+            if d < 0 and full:
+                d += cap
+            return 0 <= d < n
+
+        if sample_size > sum(not forbidden(x) for x in range(valid)):
             raise ValueError("Can't draw sample of size %d from replay dataset of size %d"
                              % (sample_size, valid))
         idx = random.sample(range(0, valid), sample_size)
-        while (head - 1) in idx:
+        while any(forbidden(x) for x in idx):
             idx = random.sample(range(0, valid), sample_size)
         idx.sort()
         return idx

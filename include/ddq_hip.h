@@ -51,7 +51,8 @@ extern "C" {
                               ddq_actors_step_async, ddq_actors_read), likewise;
                               and the selectable objective (ddq_set_objective,
                               ddq_get_objective; blobs "Qn_out", "Q_out.diff"),
-                              likewise */
+                              likewise; and n-step returns (ddq_replay_set_nstep,
+                              ddq_replay_nstep), likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -238,6 +239,53 @@ int ddq_replay_info(const ddq_ctx* ctx, int64_t* head, int64_t* valid, int64_t* 
  * ddq_actor_create return DDQ_ESTATE. */
 int ddq_replay_set_lanes(ddq_ctx* ctx, int32_t lanes);
 int ddq_replay_lanes(const ddq_ctx* ctx, int32_t* lanes, int64_t* lane_len);
+/* n-step returns.  The ring's n-step length n (1 by default, reset to 1 by
+ * ddq_replay_create) changes which slots a draw may pick and what the gather
+ * assembles; the head, the step modes and the exchanges are the same, because
+ * the head's target gamma * (P_sel * non_terminal) + reward is the n-step
+ * target when the gather hands it the discounted reward sum as reward, the
+ * remaining discount as non_terminal and s_{t+m} as next_state.  At n = 1 every
+ * launch and every bit is what it is without this call.
+ *
+ * Per lane: L = lane_len, v = valid, h = head, x = the lane-local index of a
+ * sample's slot, base = lane * L (a plain ring: base 0, L = capacity).
+ *
+ * Allowed start slots.  For x in [0, v):
+ *     d = h - 1 - x
+ *     if (d < 0 && n >= 2 && v == L) d += L      full ring: the window wraps onto the head
+ *     forbidden(x)  <=>  0 <= d < n
+ * n = 1: x == h - 1, nothing at h == 0 (the reference's rule).  n >= 2: no
+ * window reaches the write head, also across the wrap of a full ring.  Allowed
+ * slots per lane, A: v - 1 at n = 1; L - n at n >= 2, v == L; at n >= 2, v < L:
+ * v - |[max(0, h - n), h - 1] n [0, v)|.  Every draw needs B <= lanes * A
+ * (DDQ_EINVAL otherwise; the large-batch sampler n_batch <= A as well as
+ * n_batch <= valid / 2).
+ *
+ * The window of x.  s_k = base + (x + k) mod L, k = 1..n (s_1 is the next slot).
+ *     m = the smallest k in 1..n with non_terminal[s_k] == 0, else n
+ *     g = 1.0f;  R = (float)reward[s_1]
+ *     for k = 2..m:  g = g * gamma;  R = R + g * (float)reward[s_k]
+ *     w = 0.0f if a terminal was found, else gamma^(n-1), n - 1 repeated
+ *         multiplications from 1.0f
+ * every * and + an fp32 operation rounded on its own (no fused multiply-add),
+ * gamma = ddq_net_desc.gamma.  The minibatch is
+ *     state <- S[base + x]        next_state <- S[s_m]
+ *     action <- one-hot of action[s_1] (>= 4: the sticky error of ddq_replay_status)
+ *     reward[b] <- R              non_terminal[b] <- w
+ * so ddq_read_minibatch's non_terminal is w and its reward is R, blob "P_sa"
+ * carries the factor w, and "target_Q_sa" = gamma * (P_sel * w) + R.  A start
+ * slot that is itself a terminal slot stays drawable, as in the reference.
+ *
+ * ddq_replay_set_nstep synchronises and drops captured graphs; it is legal on
+ * a filled ring.  DDQ_ESTATE: no ring, or the async exchange has begun.
+ * DDQ_EINVAL: n < 1, n > DDQ_NSTEP_MAX or n >= lane_len.  ddq_replay_set_lanes
+ * refuses (DDQ_EINVAL) a lane count that would make lane_len <= n.
+ * ddq_replay_sample at n >= 2 refuses a forbidden index (DDQ_EINVAL); at n = 1
+ * it accepts what it always did.  n is a property of sampling, not of the data:
+ * it is not stored with the ring. */
+#define DDQ_NSTEP_MAX 8
+int ddq_replay_set_nstep(ddq_ctx* ctx, int32_t n);
+int ddq_replay_nstep(const ddq_ctx* ctx, int32_t* n);
 /* Bulk load / store of the ring (the HDF5 datasets of replay.py:48-61,
  * persisted by __del__ :185-192). */
 int ddq_replay_import(ddq_ctx* ctx, const uint8_t* state, const uint8_t* action,
