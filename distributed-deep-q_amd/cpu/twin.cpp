@@ -100,6 +100,15 @@ struct ddq_ctx {
   int32_t lanes = 1;
   int64_t lane_len = 0;
   int32_t nstep = 1;               // n-step returns (ddq_replay_set_nstep)
+  // prioritized replay (ddq_replay_set_priority): a flat leaf array, the draw is
+  // a linear prefix scan; isw: the bound minibatch's weights
+  bool prio_on = false;
+  ddq_priority_cfg prio_cfg{0, 0.f, 0.f, 0.f};
+  std::vector<uint32_t> prio_q;
+  uint32_t prio_pmax = 65536u;
+  uint64_t prio_ctr = 0;           // prioritized draws so far (the draw counter)
+  std::vector<float> isw;
+  bool idx_bound = false;
   int64_t steps = 0;
   // Snake actor (ddq_actor_*): 4-board history (oldest first), the start board,
   // the zoom maps and the RNG stream position
@@ -385,8 +394,16 @@ int forward_backward(ddq_ctx* c) {
     } else {
       loss += diff * diff;
     }
+    if (c->prio_on) {   // importance-sampling weight on dQ and on the loss term
+      const double w = c->isw[b], le = huber ? (std::fabs(diff) <= delta
+                                                    ? diff * diff
+                                                    : delta * (2.0 * std::fabs(diff) - delta))
+                                             : diff * diff;
+      loss += (w - 1.0) * le;          // (w == 1: adds 0, the unweighted sum)
+    }
+    const double wt = c->prio_on ? (double)c->isw[b] : 1.0;
     for (int a = 0; a < kA; ++a) {
-      dq[(size_t)b * kA + a] = c->action[(size_t)b * kA + a] * dc / B;
+      dq[(size_t)b * kA + a] = c->action[(size_t)b * kA + a] * dc / B * wt;
       c->dq_out[(size_t)b * kA + a] = (float)dq[(size_t)b * kA + a];
     }
   }
@@ -495,6 +512,88 @@ int64_t allowed_slots(const ddq_ctx* c) {
   const int64_t lo = std::max<int64_t>(0, c->head - c->nstep);
   const int64_t hi = std::min(c->head - 1, c->valid - 1);
   return c->valid - std::max<int64_t>(0, hi - lo + 1);
+}
+
+// ---- prioritized replay (include/ddq_hip.h): the contract on a flat array ----
+constexpr uint32_t kPrioOne = 65536u, kPrioMax = 1u << 24;
+
+uint64_t prio_mix64(uint64_t x) {   // splitmix64
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+bool prio_forbidden(int64_t x, int64_t head, int64_t valid, int64_t L, int n) {
+  int64_t d = head - 1 - x;
+  if (d < 0 && n >= 2 && valid == L) d += L;
+  return d >= 0 && d < n;
+}
+
+// every filled, allowed slot <- pmax = 1.0, the rest 0
+void prio_rebuild(ddq_ctx* c) {
+  if (!c->prio_on) return;
+  c->prio_pmax = kPrioOne;
+  c->prio_q.assign((size_t)c->capacity, 0u);
+  for (int64_t i = 0; i < c->capacity; ++i) {
+    const int64_t x = i % c->lane_len;
+    if (x < c->valid && !prio_forbidden(x, c->head, c->valid, c->lane_len, c->nstep))
+      c->prio_q[i] = c->prio_pmax;
+  }
+  c->idx_bound = false;
+}
+
+// the writer rule, after an add at lane-local slot h of the lane at `base`;
+// c->head / c->valid are already the values after the add
+void prio_on_add(ddq_ctx* c, int64_t base, int64_t h) {
+  if (!c->prio_on) return;
+  const int64_t L = c->lane_len;
+  c->prio_q[base + h] = prio_forbidden(h, c->head, c->valid, L, c->nstep) ? 0u : c->prio_pmax;
+  int64_t x = h - c->nstep;
+  if (x < 0 && c->valid == L) x += L;
+  if (x >= 0 && x != h && c->prio_q[base + x] == 0u) c->prio_q[base + x] = c->prio_pmax;
+}
+
+void prio_draw(ddq_ctx* c, uint64_t seed, uint64_t ctr) {
+  const int B = c->B;
+  unsigned long long T = 0;
+  for (uint32_t v : c->prio_q) T += v;
+  std::vector<uint32_t> qs(B, 1u);
+  int64_t i = 0;                       // u_j is nondecreasing in j: one pass over the leaves
+  unsigned long long C = 0;            // exclusive prefix sum at slot i
+  uint32_t qmin = 0xFFFFFFFFu;
+  for (int j = 0; j < B; ++j) {
+    const unsigned long long lo = T * (unsigned long long)j / B, hi = T * (unsigned long long)(j + 1) / B;
+    const uint64_t r = prio_mix64(seed ^ prio_mix64(ctr * 0x100000001B3ull + (uint64_t)j * 0x9E37ull));
+    const unsigned long long u = lo + (unsigned long long)(((unsigned __int128)r * (hi - lo)) >> 64);
+    while (i + 1 < c->capacity && C + c->prio_q[i] <= u) C += c->prio_q[i++];
+    c->idx[j] = (int32_t)i;
+    qs[j] = c->prio_q[i] ? c->prio_q[i] : 1u;
+    qmin = std::min(qmin, qs[j]);
+  }
+  for (int j = 0; j < B; ++j) c->isw[j] = powf((float)qmin / (float)qs[j], c->prio_cfg.beta);
+}
+
+uint32_t prio_leaf_of(float d, float eps, float alpha) {
+  const float p = powf(fabsf(d) + eps, alpha);
+  if (!std::isfinite(p)) return kPrioMax;
+  const float v = rintf(p * 65536.0f);
+  if (!(v >= 1.0f)) return 1u;
+  if (v >= (float)kPrioMax) return kPrioMax;
+  return (uint32_t)v;
+}
+
+void prio_commit(ddq_ctx* c) {
+  for (int b = 0; b < c->B; ++b) {     // ascending b: the highest b of a repeated slot wins
+    const int64_t i = c->idx[b];
+    if (i < 0 || i >= c->capacity || c->prio_q[i] == 0u) continue;
+    bool later = false;
+    for (int o = b + 1; o < c->B && !later; ++o) later = c->idx[o] == i;
+    if (later) continue;
+    const uint32_t v = prio_leaf_of(c->q_sa[b] - c->target[b], c->prio_cfg.eps, c->prio_cfg.alpha);
+    c->prio_q[i] = v;
+    c->prio_pmax = std::max(c->prio_pmax, v);
+  }
 }
 
 void gather(ddq_ctx* c) {
@@ -692,6 +791,8 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->lanes = 1;
   c->lane_len = capacity;
   c->nstep = 1;
+  c->prio_on = false;
+  c->prio_cfg = ddq_priority_cfg{0, 0.f, 0.f, 0.f};
   return DDQ_OK;
 }
 
@@ -712,6 +813,7 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   c->head = 0;
   c->p_games.clear();                // a pool or an actor belongs to the lanes it was
   c->actor = false;                  // created on
+  prio_rebuild(c);
   return DDQ_OK;
 }
 
@@ -730,6 +832,84 @@ int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
     return fail(c, DDQ_EINVAL, "n-step length must be in [1, %d] and below lane_len %lld (got %d)",
                 DDQ_NSTEP_MAX, (long long)c->lane_len, n);
   c->nstep = n;
+  prio_rebuild(c);
+  return DDQ_OK;
+}
+
+static bool unit_interval(float x) { return std::isfinite(x) && x >= 0.f && x <= 1.f; }
+
+int ddq_replay_set_priority(ddq_ctx* c, const ddq_priority_cfg* p) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!p) return fail(c, DDQ_EINVAL, "null priority cfg");
+  if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!p->enabled) {
+    c->prio_on = false;
+    c->prio_cfg = ddq_priority_cfg{0, 0.f, 0.f, 0.f};
+    c->prio_q.clear();
+    return DDQ_OK;
+  }
+  if (!unit_interval(p->alpha)) return fail(c, DDQ_EINVAL, "alpha must be in [0, 1] (got %g)", (double)p->alpha);
+  if (!unit_interval(p->beta)) return fail(c, DDQ_EINVAL, "beta must be in [0, 1] (got %g)", (double)p->beta);
+  if (!(std::isfinite(p->eps) && p->eps > 0.f))
+    return fail(c, DDQ_EINVAL, "eps must be finite and > 0 (got %g)", (double)p->eps);
+  if (c->B > 256)
+    return fail(c, DDQ_EINVAL, "prioritized replay draws B <= 256 in one workgroup (B = %d)", c->B);
+  const bool was = c->prio_on;
+  c->prio_cfg = ddq_priority_cfg{1, p->alpha, p->beta, p->eps};
+  if (was) return DDQ_OK;            // the annealing path: the scalars only
+  c->prio_on = true;
+  c->isw.assign(c->B, 1.0f);
+  prio_rebuild(c);
+  return DDQ_OK;
+}
+
+int ddq_replay_get_priority(const ddq_ctx* c, ddq_priority_cfg* p) {
+  if (!c || !p) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *p = c->prio_cfg;
+  return DDQ_OK;
+}
+
+int ddq_replay_priorities(ddq_ctx* c, uint32_t* leaves, int64_t n, uint64_t* total, uint32_t* pmax) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->prio_on) return fail(c, DDQ_ESTATE, "prioritized replay is off");
+  if (leaves && n != c->capacity)
+    return fail(c, DDQ_EINVAL, "the ring has %lld leaves (got n = %lld)", (long long)c->capacity,
+                (long long)n);
+  if (leaves) std::copy(c->prio_q.begin(), c->prio_q.end(), leaves);
+  if (total) {
+    uint64_t T = 0;
+    for (uint32_t v : c->prio_q) T += v;
+    *total = T;
+  }
+  if (pmax) *pmax = c->prio_pmax;
+  return DDQ_OK;
+}
+
+int ddq_replay_set_priorities(ddq_ctx* c, const int32_t* idx, const uint32_t* q, int32_t n) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->prio_on) return fail(c, DDQ_ESTATE, "prioritized replay is off");
+  if (n < 0 || (n > 0 && (!idx || !q))) return fail(c, DDQ_EINVAL, "bad argument");
+  for (int k = 0; k < n; ++k) {
+    if (idx[k] < 0 || idx[k] >= c->capacity) return fail(c, DDQ_EINVAL, "index %d out of range", idx[k]);
+    if (q[k] > kPrioMax) return fail(c, DDQ_EINVAL, "priority %u above 2^24", q[k]);
+    if ((q[k] == 0) != (c->prio_q[idx[k]] == 0))
+      return fail(c, DDQ_EINVAL, "slot %d: a zero leaf (unfilled or forbidden slot) stays zero and "
+                                 "a nonzero leaf stays nonzero", idx[k]);
+  }
+  for (int k = 0; k < n; ++k) {
+    c->prio_q[idx[k]] = q[k];
+    c->prio_pmax = std::max(c->prio_pmax, q[k]);
+  }
+  return DDQ_OK;
+}
+
+int ddq_replay_update_priorities_async(ddq_ctx* c) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->prio_on) return fail(c, DDQ_ESTATE, "prioritized replay is off");
+  if (!c->idx_bound || (int)c->q_sa.size() != c->B)
+    return fail(c, DDQ_ESTATE, "no device-side index set is bound (the minibatch was not drawn from "
+                               "the ring, or no pass has run on it)");
+  prio_commit(c);
   return DDQ_OK;
 }
 
@@ -754,6 +934,7 @@ int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* st
   if (state) std::copy(state, state + slot, c->r_state.begin() + h * slot);
   c->head = (c->head + 1) % c->capacity;
   c->valid = std::min(c->capacity, c->valid + 1);
+  prio_on_add(c, 0, h);
   return DDQ_OK;
 }
 
@@ -782,6 +963,7 @@ int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
   std::copy(nonterm, nonterm + n, c->r_nonterm.begin());
   c->head = head;
   c->valid = valid;
+  prio_rebuild(c);
   return DDQ_OK;
 }
 
@@ -819,11 +1001,28 @@ int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   }
   std::copy(idx, idx + batch, c->idx.begin());
   gather(c);
+  if (c->prio_on) c->isw.assign(c->B, 1.0f);   // host-given set
+  c->idx_bound = true;
   return DDQ_OK;
 }
 
-int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t) {
-  return cpu_only(c, "ddq_replay_sample_device_async (device index stream)");
+// (the uniform device index stream is the HIP library's; the prioritized draw
+// is defined on integers and restated here)
+int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
+  if (!c || !c->prio_on)
+    return cpu_only(c, "ddq_replay_sample_device_async (device index stream)");
+  if (c->B > c->lanes * allowed_slots(c))
+    return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
+                c->B, (long long)(c->lanes * c->valid));
+  prio_draw(c, seed, c->prio_ctr++);
+  for (int b = 0; b < c->B; ++b) {
+    const int64_t j = (int64_t)c->idx[b] + 1, nxt = j % c->lane_len == 0 ? j - c->lane_len : j;
+    if (c->r_action[nxt] >= kA)
+      return fail(c, DDQ_ERANGE, "stored action index out of range for %d actions", kA);
+  }
+  gather(c);
+  c->idx_bound = true;
+  return DDQ_OK;
 }
 
 int ddq_read_minibatch(ddq_ctx* c, float* state, float* action, float* reward, float* next_state,
@@ -845,6 +1044,8 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
   if (action) std::copy(action, action + c->action.size(), c->action.begin());
   if (reward) std::copy(reward, reward + c->reward.size(), c->reward.begin());
   if (nonterm) std::copy(nonterm, nonterm + c->nonterm.size(), c->nonterm.begin());
+  if (c->prio_on) c->isw.assign(c->B, 1.0f);
+  c->idx_bound = false;
   return DDQ_OK;
 }
 
@@ -935,11 +1136,14 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_out", c->q_out.data(), 4ll * c->B}, {"P_out", c->p_out.data(), 4ll * c->B},
       {"Q_sa", c->q_sa.data(), c->B},         {"P_sa", c->p_sa.data(), c->B},
       {"target_Q_sa", c->target.data(), c->B}, {"loss", &c->loss, 1},
-      {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B}};
+      {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B},
+      {"is_weight", c->isw.data(), c->B}};
   for (auto& e : t)
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
-      if (e.p == c->qn_out.data() && c->obj.target != DDQ_TARGET_DOUBLE)
+      if (!strcmp(name, "is_weight") && !c->prio_on)
+        return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
+      if (!strcmp(name, "Qn_out") && c->obj.target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
       std::copy(e.p, e.p + n, dst);
       return DDQ_OK;
@@ -1347,6 +1551,7 @@ int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
     }
     c->head = (h + 1) % c->lane_len;
     c->valid = std::min(c->lane_len, c->valid + 1);
+    for (int g = 0; g < n; ++g) prio_on_add(c, (int64_t)g * c->lane_len, h);
   }
   return DDQ_OK;
 }

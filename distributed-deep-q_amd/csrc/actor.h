@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kActorThreads) void actor_env_kernel(
     uint64_t thresh, int play, int S, uint8_t* __restrict__ r_state,
     uint8_t* __restrict__ r_action, int16_t* __restrict__ r_reward,
     uint8_t* __restrict__ r_nonterm, ReplayMeta* __restrict__ meta,
-    float* __restrict__ actor_in) {
+    float* __restrict__ actor_in, const PrioTree* __restrict__ prio) {
   __shared__ int8_t bd[5 * kCells];     // 4-frame history (oldest first), then init_board
   __shared__ int8_t nbd[kCells];        // the board after this move
   __shared__ uint8_t lv[4 * kCells];    // gray levels of the next state's four boards
@@ -143,6 +143,10 @@ __global__ __launch_bounds__(kActorThreads) void actor_env_kernel(
       meta->head = h + 1 == cap ? 0 : h + 1;
       const int64_t v = meta->valid;
       meta->valid = v < cap ? v + 1 : cap;
+      // prioritized replay: the writer rule (prio.h) on the slot just written
+      if (prio)
+        prio_on_add(*prio, 0, (int)h, (int)cap, (int)(h + 1 == cap ? 0 : h + 1),
+                    (int)(v < cap ? v + 1 : cap), meta->nstep);
     }
     s_over = over;
     as->draws = k;
@@ -186,7 +190,8 @@ __global__ __launch_bounds__(kActorThreads) void actor_env_kernel(
 hipError_t launch_actor_env(const ActorEnv& e, const float* q, uint64_t thresh, int play,
                             hipStream_t s) {
   ddq_launch(actor_env_kernel, dim3(1), dim3(kActorThreads), 0, s, e.state, e.maps, q, thresh,
-             play, e.S, e.r_state, e.r_action, e.r_reward, e.r_nonterm, e.meta, e.actor_in);
+             play, e.S, e.r_state, e.r_action, e.r_reward, e.r_nonterm, e.meta, e.actor_in,
+             e.prio);
   CHECK_LAUNCH(hipGetLastError());
   return hipSuccess;
 }

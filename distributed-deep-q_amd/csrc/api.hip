@@ -54,6 +54,14 @@ struct ddq_ctx {
   int32_t lanes = 1;               // laned ring (ddq_replay_set_lanes): head / valid per lane
   int64_t lane_len = 0;            // capacity / lanes
   int32_t nstep = 1;               // n-step returns (ddq_replay_set_nstep)
+  // prioritized replay (ddq_replay_set_priority): nb.prio / nb.isw are bound while on
+  bool prio_on = false;
+  ddq_priority_cfg prio_cfg{0, 0.f, 0.f, 0.f};
+  PrioTree* d_prio = nullptr;      // device copy of nb.prio: the ring writers' argument
+  int32_t* pset_idx = nullptr;     // ddq_replay_set_priorities staging (grown on demand)
+  uint32_t* pset_q = nullptr;
+  int32_t pset_cap = 0;
+  bool idx_bound = false;          // nb.idx holds the bound minibatch's slots
   // acting scratch
   uint8_t* act_u8 = nullptr;
   float *act_in = nullptr, *act_p3 = nullptr;
@@ -309,7 +317,8 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* desc) {
     TRY(dalloc(c, &nb.state, (size_t)B * S * S * 4));
     TRY(dalloc(c, &nb.next_state, (size_t)B * S * S * 4));
     TRY(dalloc(c, &nb.action, (size_t)B * 4));
-    TRY(dalloc(c, &nb.reward, (size_t)B));
+    // (B rewards, then the B importance-sampling weights of prioritized replay)
+    TRY(dalloc(c, &nb.reward, (size_t)2 * B));
     TRY(dalloc(c, &nb.nonterm, (size_t)B));
     TRY(dalloc(c, &nb.idx, (size_t)B));
     for (int z = 0; z < 2; ++z) {
@@ -590,10 +599,55 @@ int ddq_sync_target(ddq_ctx* c) {
   return DDQ_OK;
 }
 
+// ---------------- prioritized replay: tree set-up ----------------
+static void prio_release(ddq_ctx* c) {
+  PrioTree& t = c->nb.prio;
+  dfree(c, t.leaf);
+  for (auto& p : t.sum) dfree(c, p);
+  dfree(c, t.st);
+  t = PrioTree{};
+  c->nb.isw = nullptr;
+  c->prio_on = false;
+  c->prio_cfg.enabled = 0;
+}
+
+// every filled, allowed slot <- pmax = 1.0, the rest 0, sums bottom-up
+// (enable, import, fill_tiled, set_nstep, set_lanes); synchronises
+static int prio_rebuild(ddq_ctx* c) {
+  if (!c->prio_on) return DDQ_OK;
+  const uint32_t one = kPrioOne;
+  HIP_TRY(c, hipMemcpyAsync(&c->nb.prio.st->pmax, &one, 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, launch_prio_rebuild(c->nb.prio, c->r_meta, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->idx_bound = false;
+  return DDQ_OK;
+}
+
+// the enable path's device work: the scalars, the writers' copy of the tree,
+// weights of 1 for a minibatch bound before any draw, the first rebuild
+static int prio_enable_fill(ddq_ctx* c, const float abe[3]) {
+  const PrioTree& t = c->nb.prio;
+  HIP_TRY(c, hipMemcpyAsync(t.st, abe, 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_prio, &t, sizeof(t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, launch_fill_ones(c->nb.isw, c->nb.B, c->stream));
+  return prio_rebuild(c);
+}
+
+static int prio_refuse(ddq_ctx* c, const char* what) {
+  if (c && c->prio_on)
+    return fail(c, DDQ_ESTATE, "%s while prioritized replay is on: priorities are kept per ring, "
+                               "not across ranks (ddq_replay_set_priority with enabled = 0 first)",
+                what);
+  return DDQ_OK;
+}
+
 // ---------------- replay ----------------
-static int push_meta(ddq_ctx* c) {
+static int push_meta(ddq_ctx* c, bool prio_add = false, int64_t h = 0) {
   int64_t hv[2] = {c->head, c->valid};
   HIP_TRY(c, hipMemcpyAsync(c->r_meta, hv, sizeof(hv), hipMemcpyHostToDevice, c->stream));
+  // prioritized replay: the writer rule on the slot just added, after the new
+  // head / valid (stream order)
+  if (prio_add) HIP_TRY(c, launch_prio_add(c->nb.prio, c->r_meta, 0, h, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;
 }
@@ -615,6 +669,7 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->lane_len = capacity;
   c->nstep = 1;
   c->nb.nstep = 1;
+  prio_release(c);
   ReplayMeta m{};
   m.capacity = capacity;
   m.lanes = 1;
@@ -644,7 +699,7 @@ int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* st
     HIP_TRY(c, hipMemcpyAsync(c->r_state + h * slot, state, slot, hipMemcpyHostToDevice, c->stream));
   c->head = (c->head + 1) % c->capacity;
   c->valid = std::min(c->capacity, c->valid + 1);
-  return push_meta(c);
+  return push_meta(c, c->prio_on, h);
 }
 
 int ddq_replay_info(const ddq_ctx* c, int64_t* head, int64_t* valid, int64_t* capacity) {
@@ -698,7 +753,8 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   char* m = reinterpret_cast<char*>(c->r_meta);
   HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lanes), &c->lanes, 4, hipMemcpyHostToDevice));
   HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lane_len), &c->lane_len, 8, hipMemcpyHostToDevice));
-  return push_meta(c);
+  TRY(push_meta(c));
+  return prio_rebuild(c);
 }
 
 int ddq_replay_lanes(const ddq_ctx* c, int32_t* lanes, int64_t* lane_len) {
@@ -727,13 +783,145 @@ int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
   c->nb.nstep = n;   // n >= 2: the n-step instantiations of the drawing / gathering kernels
   HIP_TRY(c, scopy(c, reinterpret_cast<char*>(c->r_meta) + offsetof(ReplayMeta, nstep), &c->nstep,
                    4, hipMemcpyHostToDevice));
-  return DDQ_OK;
+  return prio_rebuild(c);
 }
 
 int ddq_replay_nstep(const ddq_ctx* c, int32_t* n) {
   if (!c || !n) return fail(nullptr, DDQ_EINVAL, "null argument");
   if (!c->r_state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
   *n = c->nstep;
+  return DDQ_OK;
+}
+
+// ---------------- prioritized replay: entry points ----------------
+static bool unit_interval(float x) { return std::isfinite(x) && x >= 0.f && x <= 1.f; }
+
+int ddq_replay_set_priority(ddq_ctx* c, const ddq_priority_cfg* p) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!p) return fail(c, DDQ_EINVAL, "null priority cfg");
+  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  TRY(set_dev(c));
+  if (!p->enabled) {
+    if (!c->prio_on) return DDQ_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    invalidate_graph(c);   // captured steps hold the tree, the weights and the extra launches
+    prio_release(c);
+    return DDQ_OK;
+  }
+  if (!unit_interval(p->alpha)) return fail(c, DDQ_EINVAL, "alpha must be in [0, 1] (got %g)", (double)p->alpha);
+  if (!unit_interval(p->beta)) return fail(c, DDQ_EINVAL, "beta must be in [0, 1] (got %g)", (double)p->beta);
+  if (!(std::isfinite(p->eps) && p->eps > 0.f))
+    return fail(c, DDQ_EINVAL, "eps must be finite and > 0 (got %g)", (double)p->eps);
+  if (c->nb.B > 256)
+    return fail(c, DDQ_EINVAL, "prioritized replay draws B <= 256 in one workgroup (B = %d)", c->nb.B);
+  // (the async exchange needs a communicator or a group, so it is named first)
+  if (c->async_on) return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx");
+  if (c->comm || c->local)
+    return fail(c, DDQ_ESTATE, "prioritized replay on a ctx with a communicator or in a group: "
+                               "priorities are kept per ring, not across ranks");
+  const float abe[3] = {p->alpha, p->beta, p->eps};
+  if (c->prio_on) {
+    // the annealing path: three scalars in device memory, stream-ordered; captured
+    // graphs read them live.  No synchronisation, no rebuild, no graph drop.
+    HIP_TRY(c, hipMemcpyAsync(c->nb.prio.st, abe, sizeof(abe), hipMemcpyHostToDevice, c->stream));
+    c->prio_cfg = ddq_priority_cfg{1, p->alpha, p->beta, p->eps};
+    return DDQ_OK;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);
+  PrioTree t{};
+  t.capacity = c->capacity;
+  t.padded[0] = (c->capacity + 63) / 64 * 64;
+  int K = 0;
+  do {
+    ++K;
+    t.padded[K] = (t.padded[K - 1] / 64 + 63) / 64 * 64;
+  } while (t.padded[K - 1] / 64 > 64 && K < kPrioLevels);
+  if (t.padded[K - 1] / 64 > 64) return fail(c, DDQ_EINVAL, "ring too large for the priority tree");
+  t.nlev = K;
+  int rc = dalloc(c, &t.leaf, (size_t)t.padded[0]);
+  for (int k = 1; k <= K && rc == DDQ_OK; ++k) rc = dalloc(c, &t.sum[k - 1], (size_t)t.padded[k]);
+  if (rc == DDQ_OK) rc = dalloc(c, &t.st, 1);
+  // (d_prio and the ddq_replay_set_priorities staging outlive a disable: the next
+  // enable reuses them, ddq_destroy frees them with every other allocation)
+  if (rc == DDQ_OK && !c->d_prio) rc = dalloc(c, &c->d_prio, 1);
+  c->nb.prio = t;
+  c->nb.isw = c->nb.reward + c->nb.B;   // the second half of the reward buffer (mb_view: set 1's)
+  c->prio_on = true;
+  if (rc == DDQ_OK) rc = prio_enable_fill(c, abe);
+  if (rc != DDQ_OK) { prio_release(c); return rc; }   // all or nothing: no half-bound tree
+  c->prio_cfg = ddq_priority_cfg{1, p->alpha, p->beta, p->eps};
+  return DDQ_OK;
+}
+
+int ddq_replay_get_priority(const ddq_ctx* c, ddq_priority_cfg* p) {
+  if (!c || !p) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *p = c->prio_cfg;
+  return DDQ_OK;
+}
+
+int ddq_replay_priorities(ddq_ctx* c, uint32_t* leaves, int64_t n, uint64_t* total, uint32_t* pmax) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->prio_on) return fail(c, DDQ_ESTATE, "prioritized replay is off");
+  if (leaves && n != c->capacity)
+    return fail(c, DDQ_EINVAL, "the ring has %lld leaves (got n = %lld)", (long long)c->capacity,
+                (long long)n);
+  TRY(set_dev(c));
+  if (leaves) HIP_TRY(c, scopy(c, leaves, c->nb.prio.leaf, (size_t)n * 4, hipMemcpyDeviceToHost));
+  PrioState st;
+  HIP_TRY(c, scopy(c, &st, c->nb.prio.st, sizeof(st), hipMemcpyDeviceToHost));
+  if (total) *total = st.total;
+  if (pmax) *pmax = st.pmax;
+  return DDQ_OK;
+}
+
+int ddq_replay_set_priorities(ddq_ctx* c, const int32_t* idx, const uint32_t* q, int32_t n) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->prio_on) return fail(c, DDQ_ESTATE, "prioritized replay is off");
+  if (n < 0 || (n > 0 && (!idx || !q))) return fail(c, DDQ_EINVAL, "bad argument");
+  if (n == 0) return DDQ_OK;
+  TRY(set_dev(c));
+  std::vector<uint32_t> leaf((size_t)c->capacity);
+  HIP_TRY(c, scopy(c, leaf.data(), c->nb.prio.leaf, leaf.size() * 4, hipMemcpyDeviceToHost));
+  for (int k = 0; k < n; ++k) {
+    if (idx[k] < 0 || idx[k] >= c->capacity) return fail(c, DDQ_EINVAL, "index %d out of range", idx[k]);
+    if (q[k] > kPrioMax) return fail(c, DDQ_EINVAL, "priority %u above 2^24", q[k]);
+    if ((q[k] == 0) != (leaf[idx[k]] == 0))
+      return fail(c, DDQ_EINVAL, "slot %d: a zero leaf (unfilled or forbidden slot) stays zero and "
+                                 "a nonzero leaf stays nonzero", idx[k]);
+  }
+  // a slot given twice takes its last value
+  std::vector<int32_t> hi;
+  std::vector<uint32_t> hq;
+  for (int k = 0; k < n; ++k) {
+    bool later = false;
+    for (int o = k + 1; o < n && !later; ++o) later = idx[o] == idx[k];
+    if (!later) { hi.push_back(idx[k]); hq.push_back(q[k]); }
+  }
+  const int m = (int)hi.size();
+  if (m > c->pset_cap) {
+    dfree(c, c->pset_idx);
+    dfree(c, c->pset_q);
+    c->pset_cap = 0;
+    TRY(dalloc(c, &c->pset_idx, (size_t)m));
+    TRY(dalloc(c, &c->pset_q, (size_t)m));
+    c->pset_cap = m;
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->pset_idx, hi.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->pset_q, hq.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, launch_prio_set(c->nb.prio, c->pset_idx, c->pset_q, m, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return DDQ_OK;
+}
+
+int ddq_replay_update_priorities_async(ddq_ctx* c) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->prio_on) return fail(c, DDQ_ESTATE, "prioritized replay is off");
+  if (!c->idx_bound)
+    return fail(c, DDQ_ESTATE, "no device-side index set is bound (the minibatch was not drawn from "
+                               "the ring)");
+  TRY(set_dev(c));
+  HIP_TRY(c, launch_prio_commit(c->nb, c->r_meta, c->stream));
   return DDQ_OK;
 }
 
@@ -754,7 +942,8 @@ int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
   HIP_TRY(c, scopy(c, c->r_nonterm, nonterm, n, hipMemcpyHostToDevice));
   c->head = head;
   c->valid = valid;
-  return push_meta(c);
+  TRY(push_meta(c));
+  return prio_rebuild(c);
 }
 
 int ddq_replay_export(ddq_ctx* c, uint8_t* state, uint8_t* action, int16_t* reward,
@@ -804,8 +993,10 @@ int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   }
   TRY(set_dev(c));
   HIP_TRY(c, hipMemcpyAsync(c->nb.idx, idx, batch * 4, hipMemcpyHostToDevice, c->stream));
+  if (c->nb.isw) HIP_TRY(c, launch_fill_ones(c->nb.isw, batch, c->stream));   // host-given set
   HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
                            c->stream));
+  c->idx_bound = true;
   return check_err_flag(c);
 }
 
@@ -816,9 +1007,14 @@ int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 c->nb.B, (long long)(c->lanes * c->valid));
   TRY(set_dev(c));
-  HIP_TRY(c, launch_sample(c->nb, c->r_meta, seed, c->stream));
+  if (c->prio_on) {   // the prioritized draw (one workgroup), then its counter's advance
+    HIP_TRY(c, launch_prio_sample(c->nb, c->r_meta, seed, c->stream, true));
+  } else {
+    HIP_TRY(c, launch_sample(c->nb, c->r_meta, seed, c->stream));
+  }
   HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
                            c->stream));
+  c->idx_bound = true;
   return DDQ_OK;
 }
 
@@ -849,7 +1045,8 @@ int ddq_replay_fill_tiled(ddq_ctx* c, const uint8_t* state, const uint8_t* actio
   HIP_TRY(c, scopy(c, c->r_nonterm, t.data(), n, hipMemcpyHostToDevice));
   c->head = head;
   c->valid = valid;
-  return push_meta(c);
+  TRY(push_meta(c));
+  return prio_rebuild(c);
 }
 
 static int check_batch_out(ddq_ctx* c, int32_t n, float* s0, float* a, float* r, float* s1,
@@ -1016,6 +1213,11 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
   if (action) HIP_TRY(c, scopy(c, c->nb.action, action, B * 16, hipMemcpyHostToDevice));
   if (reward) HIP_TRY(c, scopy(c, c->nb.reward, reward, B * 4, hipMemcpyHostToDevice));
   if (nonterm) HIP_TRY(c, scopy(c, c->nb.nonterm, nonterm, B * 4, hipMemcpyHostToDevice));
+  if (c->nb.isw) {   // a minibatch set directly has no draw: weights 1
+    HIP_TRY(c, launch_fill_ones(c->nb.isw, B, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  c->idx_bound = false;
   return DDQ_OK;
 }
 
@@ -1137,12 +1339,15 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_out", c->nb.q_out, 4ll * B}, {"P_out", c->nb.p_out, 4ll * B},
       {"Q_sa", c->nb.q_sa, B},         {"P_sa", c->nb.p_sa, B},
       {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1},
-      {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B}};
+      {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B},
+      {"is_weight", c->nb.isw, B}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
       if (!strcmp(name, "Qn_out") && c->nb.obj_target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
+      if (!strcmp(name, "is_weight") && !c->nb.isw)
+        return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       TRY(set_dev(c));
       return copy_out(c, dst, e.p, n, 0);
     }
@@ -1219,6 +1424,7 @@ static ActorEnv actor_env(const ddq_ctx* c) {
   e.state = c->a_state; e.maps = c->a_maps; e.actor_in = c->a_in; e.S = c->nb.S;
   e.r_state = c->r_state; e.r_action = c->r_action; e.r_reward = c->r_reward;
   e.r_nonterm = c->r_nonterm; e.meta = c->r_meta;
+  e.prio = c->prio_on ? c->d_prio : nullptr;
   return e;
 }
 
@@ -1424,6 +1630,7 @@ static PoolEnv pool_env(const ddq_ctx* c) {
   e.ngames = c->p_n; e.lane_len = c->lane_len; e.h0 = c->p_h0; e.v0 = c->p_v0;
   e.r_state = c->r_state; e.r_action = c->r_action; e.r_reward = c->r_reward;
   e.r_nonterm = c->r_nonterm; e.meta = c->r_meta;
+  e.prio = c->prio_on ? c->d_prio : nullptr;
   return e;
 }
 
@@ -1590,6 +1797,7 @@ int ddq_comm_init(ddq_ctx* c, const uint8_t id[128], int32_t nranks, int32_t ran
   if (nranks < 1 || nranks > kMaxRanks || rank < 0 || rank >= nranks)
     return fail(c, DDQ_EINVAL, "bad rank/nranks (nranks <= %d)", kMaxRanks);
   if (c->local) return fail(c, DDQ_ESTATE, "ctx belongs to an in-process group");
+  TRY(prio_refuse(c, "ddq_comm_init"));
   TRY(set_dev(c));
   if (c->comm) ncclCommDestroy(c->comm);
   c->comm = nullptr;
@@ -1662,7 +1870,8 @@ static hipError_t fc4_bucket_start(void* arg) {
 
 static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
                              void* marg, int book, ReplayMeta* bump, bool overlap,
-                             const Prefetch* pf = nullptr) {
+                             const Prefetch* pf = nullptr, const NetBuffers* prio_next = nullptr,
+                             uint64_t prio_seed = 0) {
   TRY(enqueue_qn_forward(c, nb, mark, marg));
   if (nb.small) {
     HIP_TRY(c, launch_small_fwd_head(nb, c->stream, mark, marg, bump, nb.fa.on ? pf : nullptr));
@@ -1672,6 +1881,14 @@ static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void
     // fused apply: the draw counter advances here (pipelined: with the next
     // step's draw, kernels.hip head_draw)
     HIP_TRY(c, launch_head(nb, c->stream, bump, nb.fa.on ? pf : nullptr));
+  }
+  // prioritized replay: right after the launch that wrote Q_sa and target_Q_sa,
+  // one workgroup commits this step's |TD|, advances the draw counter and, when
+  // a next step is being prefetched, draws its index set and weights (the
+  // prefetch blocks below then gather with predrawn = 1)
+  if (nb.prio.leaf && bump) {
+    if (mark) mark(marg, "prio_commit");
+    HIP_TRY(c, launch_prio_commit_draw(nb, bump, prio_next, prio_seed, c->stream));
   }
   hipError_t e = nb.small ? launch_small_bwd(nb, c->stream, mark, marg, book >= 0, book, bump,
                                              overlap ? fc4_bucket_start : nullptr, c, pf)
@@ -1809,6 +2026,14 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
     nb.fa.lr = u.lr; nb.fa.decay = u.decay; nb.fa.eps = u.eps;
     nb.fa.momentum = u.momentum; nb.fa.wd = u.weight_decay;
   }
+  // Not a refusal of the contract but an invariant: while prioritization is on
+  // every exchange is refused (check_step), so ex is NONE; fused_apply_ok holds
+  // for every layout make_layout builds; and every caller of a prioritized step
+  // passes the draw counter (B <= 256, no async exchange).  Were one of these
+  // ever to change, the step would commit with no counter to advance: stop.
+  if (nb.prio.leaf && (!nb.fa.on || !bump))
+    return fail(c, DDQ_ESTATE, "internal: a prioritized step without the fused apply or the draw "
+                               "counter");
   if (pre && fused_prefetch(c, cfg)) {
     // the step's bookkeeping advances the draw counter (bump) before the apply
     // launch draws the next minibatch with it
@@ -1816,7 +2041,7 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
                                       c->r_meta, cfg->seed);
     // fused apply: the slab-reduce launch carries the draw + gather too
     TRY(enqueue_fwd_bwd_x(c, nb, mark, marg, cfg->target_period > 0 ? cfg->target_period : 0,
-                          c->r_meta, ar_overlap, nb.fa.on ? &pf : nullptr));
+                          c->r_meta, ar_overlap, nb.fa.on ? &pf : nullptr, pre, cfg->seed));
     return enqueue_exchange_apply(c, cfg, nb, mark, marg, ar_overlap, nb.fa.on ? nullptr : &pf);
   }
   if (pre) {
@@ -1828,7 +2053,7 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
     HIP_TRY(c, hipEventRecord(nb.ev[7], nb.side));
   }
   TRY(enqueue_fwd_bwd_x(c, nb, mark, marg, cfg->target_period > 0 ? cfg->target_period : 0, bump,
-                        ar_overlap));
+                        ar_overlap, nullptr, nullptr, cfg->seed));
   TRY(enqueue_exchange_apply(c, cfg, nb, mark, marg, ar_overlap));
   if (pre) HIP_TRY(c, hipStreamWaitEvent(c->stream, nb.ev[7], 0));
   return DDQ_OK;
@@ -1851,6 +2076,14 @@ static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& 
 
 static int enqueue_step(ddq_ctx* c, const ddq_step_cfg* cfg, void (*mark)(void*, const char*),
                         void* marg) {
+  if (c->prio_on) {   // one workgroup descends the sum tree, then the plain gather
+    if (mark) mark(marg, "prio_sample");
+    HIP_TRY(c, launch_prio_sample(c->nb, c->r_meta, cfg->seed, c->stream));
+    if (mark) mark(marg, "gather");
+    HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
+                             c->stream));
+    return enqueue_train(c, cfg, c->nb, nullptr, mark, marg, c->r_meta);
+  }
   if (c->nb.B <= 256) {   // one kernel: every gather workgroup draws the same index set
     if (mark) mark(marg, "sample_gather");
     HIP_TRY(c, launch_sample_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
@@ -1871,6 +2104,7 @@ static NetBuffers mb_view(const ddq_ctx* c, int p) {
   if (p == 1) {
     v.state = c->mb2_state; v.next_state = c->mb2_next; v.action = c->mb2_action;
     v.reward = c->mb2_reward; v.nonterm = c->mb2_nonterm; v.idx = c->mb2_idx;
+    if (c->prio_on) v.isw = c->mb2_reward + c->nb.B;
   }
   return v;
 }
@@ -1901,6 +2135,7 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
     return fail(c, DDQ_EINVAL, "unknown step flags 0x%x", (unsigned)cfg->flags);
   if (cfg->exchange != DDQ_EXCHANGE_NONE && c->nranks > 1 && !c->comm && !c->local)
     return fail(c, DDQ_ESTATE, "no communicator");
+  if (has_exchange(c, cfg)) TRY(prio_refuse(c, "an exchanged step"));
   return DDQ_OK;
 }
 
@@ -2131,6 +2366,7 @@ static int rccl_async_round(ddq_ctx* c, const ddq_step_cfg* cfg) {
 }
 
 int ddq_async_begin(ddq_ctx* c, const ddq_step_cfg* cfg) {
+  TRY(prio_refuse(c, "ddq_async_begin"));
   TRY(check_step(c, cfg));
   if (cfg->exchange != DDQ_EXCHANGE_ASYNC) return fail(c, DDQ_EINVAL, "cfg exchange is not async");
   if (c->mon.ring && c->mon_period > 0)
@@ -2360,6 +2596,7 @@ int ddq_step_async(ddq_ctx* c, const ddq_step_cfg* cfg) {
   TRY(rc);
   c->steps++;
   c->applied += step_inc(c, cfg);
+  c->idx_bound = true;
   return DDQ_OK;
 }
 
@@ -2410,6 +2647,7 @@ int ddq_step_graph_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps) {
   for (; i + kGraphSteps <= nsteps; i += kGraphSteps)
     HIP_TRY(c, hipGraphLaunch(c->gexec_k, c->stream));
   for (; i < nsteps; ++i) HIP_TRY(c, hipGraphLaunch(c->gexec, c->stream));
+  if (nsteps > 0) c->idx_bound = true;
   c->steps += nsteps;
   c->applied += (int64_t)nsteps * step_inc(c, cfg);
   return DDQ_OK;
@@ -2451,7 +2689,7 @@ static int ensure_pipe(ddq_ctx* c, const ddq_step_cfg* cfg) {
     TRY(dalloc(c, &c->mb2_state, (size_t)B * S * S * 4));
     TRY(dalloc(c, &c->mb2_next, (size_t)B * S * S * 4));
     TRY(dalloc(c, &c->mb2_action, (size_t)B * 4));
-    TRY(dalloc(c, &c->mb2_reward, (size_t)B));
+    TRY(dalloc(c, &c->mb2_reward, (size_t)2 * B));   // (rewards, then weights, as nb.reward)
     TRY(dalloc(c, &c->mb2_nonterm, (size_t)B));
     TRY(dalloc(c, &c->mb2_idx, (size_t)B));
   }
@@ -2510,9 +2748,14 @@ int ddq_step_pipelined_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps
   TRY(ensure_pipe(c, cfg));
   const bool fpf = fused_prefetch(c, cfg);
   if (c->steps == 0) TRY(initial_target_sync(c, cfg));
+  c->idx_bound = true;
   int p = (nsteps - 1) & 1;
   const NetBuffers first = mb_view(c, p);
-  if (fpf) {
+  if (c->prio_on) {
+    HIP_TRY(c, launch_prio_sample(first, c->r_meta, cfg->seed, c->stream));
+    HIP_TRY(c, launch_gather(first, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
+                             c->stream));
+  } else if (fpf) {
     HIP_TRY(c, launch_sample_gather(first, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
                                     c->r_meta, cfg->seed, c->stream));
   } else {
@@ -2553,6 +2796,7 @@ int ddq_group_init(ddq_ctx** ctxs, int32_t W) {
     ddq_ctx* c = ctxs[r];
     if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx in group");
     if (c->comm) return fail(c, DDQ_ESTATE, "ctx already has an RCCL communicator");
+    TRY(prio_refuse(c, "ddq_group_init"));
     if (c->nb.S != ctxs[0]->nb.S || c->nb.B != ctxs[0]->nb.B)
       return fail(c, DDQ_EINVAL, "group members must share batch and frame");
   }
@@ -2634,6 +2878,7 @@ static int check_group(ddq_ctx** ctxs, int W, const ddq_step_cfg* cfg) {
   if (!ctxs || !cfg || W < 1) return fail(nullptr, DDQ_EINVAL, "bad argument");
   for (int r = 0; r < W; ++r) {
     ddq_ctx* c = ctxs[r];
+    TRY(prio_refuse(c, "a group step or tick"));
     if (!c || !c->local || c->nranks != W || c->rank != r)
       return fail(c, DDQ_ESTATE, "ctx %d is not rank %d of a %d-member group", r, r, W);
     TRY(check_step(c, cfg));

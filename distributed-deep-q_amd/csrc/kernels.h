@@ -61,6 +61,30 @@ struct FusedApplyCfg {
 
 struct Prefetch;
 
+// Prioritized replay (prio.hip, prio.h, ddq_replay_set_priority): a radix-64 sum tree over
+// the ring's slots in device memory.  Leaves are uint32 fixed-point priorities
+// (16 fraction bits; 0 = unfilled or forbidden slot, else in [1, 2^24]); level
+// k >= 1 holds the exact uint64 sums of 64 nodes of level k - 1; every level is
+// padded with zeros to a multiple of 64 nodes and the top level has <= 64.  The
+// scalars a captured graph must read live sit in PrioState, never in a launch
+// argument.
+constexpr int kPrioLevels = 6;          // sum levels: 64^6 > 2^31 slots
+constexpr uint32_t kPrioOne = 65536u;   // p = 1.0
+constexpr uint32_t kPrioMax = 1u << 24;
+struct PrioState {
+  float alpha, beta, eps;
+  uint32_t pmax;
+  unsigned long long total;             // sum of all leaves (the root)
+};
+struct PrioTree {
+  uint32_t* leaf;                       // nullptr: prioritization off
+  unsigned long long* sum[kPrioLevels]; // sum[k - 1]: level k
+  int64_t padded[kPrioLevels + 1];      // nodes per level with padding ([0]: leaves)
+  int32_t nlev;                         // sum levels K >= 1
+  int64_t capacity;
+  PrioState* st;
+};
+
 struct NetBuffers {
   int B, S;
   // minibatch (NHWC frames; action one-hot (B,4); reward / non_terminal (B))
@@ -122,6 +146,12 @@ struct NetBuffers {
   int obj_target = 0, obj_loss = 0;
   float huber_delta = 0.f;
   float* qn_out = nullptr;
+  // prioritized replay: the minibatch's importance-sampling weights (B), bound
+  // only while prioritization is on and then always reward + B, the second half
+  // of the reward buffer (the head then runs its objective instantiation, reads
+  // them there and scales dQ and the loss terms by them); prio: the tree
+  float* isw = nullptr;
+  PrioTree prio{};
   // deepq16 step (small.h, small_bwd.h): fc4 chain partials and its fan-in words
   int small;                        // S == 16, B <= 256: the four-launch step
   int small_G = 1;                  // its fc4 chain's image chunks (B > 32: ceil(B / 32))
@@ -256,6 +286,7 @@ struct ActorEnv {
   int16_t* r_reward;
   uint8_t* r_nonterm;
   ReplayMeta* meta;
+  const PrioTree* prio;             // device copy of the tree; nullptr: prioritization off
 };
 // One workgroup: (play != 0) epsilon-greedy action from q[0..4) and the coin
 // against thresh = ceil(epsilon * 2^53), one game step, the transition into
@@ -303,6 +334,7 @@ struct PoolEnv {
   int16_t* r_reward;
   uint8_t* r_nonterm;
   ReplayMeta* meta;
+  const PrioTree* prio;             // device copy of the tree; nullptr: prioritization off
 };
 // ngames workgroups: (play != 0) game g's epsilon-greedy action from
 // q[4g..4g+4) and the coin against thresh, one game step, the transition into
@@ -363,6 +395,31 @@ hipError_t launch_gather_nchw(const uint8_t* st, const uint8_t* act, const int16
 hipError_t launch_tile(uint8_t* dst, const uint8_t* src, uint64_t pool_bytes, uint64_t total,
                        hipStream_t s);
 hipError_t launch_u8_to_nhwc(const uint8_t* src, int n, int S, float* dst, hipStream_t s);
+
+// Prioritized replay launches (prio.hip).  All one stream-ordered launch each, no
+// allocation, graph-capture safe.
+// every filled, allowed slot <- st->pmax, the rest 0, then the sums bottom-up
+hipError_t launch_prio_rebuild(const PrioTree& t, const ReplayMeta* meta, hipStream_t s);
+// one workgroup: the draw counter's stratified sample into nb.idx / nb.isw (and
+// the index log); advance: the counter moves on afterwards (a step's own
+// launch_prio_commit_draw does that otherwise)
+hipError_t launch_prio_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s,
+                              bool advance = false);
+// one workgroup, after the launch that wrote nb.q_sa / nb.target: commit |TD| of
+// nb.idx.  bump: the draw counter advances by one; next != nullptr: then draw
+// the advanced counter's sample into next->idx / next->isw and log it
+hipError_t launch_prio_commit_draw(const NetBuffers& nb, ReplayMeta* bump, const NetBuffers* next,
+                                   uint64_t seed, hipStream_t s);
+// the commit alone (ddq_replay_update_priorities_async)
+hipError_t launch_prio_commit(const NetBuffers& nb, ReplayMeta* meta, hipStream_t s);
+// the writer rule for one add at lane-local slot h of lane `lane` (host adds)
+hipError_t launch_prio_add(const PrioTree& t, const ReplayMeta* meta, int64_t lane, int64_t h,
+                           hipStream_t s);
+// leaves idx[0..n) <- q[0..n) (device arrays), sums fixed, pmax raised
+hipError_t launch_prio_set(const PrioTree& t, const int32_t* idx, const uint32_t* q, int n,
+                           hipStream_t s);
+// fill n floats with 1.0f (the weights of a host-given minibatch)
+hipError_t launch_fill_ones(float* dst, int n, hipStream_t s);
 
 double step_flops(int B, int S);
 

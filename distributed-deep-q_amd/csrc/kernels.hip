@@ -5,6 +5,7 @@
 #include "fc.h"
 #include "split.h"
 #include "small.h"
+#include "replay_dev.h"
 
 namespace ddq {
 
@@ -82,12 +83,7 @@ double step_flops(int B, int S) {
 // ---------------------------------------------------------------------------
 // replay: index draw (device RNG) and minibatch gather (replay.py:144-183)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+// (splitmix64, replay_forbidden, log_draw: replay_dev.h, shared with prio.hip)
 
 // One workgroup: B <= blockDim distinct indices, uniform over [0,valid) \ {head-1}
 // (the distribution of replay.py:152-157's whole-list redraw), sorted into
@@ -99,17 +95,6 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 // x forbidden iff head >= 1 and x mod valid == head - 1, and the final sorted x
 // mapped to slots (x div valid) * lane_len + x mod valid.
 constexpr int kDrawRounds = 4096;
-
-// n-step returns (ddq_replay_set_nstep, include/ddq_hip.h): may a sample start
-// at lane-local slot x of a lane with head h, v of L slots filled?  Not when
-// one of its n window slots x+1..x+n is the write head's or a later, unwritten
-// one: d = h - 1 - x in [0, n), d taken mod L on a full ring.  n = 1: x == h - 1.
-// (slots fit 32 bits: capacity < 2^31)
-__device__ __forceinline__ bool replay_forbidden(int x, int h, int v, int L, int n) {
-  int d = h - 1 - x;
-  if (d < 0 && n >= 2 && v == L) d += L;
-  return (uint32_t)d < (uint32_t)n;
-}
 
 // The n-step window of slot i: s_k = base + (x + k) mod L within i's lane,
 // m = the first k in 1..n whose slot is terminal (else n), s1, sm, and -- for
@@ -278,12 +263,6 @@ __device__ void draw_sorted(ReplayMeta* meta, int B, uint64_t seed, uint64_t ctr
     cand[t] = (int64_t)lane * meta->lane_len + (x - lane * (uint32_t)lvalid);
   }
   __syncthreads();
-}
-
-// Index log (ddq_index_log_enable): draw `ctr`'s sorted set, B entries.
-__device__ __forceinline__ void log_draw(int32_t* log, int64_t cap, uint64_t ctr, int B, int t,
-                                         int32_t v) {
-  if (log && t < B) log[(int64_t)(ctr % (uint64_t)cap) * B + t] = v;
 }
 
 template <bool NS>
@@ -809,8 +788,15 @@ struct HeadArgs {
   // selectable objective (NetBuffers::obj_*), uniform over the launch
   int obj_target, obj_loss;
   float huber_delta;
+  // prioritized replay: the minibatch's importance-sampling weights follow its
+  // rewards, reward[B..2B) (NetBuffers::isw; read by the objective instantiation
+  // only).  The flag sits in the hole before qn: no offset of the struct moves
+  int weighted;
   const float* qn;
 };
+static_assert(offsetof(HeadArgs, qn) == offsetof(HeadArgs, huber_delta) + 8 &&
+                  sizeof(HeadArgs) == offsetof(HeadArgs, qn) + 8,
+              "HeadArgs: the weight flag fills padding");
 
 template <bool NS>
 __device__ __forceinline__ void head_draw(const HeadArgs& H) {
@@ -1035,6 +1021,11 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
     gsc = fminf(fmaxf(diff, -dl), dl) / (float)B;
     le = ad <= dl ? diff * diff : dl * (2.f * ad - dl);
   }
+  if (OBJ && H.weighted) {                                       // importance-sampling weight:
+    const float wb = H.reward[B + b];                            // each product rounded on its own
+    gsc = wb * gsc;
+    le = wb * le;
+  }
   float dq[4];
 #pragma unroll
   for (int a = 0; a < 4; ++a) dq[a] = ac[a] * gsc;
@@ -1248,11 +1239,13 @@ static HeadArgs head_args(const NetBuffers& nb, ReplayMeta* bump) {
                   L.w[4], L.b[4], nb.action, nb.reward, nb.nonterm, nb.h4[0], nb.h4[1], nb.q_out,
                   nb.p_out, nb.q_sa, nb.p_sa, nb.target, nb.dqbuf, nb.lpart, nb.dh4,
                   nb.fa.on ? nb.opt_init : nullptr, nb.iter, nb.fa.period, nb.book_inc,
-                  (nb.fa.on || nb.head_bump) ? bump : nullptr, nb.wks[0], L.wks_total,
+                  // (prioritized steps: prio_commit_draw advances the counter and draws)
+                  ((nb.fa.on || nb.head_bump) && !nb.prio.leaf) ? bump : nullptr, nb.wks[0],
+                  L.wks_total,
                   L.wks_off[1], L.wkst_off,
                   L.wks_off[2], L.wkst3_off,
                   nullptr, nullptr, 0, nullptr, 0,
-                  nb.obj_target, nb.obj_loss, nb.huber_delta, nb.qn_out};
+                  nb.obj_target, nb.obj_loss, nb.huber_delta, nb.isw != nullptr, nb.qn_out};
 }
 
 static Fc4DgradArgs fc4_dgrad_args(const NetBuffers& nb, bool& narrow, int& ndx, int& nd) {
@@ -1279,7 +1272,7 @@ hipError_t launch_head(const NetBuffers& nb, hipStream_t s, ReplayMeta* bump, co
     H.didx = pf->idx; H.dseed = pf->seed; H.dlog = pf->idx_log; H.dlog_cap = pf->log_cap;
     extra = 1;
   }
-  const bool obj = H.obj_target || H.obj_loss;
+  const bool obj = H.obj_target || H.obj_loss || H.weighted;
   ddq_launch(nb.nstep > 1 ? (obj ? fc4_head_obj_kernel<true> : fc4_head_kernel<true>)
                           : (obj ? fc4_head_obj_kernel<false> : fc4_head_kernel<false>),
              dim3(nb.B + 25 + 9 + extra), dim3(kFc4), 0, s, H);
@@ -2143,7 +2136,8 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   sm16::BookArgs bk{};
   bk.latch = nb.fa.on ? nb.opt_init : nullptr;
   bk.iter = nb.iter; bk.period = nb.fa.period; bk.inc = nb.book_inc; bk.B = nb.B;
-  ReplayMeta* hb = (nb.fa.on || nb.head_bump) ? bump : nullptr;
+  // (prioritized steps: prio_commit_draw advances the counter and draws)
+  ReplayMeta* hb = ((nb.fa.on || nb.head_bump) && !nb.prio.leaf) ? bump : nullptr;
   if (pf && pf->ng > 0 && hb && nb.B <= 256) {
     bk.dmeta = hb;
     bk.didx = pf->idx; bk.dseed = pf->seed; bk.dlog = pf->idx_log; bk.dlog_cap = pf->log_cap;
@@ -2165,6 +2159,7 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   c.dq_out = nb.dqbuf;
   c.obj_target = nb.obj_target; c.obj_loss = nb.obj_loss; c.huber_delta = nb.huber_delta;
   c.qn = nb.qn_out;
+  c.weighted = nb.isw != nullptr;
   if (c.obj_target && !c.qn) return hipErrorInvalidValue;
   c.apply = nb.fa.on && !nb.fa.ext;
   c.store_grad = nb.fa.store_grad;
@@ -2175,7 +2170,7 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   if (c.G > 8 || (c.G > 1 && (!c.upart || !c.w4part))) return hipErrorInvalidValue;
   // B <= 32: one tower a workgroup (kFcBlk of the P tower, then kFcBlk of
   // Q); B > 32: both towers a workgroup, kFcBlk G (all resident)
-  const bool one = c.G == 1, obj = c.obj_target || c.obj_loss;
+  const bool one = c.G == 1, obj = c.obj_target || c.obj_loss || c.weighted;
   auto kern = obj ? (one ? sm16::fc4_chain16_obj_kernel<1> : sm16::fc4_chain16_obj_kernel<2>)
                   : (one ? sm16::fc4_chain16_kernel<1> : sm16::fc4_chain16_kernel<2>);
   static std::atomic<uint64_t> attr[4] = {{0}, {0}, {0}, {0}};
@@ -2515,6 +2510,8 @@ __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
 
 }  // namespace ddq
 
+// prioritized replay: the writers' rule (the tree's own kernels: prio.hip)
+#include "prio.h"
 // the device-resident actor's environment step (after launch_act's forward)
 #include "actor.h"
 // the device-resident evaluator's environment step: one game per workgroup

@@ -24,7 +24,8 @@ __global__ __launch_bounds__(kActorThreads) void pool_env_kernel(
     ActorState* __restrict__ games, const uint8_t* __restrict__ maps, const float* __restrict__ q,
     uint64_t thresh, int play, int S, int64_t lane_len, int64_t h0, int64_t v0,
     uint8_t* __restrict__ r_state, uint8_t* __restrict__ r_action, int16_t* __restrict__ r_reward,
-    uint8_t* __restrict__ r_nonterm, ReplayMeta* __restrict__ meta, float* __restrict__ pool_in) {
+    uint8_t* __restrict__ r_nonterm, ReplayMeta* __restrict__ meta, float* __restrict__ pool_in,
+    const PrioTree* __restrict__ prio) {
   __shared__ int8_t bd[5 * kCells];     // 4-frame history (oldest first), then init_board
   __shared__ int8_t nbd[kCells];        // the board after this move
   __shared__ uint8_t lv[4 * kCells];    // gray levels of the next state's four boards
@@ -56,6 +57,14 @@ __global__ __launch_bounds__(kActorThreads) void pool_env_kernel(
       meta->head = h + 1 == lane_len ? 0 : h + 1;
       const int64_t v = v0 + steps + 1;
       meta->valid = v < lane_len ? v : lane_len;
+    }
+    // prioritized replay: the writer rule (prio.h) on this lane's slot; the
+    // lanes' shared ancestors take integer atomic adds, which are exact
+    if (prio) {
+      const int64_t v2 = v0 + steps + 1;
+      prio_on_add(*prio, (int64_t)gi * lane_len, (int)h, (int)lane_len,
+                  (int)(h + 1 == lane_len ? 0 : h + 1), (int)(v2 < lane_len ? v2 : lane_len),
+                  meta->nstep);
     }
     s_over = over;
     as->draws = k;
@@ -101,7 +110,7 @@ hipError_t launch_pool_env(const PoolEnv& e, const float* q, uint64_t thresh, in
                            hipStream_t s) {
   ddq_launch(pool_env_kernel, dim3(e.ngames), dim3(kActorThreads), 0, s, e.games, e.maps, q,
              thresh, play, e.S, e.lane_len, e.h0, e.v0, e.r_state, e.r_action, e.r_reward,
-             e.r_nonterm, e.meta, e.pool_in);
+             e.r_nonterm, e.meta, e.pool_in, e.prio);
   CHECK_LAUNCH(hipGetLastError());
   return hipSuccess;
 }

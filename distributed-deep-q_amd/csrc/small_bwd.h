@@ -60,6 +60,10 @@ struct ChainArgs {
   int64_t w4_off, b4_off, w5_off, b5_off;
   const float *action, *reward, *nonterm;
   float gamma;
+  // prioritized replay: the minibatch's importance-sampling weights follow its
+  // rewards, reward[B..2B) (NetBuffers::isw; read by the objective instantiation
+  // only).  The flag sits in the hole before qpart: no offset of the struct moves
+  int weighted;
   float* qpart;                    // [32][2][B][4]
   float* dpart;                    // [32][B][256]
   int32_t* sync;                   // [0..1] the fan-in's 64-bit counter, [2] sticky spin timeout,
@@ -83,6 +87,8 @@ struct ChainArgs {
   ApplyArgs aa;
   ApplyTail at;
 };
+static_assert(offsetof(ChainArgs, qpart) == offsetof(ChainArgs, gamma) + 8,
+              "ChainArgs: the weight flag fills padding");
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
@@ -329,6 +335,11 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
       const float dl = c.huber_delta, ad = fabsf(diff);
       gsc = fminf(fmaxf(diff, -dl), dl) / (float)B;
       le = ad <= dl ? diff * diff : dl * (2.f * ad - dl);
+    }
+    if (OBJ && c.weighted) {                       // importance-sampling weight: each
+      const float wb = c.reward[B + b];            // product rounded on its own
+      gsc = wb * gsc;
+      le = wb * le;
     }
     float4 dqv;
     dqv.x = ac[0] * gsc; dqv.y = ac[1] * gsc; dqv.z = ac[2] * gsc; dqv.w = ac[3] * gsc;

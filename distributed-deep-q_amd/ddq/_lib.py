@@ -71,6 +71,13 @@ class Objective(ctypes.Structure):
                 ("huber_delta", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class PriorityCfg(ctypes.Structure):
+    """include/ddq_hip.h ddq_priority_cfg (16 bytes)."""
+    _fields_ = [("enabled", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("beta", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+PRIO_ONE, PRIO_MAX = 1 << 16, 1 << 24      # a leaf of 1.0; the largest leaf
 TARGETS = {"max": 0, "double": 1}          # include/ddq_hip.h enum ddq_target
 LOSSES = {"euclidean": 0, "huber": 1}      # include/ddq_hip.h enum ddq_loss
 STEP_NO_GRAD_STORE = 1     # include/ddq_hip.h DDQ_STEP_NO_GRAD_STORE
@@ -139,6 +146,12 @@ _SIGS = {
     "ddq_replay_lanes": (ctypes.c_int, [_P, _P, _P]),
     "ddq_replay_set_nstep": (ctypes.c_int, [_P, _i32]),
     "ddq_replay_nstep": (ctypes.c_int, [_P, _P]),
+    "ddq_replay_set_priority": (ctypes.c_int, [_P, ctypes.POINTER(PriorityCfg)]),
+    "ddq_replay_get_priority": (ctypes.c_int, [_P, ctypes.POINTER(PriorityCfg)]),
+    "ddq_replay_update_priorities_async": (ctypes.c_int, [_P]),
+    "ddq_replay_priorities": (ctypes.c_int, [_P, _P, _i64, ctypes.POINTER(_u64),
+                                             ctypes.POINTER(ctypes.c_uint32)]),
+    "ddq_replay_set_priorities": (ctypes.c_int, [_P, _P, _P, _i32]),
     "ddq_actors_create": (ctypes.c_int, [_P, _i32, _P, _P, _P, _u64]),
     "ddq_actors_step_async": (ctypes.c_int, [_P, _i32, _i64]),
     "ddq_actors_read": (ctypes.c_int, [_P, _P, _P, _P]),

@@ -150,7 +150,12 @@ class DeviceActor:
         would be drawn against the ring as it was before that act's transition.
         That holds per single act.  A chain's first step draws and gathers for
         itself, so a whole chain can follow a move of N lock-step actors:
-        ``DeviceActorPool.act_and_train``."""
+        ``DeviceActorPool.act_and_train``.
+
+        With prioritized replay on (``net.replay_set_priority``) the act also
+        keeps the priority tree (the new slot becomes undrawable, the one
+        leaving the head's reach gets the largest priority) and every step
+        commits its |TD| before the next draw."""
         for k in range(int(n)):
             self.net.actor_step(1, iter0 + k)
             self.net.step_graph(cfg, 1)
@@ -203,7 +208,10 @@ class DeviceActorPool:
         pipelined chain), all enqueued on the ctx stream; the caller
         synchronises.  Act and train stay 1:1.  The chain's first step draws and
         gathers after the move, so every minibatch of a round is drawn against
-        the ring as the round's move left it."""
+        the ring as the round's move left it.  With prioritized replay on
+        (``net.replay_set_priority``) the move keeps the priority tree lane by
+        lane, and inside the chain each step's commit precedes the next step's
+        draw, exactly as in the same sequence issued eagerly."""
         n = self.ngames
         for r in range(int(rounds)):
             self.net.actors_step(1, iter0 + r * n)

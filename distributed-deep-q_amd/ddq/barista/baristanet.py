@@ -2,7 +2,7 @@
 with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
-reset_log=False, objective=None, n_step=None)``:
+reset_log=False, objective=None, n_step=None, priority=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -16,7 +16,13 @@ reset_log=False, objective=None, n_step=None)``:
   "huber", "huber_delta": 1.0}``;
 * ``n_step`` -- None (the dataset's own n-step length, 1 unless it was made with
   ``ReplayDataset(n_step=)``) or the n of the n-step returns the minibatches are
-  gathered for (``DeepQNet.replay_set_nstep``), set on every dataset added.
+  gathered for (``DeepQNet.replay_set_nstep``), set on every dataset added;
+* ``priority`` -- None (the dataset's own setting, uniform unless it was made with
+  ``ReplayDataset(priority=)``) or a dict ``{"alpha":, "beta":, "eps":}`` of
+  proportional prioritized replay (``DeepQNet.replay_set_priority``), set on
+  every dataset added.  With it ``load_minibatch`` takes the device's
+  prioritized draw and ``full_pass`` is followed by the commit of the pass's
+  |TD| to the drawn slots.
 
 The input buffers ``state``, ``action``, ``reward``, ``next_state``,
 ``non_terminal`` have the reference's shapes (baristanet.py:30-34).  They are
@@ -27,6 +33,7 @@ and ``sync_inputs()`` / ``push_inputs()`` move them host <-> device on demand.
 from __future__ import annotations
 
 import os
+import random
 import re
 import urllib.request
 
@@ -68,7 +75,8 @@ class _Blob:
 
 class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
-                 reset_log=False, device=0, mode="gpu", objective=None, n_step=None):
+                 reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
+                 priority=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
@@ -88,6 +96,8 @@ class BaristaNet:
         self.dqn.sync_target()
         self.dataset = None
         self.n_step = None if n_step is None else int(n_step)
+        self.priority = priority
+        self.per_seed = random.getrandbits(63)   # the prioritized draws' index stream
         self.driver = driver
         # logpath: the reference's per-step loss / norm files (baristanet.py:45-46,
         # netutils.NetLogger), from records of the device-resident monitor; None
@@ -127,6 +137,8 @@ class BaristaNet:
         dset.attach(self.dqn)
         if self.n_step is not None:
             dset.set_n_step(self.n_step)
+        if self.priority is not None:
+            dset.set_priority(self.priority)
         self.dataset = dset
 
     # --------------------------------------------------------------- inputs
@@ -143,7 +155,10 @@ class BaristaNet:
 
     def load_minibatch(self):
         """baristanet.py:55-68: sample from the replay into the net inputs."""
-        if self.dataset:
+        if self.dataset and self.dataset.priority is not None:
+            # the device's prioritized draw (and its importance-sampling weights)
+            self.dqn.replay_sample_device(self.per_seed)
+        elif self.dataset:
             idx = self.dataset.draw_indices(self.batch_size)
             self.dqn.replay_sample(np.asarray(idx, np.int32))
         else:
@@ -201,8 +216,13 @@ class BaristaNet:
             self.dqn.forward_backward()
 
     def full_pass(self):
-        """baristanet.py:138-140: forward + backward on the bound minibatch."""
-        return self.dqn.forward_backward()
+        """baristanet.py:138-140: forward + backward on the bound minibatch; on
+        a prioritized dataset the pass's |TD| then becomes the drawn slots'
+        priorities."""
+        loss = self.dqn.forward_backward()
+        if self.dataset and self.dataset.priority is not None:
+            self.dqn.replay_update_priorities()
+        return loss
 
     def select_action(self, state, batch_size=1):
         """baristanet.py:142-146: argmax_a Q(s, a) (first max).  ``state`` is

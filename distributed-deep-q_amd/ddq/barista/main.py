@@ -28,6 +28,12 @@ Huber loss with band D in place of the Euclidean one.  Both work in either mode.
 (``DeepQNet.replay_set_nstep``): the discounted sum of up to N rewards and
 gamma^N P(s_{t+N}, .), cut at the first terminal step.  Either mode.
 
+``--per-alpha A`` (off by default) turns on proportional prioritized replay
+(``DeepQNet.replay_set_priority``) with exponent A in [0, 1]; ``--per-beta``
+(default 0.4, in [0, 1]) is the importance-sampling exponent and ``--per-eps``
+(default 0.01, > 0) the priority floor.  ``load_minibatch`` then takes the
+device's prioritized draw and every ``full_pass`` commits its |TD|.  Either mode.
+
 ``--logpath PREFIX`` (off by default) makes ``net.log()`` append the step's loss
 and every blob's gradient / parameter RMS to files under ``PREFIX-<date>``
 (netutils.NetLogger), from one record of the device-resident monitor.
@@ -114,7 +120,21 @@ def get_args(argv=None):
                     help="Huber loss with this band instead of the Euclidean loss")
     ap.add_argument("--n-step", dest="n_step", type=int, default=1,
                     help="N-step returns: the replay gathers N-step windows (default 1)")
+    ap.add_argument("--per-alpha", dest="per_alpha", type=float, default=None,
+                    help="prioritized replay with this priority exponent in [0, 1] (default: off)")
+    ap.add_argument("--per-beta", dest="per_beta", type=float, default=None,
+                    help="prioritized replay: importance-sampling exponent in [0, 1] (default 0.4)")
+    ap.add_argument("--per-eps", dest="per_eps", type=float, default=None,
+                    help="prioritized replay: priority floor, > 0 (default 0.01)")
     args = ap.parse_args(argv)
+    if args.per_alpha is None and (args.per_beta is not None or args.per_eps is not None):
+        ap.error("--per-beta / --per-eps need --per-alpha")
+    if args.per_alpha is not None and not 0.0 <= args.per_alpha <= 1.0:
+        ap.error("--per-alpha must be in [0, 1]")
+    if args.per_beta is not None and not 0.0 <= args.per_beta <= 1.0:
+        ap.error("--per-beta must be in [0, 1]")
+    if args.per_eps is not None and not args.per_eps > 0:
+        ap.error("--per-eps must be > 0")
     if not 1 <= args.n_step <= NSTEP_MAX:
         ap.error("--n-step must be in [1, %d]" % NSTEP_MAX)
     if args.n_step >= args.dset_size:
@@ -138,6 +158,16 @@ def objective_of(args):
     return obj
 
 
+def priority_of(args):
+    """ReplayDataset's ``priority`` for --per-alpha / --per-beta / --per-eps (None: off)."""
+    alpha = getattr(args, "per_alpha", None)
+    if alpha is None:
+        return None
+    beta, eps = getattr(args, "per_beta", None), getattr(args, "per_eps", None)
+    return {"alpha": alpha, "beta": 0.4 if beta is None else beta,
+            "eps": 0.01 if eps is None else eps}
+
+
 def build_worker(args):
     model = None if args.model in ("none", "None") else args.model
     net = BaristaNet(args.architecture, model, args.driver,
@@ -145,7 +175,7 @@ def build_worker(args):
                      objective=objective_of(args))
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
                            overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode,
-                           n_step=getattr(args, "n_step", 1))
+                           n_step=getattr(args, "n_step", 1), priority=priority_of(args))
     net.add_dataset(replay)
     game = SnakeGame()
     pre = eg.generate_preprocessor(net.state.shape[2:], gray_scale)

@@ -21,7 +21,7 @@ NUM_ACTIONS = 4     # barista/constants.py:8
 NFRAME = 4          # expgain.py:9
 
 BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0,
-         "Qn_out": 4, "Q_out.diff": 4}
+         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1}
 
 # include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
 MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
@@ -443,6 +443,51 @@ class DeepQNet:
         n = _lib._i32()
         self._check(self.lib.ddq_replay_nstep(self.ctx, ctypes.byref(n)))
         return int(n.value)
+
+    def replay_set_priority(self, alpha=0.6, beta=0.4, eps=1e-2, enabled=True):
+        """Proportional prioritized replay (ddq_replay_set_priority): device draws
+        pick slots in proportion to their priority (|TD| + eps)^alpha, the head
+        weights each sample by (q_min / q)^beta (blob ``is_weight``), and every
+        step commits its |TD| back.  Called while enabled it only rewrites
+        alpha, beta and eps, stream-ordered with no synchronisation (anneal beta
+        this way).  ``enabled=False`` frees the tree and restores the uniform
+        launches."""
+        cfg = _lib.PriorityCfg(1 if enabled else 0, float(alpha), float(beta), float(eps))
+        self._check(self.lib.ddq_replay_set_priority(self.ctx, ctypes.byref(cfg)))
+
+    def replay_priority(self):
+        """The prioritization settings, or None while it is off."""
+        cfg = _lib.PriorityCfg()
+        self._check(self.lib.ddq_replay_get_priority(self.ctx, ctypes.byref(cfg)))
+        if not cfg.enabled:
+            return None
+        return {"alpha": float(cfg.alpha), "beta": float(cfg.beta), "eps": float(cfg.eps)}
+
+    def replay_priorities(self, leaves=True):
+        """(leaves, total, pmax): every slot's uint32 priority (65536 = 1.0, 0 =
+        unfilled or forbidden slot; None with ``leaves=False``), their exact sum
+        and the largest priority seen since the last rebuild.  Synchronises."""
+        _, _, cap = self.replay_info()
+        q = np.empty(cap, np.uint32) if leaves else None
+        total, pmax = _lib._u64(), ctypes.c_uint32()
+        self._check(self.lib.ddq_replay_priorities(self.ctx, ptr(q), cap, ctypes.byref(total),
+                                                   ctypes.byref(pmax)))
+        return q, int(total.value), int(pmax.value)
+
+    def replay_set_priorities(self, idx, q):
+        """Overwrite the leaves of slots ``idx`` with ``q`` (uint32 in [1, 2^24];
+        a zero leaf stays zero).  Synchronises."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        q = np.ascontiguousarray(q, np.uint32)
+        if idx.shape != q.shape or idx.ndim != 1:
+            raise ValueError("idx and q must be 1-D arrays of one length")
+        self._check(self.lib.ddq_replay_set_priorities(self.ctx, ptr(idx), ptr(q), idx.size))
+
+    def replay_update_priorities(self):
+        """Commit |Q_sa - target_Q_sa| of the last pass over the bound, ring-drawn
+        minibatch to its slots' priorities (the step modes do this themselves;
+        this is for forward_backward users).  Enqueued, no sync."""
+        self._check(self.lib.ddq_replay_update_priorities_async(self.ctx))
 
     def replay_import(self, state, action, reward, non_terminal, head, valid):
         st = np.ascontiguousarray(state, np.uint8)

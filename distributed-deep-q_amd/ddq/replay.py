@@ -23,6 +23,13 @@ start slot whose n-slot window would reach the write head), and the gather
 returns the discounted reward sum as ``reward``, gamma^(n-1) or 0 as
 ``non_terminal`` and s_{t+m} as ``next_state``.  n is a property of sampling,
 not of the data: the file does not hold it.
+``priority`` (default None: uniform sampling, the reference) is a dict
+``{"alpha":, "beta":, "eps":}`` that turns on proportional prioritized replay
+on the ring (``DeepQNet.replay_set_priority``): the device draws
+(``DeepQNet.replay_sample_device``, the step modes) then follow the slots'
+priorities, while ``draw_indices`` stays the reference's uniform host draw
+(weights 1).  Priorities are a property of sampling too: the file does not hold
+them, and a reopened or attached ring starts with every allowed slot at 1.0.
 Persistence (replay.py:23-45 reopen, :185-192 persist on ``__del__``):
 ``save()`` / ``close()`` / ``__del__`` write ``filename`` as the reference's
 HDF5 file (``ddq.h5lite``: same datasets, dtypes and head/valid attributes,
@@ -48,11 +55,13 @@ class ReplayDataset:
     # the default for an object made without __init__ (tests build one around a
     # stub ring to check draw_indices against the reference's recorded draws)
     n_step = 1
+    priority = None
 
     def __init__(self, filename, state_shape, dset_size=1000, overwrite=False, batch_size=32,
-                 device=0, net=None, mode="gpu", n_step=1):
+                 device=0, net=None, mode="gpu", n_step=1, priority=None):
         self.filename = filename
         self.n_step = int(n_step)
+        self.priority = _priority_dict(priority)
         self.state_shape = tuple(int(x) for x in state_shape)
         if len(self.state_shape) != 3 or self.state_shape[0] != 4 or \
                 self.state_shape[1] != self.state_shape[2]:
@@ -80,6 +89,19 @@ class ReplayDataset:
                                     int(loaded["head"]), int(loaded["valid"]))
         if self.n_step != 1:
             self._net.replay_set_nstep(self.n_step)
+        if self.priority is not None:
+            self._net.replay_set_priority(**self.priority)
+
+    def set_priority(self, priority):
+        """Turn prioritized replay on (a dict of alpha / beta / eps; on an enabled
+        ring this only moves the three scalars, e.g. to anneal beta) or off
+        (None)."""
+        priority = _priority_dict(priority)
+        if priority is None:
+            self._net.replay_set_priority(enabled=False)
+        else:
+            self._net.replay_set_priority(**priority)
+        self.priority = priority
 
     def set_n_step(self, n):
         """Change the n-step length of the ring (legal on a filled ring)."""
@@ -106,6 +128,8 @@ class ReplayDataset:
         net.replay_import(st, ac, rw, nt.astype(np.uint8), head, valid)
         if self.n_step != 1:
             net.replay_set_nstep(self.n_step)
+        if self.priority is not None:
+            net.replay_set_priority(**self.priority)
         if self._own_net:
             self._net.close()
         self._net, self._own_net = net, False
@@ -216,6 +240,19 @@ class ReplayDataset:
             self.close()
         except Exception:
             pass
+
+
+def _priority_dict(priority):
+    """None, or {"alpha", "beta", "eps"} with the defaults of
+    ``DeepQNet.replay_set_priority`` filled in."""
+    if priority is None:
+        return None
+    unknown = set(priority) - {"alpha", "beta", "eps"}
+    if unknown:
+        raise ValueError("unknown priority settings %s" % sorted(unknown))
+    out = {"alpha": 0.6, "beta": 0.4, "eps": 1e-2}
+    out.update({k: float(v) for k, v in priority.items()})
+    return out
 
 
 def _load_ring(filename):

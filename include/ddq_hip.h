@@ -52,7 +52,11 @@ extern "C" {
                               and the selectable objective (ddq_set_objective,
                               ddq_get_objective; blobs "Qn_out", "Q_out.diff"),
                               likewise; and n-step returns (ddq_replay_set_nstep,
-                              ddq_replay_nstep), likewise */
+                              ddq_replay_nstep), likewise; and prioritized replay
+                              (ddq_replay_set_priority, ddq_replay_get_priority,
+                              ddq_replay_priorities, ddq_replay_set_priorities,
+                              ddq_replay_update_priorities_async; blob "is_weight"),
+                              likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -286,6 +290,91 @@ int ddq_replay_lanes(const ddq_ctx* ctx, int32_t* lanes, int64_t* lane_len);
 #define DDQ_NSTEP_MAX 8
 int ddq_replay_set_nstep(ddq_ctx* ctx, int32_t n);
 int ddq_replay_nstep(const ddq_ctx* ctx, int32_t* n);
+/* Proportional prioritized replay (Schaul et al. 2016; no reference counterpart).
+ * Off by default; while off every launch and every bit is what it is without
+ * this section.  While on, the device draws (the step modes,
+ * ddq_replay_sample_device_async) pick slots in proportion to a per-slot
+ * priority kept in a device sum tree, the head scales each sample's dQ and loss
+ * term by an importance-sampling weight, and every step commits |TD| back.
+ *
+ * Priorities are integers.  Slot i has a leaf q[i], a uint32: 0, or a value in
+ * [1, 2^24] read as fixed point with 16 fraction bits (65536 = 1.0).  All sums
+ * are uint64 and exact, so nothing depends on the tree's shape, the order of a
+ * reduction or of the atomics.
+ *
+ * Invariant, after every call or launch that changes the ring or n:
+ *     q[i] == 0  <=>  slot i is unfilled or forbidden
+ * with `forbidden` the n-step rule above on the ring's current head, valid,
+ * lane_len and n, per lane.  A zero leaf is never drawn, so the prioritized draw
+ * has no rejection and no redraw rounds.
+ *
+ * Writers.  After an add at lane-local slot h (lane length L, n-step length n),
+ * with head' and valid' the lane's values after the add: q[h] <- 0 if h is
+ * forbidden under head' / valid' (always, except at n = 1 when head' wrapped to
+ * 0: the n = 1 rule forbids nothing there and the slot is allowed at once, so it
+ * takes pmax); x = h - n, taken mod L when valid' == L; if x >= 0 and q[x] == 0,
+ * q[x] <- pmax (x is the slot whose window just left the head).  pmax is the
+ * largest priority ever committed or set since the last rebuild, at least
+ * 65536.  ddq_replay_add, the device actor and the actor pool follow it.
+ * A rebuild sets pmax = 65536, every filled, allowed slot to pmax and the rest
+ * to 0: on enabling, ddq_replay_import, ddq_replay_fill_tiled,
+ * ddq_replay_set_nstep and ddq_replay_set_lanes.  Priorities are a property of
+ * sampling, like n: they are not stored with the ring or in the HDF5 file.
+ *
+ * Draw ctr with seed `seed`: B samples, possibly with duplicates (idx, the index
+ * log and ddq_read_indices may repeat a slot), sorted by construction.
+ *     T    = sum of all leaves              (B <= lanes * A as for every draw, so T >= B)
+ *     lo_j = (T * j) / B      j = 0..B      uint64 floor division
+ *     r_j  = splitmix64(seed ^ splitmix64(ctr * 0x100000001B3 + j * 0x9E37))
+ *     u_j  = lo_j + mulhi64(r_j, lo_{j+1} - lo_j)
+ *     idx_j = the slot i with C(i) <= u_j < C(i+1), C the exclusive prefix sum
+ *             of q over slots 0..capacity-1
+ *     qmin = min_j q[idx_j];  isw_j = powf((float)qmin / (float)q[idx_j], beta)
+ * (N and T cancel under the batch-max normalisation; beta == 0 gives exactly
+ * 1.0f.)  isw is a per-minibatch buffer right behind reward, blob "is_weight" (B).
+ * ddq_replay_sample (host indices) and ddq_write_minibatch set it to 1.0f.  The
+ * large-batch sampler stays uniform.
+ *
+ * Head, per image b, with c = d (or clamp(d) under Huber) as above:
+ *     t = c / (float)B;  dQ scale = isw_b * t;  loss term = isw_b * le_b
+ * each product rounded on its own; with isw == 1.0f the pass is bit for bit the
+ * unweighted one.
+ *
+ * Commit, after a pass, for b = 0..B-1 and i = idx[b]:
+ *     d = Q_sa[b] - target_Q_sa[b];  p = powf(fabsf(d) + eps, alpha)
+ *     v = clamp(rintf(p * 65536.0f), 1, 2^24)       (non-finite p: 2^24)
+ * q[i] <- v only if q[i] != 0 (a slot an actor has since made forbidden is not
+ * resurrected); a slot that appears more than once takes its highest b;
+ * pmax <- max(pmax, v) over the values written.  Every step mode commits its
+ * own step (one one-workgroup launch after the head, "prio_commit" in
+ * ddq_profile_step, which in a pipelined chain also draws the next step's set):
+ * draw d+1 sees the commits of every step <= d and every add enqueued before
+ * it, in eager, graph and pipelined mode alike.  An eager step begins with
+ * "prio_sample" and "gather".
+ *
+ * ddq_replay_set_priority, enabled 0 -> 1: synchronises, drops captured graphs,
+ * allocates the tree and rebuilds.  1 -> 0 frees it.  Called while enabled it
+ * only rewrites alpha, beta and eps in device memory, stream-ordered (no
+ * synchronisation, no rebuild, no graph drop: the beta-annealing path; captured
+ * graphs read them live).  DDQ_EINVAL: alpha or beta outside [0, 1] or not
+ * finite, eps <= 0 or not finite, B > 256.  DDQ_ESTATE: no ring, a communicator
+ * or group is attached, the async exchange has begun.  While enabled,
+ * exchanged steps, ddq_group_step, ddq_group_async_*, ddq_async_begin,
+ * ddq_comm_init and ddq_group_init return DDQ_ESTATE. */
+typedef struct ddq_priority_cfg { int32_t enabled; float alpha, beta, eps; } ddq_priority_cfg; /* 16 B */
+int ddq_replay_set_priority(ddq_ctx* ctx, const ddq_priority_cfg* cfg);
+int ddq_replay_get_priority(const ddq_ctx* ctx, ddq_priority_cfg* cfg);
+/* The commit above for the bound minibatch after ddq_forward_backward: enqueued,
+ * no sync.  DDQ_ESTATE when disabled or when no device-side index set is bound
+ * (the minibatch came from ddq_write_minibatch, or the ring was rebuilt). */
+int ddq_replay_update_priorities_async(ddq_ctx* ctx);
+/* Synchronise and read: leaves (n == capacity), the root, pmax; any pointer may
+ * be NULL.  DDQ_ESTATE while disabled. */
+int ddq_replay_priorities(ddq_ctx* ctx, uint32_t* leaves, int64_t n, uint64_t* total, uint32_t* pmax);
+/* Synchronise, overwrite leaves idx[k] <- q[k] and fix the sums; pmax rises to
+ * the largest value set.  DDQ_EINVAL: a nonzero value on a zero leaf, zero on a
+ * nonzero leaf, q > 2^24, idx out of range. */
+int ddq_replay_set_priorities(ddq_ctx* ctx, const int32_t* idx, const uint32_t* q, int32_t n);
 /* Bulk load / store of the ring (the HDF5 datasets of replay.py:48-61,
  * persisted by __del__ :185-192). */
 int ddq_replay_import(ddq_ctx* ctx, const uint8_t* state, const uint8_t* action,
