@@ -3,9 +3,16 @@
 Tolerances (north star: "Q-values, targets, gradients and post-update weights
 must match within fp32 rtol 1e-4"):
   * integer / index / byte work (replay gather, argmax actions): bit-exact;
-  * fp32 tensors: tests/_parity.py ``close`` -- elementwise rtol 1e-4 for every
-    element with |ref| >= 1e-3 of the tensor's scale, the same rtol on that
-    1e-3 floor below it; the oracle runs in float64.
+  * fp32 blobs and gradients: tests/_parity.py ``close(..., mag=M)`` -- per
+    tensor, normwise ||gpu - ref|| / ||ref|| <= 1e-5; elementwise rtol 1e-4 for
+    every element with |ref| >= 1e-2 of the tensor's max|ref| and 1e-6 of that
+    max below it; and every element within rtol 1e-4 * |ref| + 2e-7 * (its sum
+    of |terms|).  The last rule alone would accept a zeroed gradient
+    (tests/test_parity_harness.py); test_full_pass_rejects_mutated_gradients
+    shows on the GPU's own output that the three together do not;
+  * parameters and optimizer state: rtol 1e-4 for every element with |ref| >=
+    1e-3 of the tensor's max, 1e-6 of the max below it;
+  * the oracle runs in float64.
 """
 import glob
 import os
@@ -199,11 +206,49 @@ def test_full_pass_parity(ddq, ref, S, B, frames, init):
     net.write_minibatch(st, act, rw, ns, nt)
     loss = net.forward_backward()
     # Pool routing bit-exact except at proven fp32-vs-fp64 near-ties (GPU
-    # routing adopted there); every blob and gradient element within
-    # rtol 1e-4 + 1e-6 * (its sum of |terms|) (tests/_parity.py).
+    # routing adopted there); every blob and gradient tensor under the three
+    # rules of tests/_parity.py (normwise 1e-5; rtol 1e-4 above 1e-2 of its
+    # max, 1e-6 of the max below; rtol 1e-4 + 2e-7 * (sum of |terms|)).
     blobs, _, nties = check_full_pass(ref, net, pQ, pP, (st, act, rw, ns, nt))
     assert loss == float(net.blob("loss"))
     print("near-tie routings adopted: %d" % nties)
+
+
+@pytest.mark.parametrize("S,B", [(16, 32),    # the small-map step's kernels K1-K4
+                                 (64, 2)])    # split-bf16 convs, the pair, a ragged last group
+def test_full_pass_rejects_mutated_gradients(ddq, ref, S, B):
+    """The harness on the GPU's own output: its gradients pass, and the same
+    buffer with any one of the ten gradient tensors zeroed, negated or scaled
+    by 1.001 does not (one pass and one oracle run per case)."""
+    from _parity import full_pass_reference
+    rng = np.random.default_rng(100 + S + B)
+    pQ, pP = make_params(ref, rng, S, "x3")
+    net = ddq.DeepQNet(batch=B, frame=S)
+    params = dict(pQ)
+    params.update(pP)
+    net.set_params(params)
+    mb = make_inputs(rng, B, S, "uniform")
+    net.write_minibatch(*mb)
+    net.forward_backward()
+    g_gpu = net.get_grads_flat().copy()
+    oracle = full_pass_reference(ref, net, pQ, pP, mb, g_gpu)
+    check_full_pass(ref, net, pQ, pP, mb, grads_gpu=g_gpu, reference=oracle)
+    rejected = 0
+    for lname, blobs in net.layout.items():
+        if not lname.startswith("Q"):
+            continue
+        for i in range(2):
+            _, off, cnt = blobs[i]
+            for label, f in (("zeroed", 0.0), ("negated", -1.0), ("x1.001", 1.001)):
+                bad = g_gpu.copy()
+                bad[off:off + cnt] *= np.float32(f)
+                with pytest.raises(AssertionError) as ei:
+                    check_full_pass(ref, net, pQ, pP, mb, grads_gpu=bad, quiet=True,
+                                    reference=oracle)
+                assert "%s[%d]" % (lname, i) in str(ei.value), (lname, i, label, str(ei.value))
+                rejected += 1
+    assert rejected == 30
+    net.close()
 
 
 @pytest.mark.parametrize("rule", ["sgd", "rmsprop", "adagrad", "momentum"])
