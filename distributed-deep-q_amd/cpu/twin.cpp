@@ -110,35 +110,30 @@ struct ddq_ctx {
   std::vector<float> isw;
   bool idx_bound = false;
   int64_t steps = 0;
-  // Snake actor (ddq_actor_*): 4-board history (oldest first), the start board,
-  // the zoom maps and the RNG stream position
-  bool actor = false;
-  int8_t a_boards[4][100], a_init[100];
-  std::vector<int32_t> a_row, a_col;
-  uint64_t a_seed = 0, a_draws = 0;
-  int64_t a_steps = 0, a_games = 0, a_reward = 0;
-  // policy evaluation (ddq_eval_*): the games in lock step, each with its own
-  // stream, move counter and episode log
-  struct EvalGame {
-    uint64_t seed = 0, draws = 0;
-    int64_t reward = 0;
-    int32_t move = 0, score = 0, moves = 0;
-    int8_t boards[4][100], init[100];
-    std::vector<int32_t> log;      // 4 per record: end_move, score, moves, ended_by
-  };
-  std::vector<EvalGame> e_games;   // empty: no evaluator
-  std::vector<int32_t> e_row, e_col;
-  double e_eps = 0.0;
-  int32_t e_max_moves = 0, e_max_ep = 0;
-  int64_t e_moves = 0;
-  // actor pool (ddq_actors_*): one game per ring lane, in lock step
-  struct PoolGame {
+  // Snake environments.  A game: its RNG stream and position, its counters, the
+  // 4-board history (oldest first) and its start board
+  struct Game {
     uint64_t seed = 0, draws = 0;
     int64_t steps = 0, games = 0, reward = 0;
     int8_t boards[4][100], init[100];
   };
-  std::vector<PoolGame> p_games;   // empty: no pool
-  std::vector<int32_t> p_row, p_col;
+  // an evaluated game also has its lock-step move counter, the running
+  // episode's score / moves and its episode log
+  struct EvalGame : Game {
+    int32_t move = 0, score = 0, moves = 0;
+    std::vector<int32_t> log;      // 4 per record: end_move, score, moves, ended_by
+  };
+  template <class G>
+  struct Env {
+    std::vector<G> games;          // empty: not created
+    std::vector<int32_t> row, col; // the zoom maps
+  };
+  Env<Game> a_env;                 // Snake actor (ddq_actor_*): one game
+  Env<EvalGame> e_env;             // policy evaluation (ddq_eval_*): games in lock step
+  Env<Game> p_env;                 // actor pool (ddq_actors_*): one game per ring lane
+  double e_eps = 0.0;
+  int32_t e_max_moves = 0, e_max_ep = 0;
+  int64_t e_moves = 0;
   // training monitor (ddq_monitor_*): the ring (empty: off) and the records taken
   std::vector<ddq_monitor_record> m_ring;
   int64_t m_total = 0;
@@ -811,8 +806,8 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   c->lanes = lanes;
   c->lane_len = c->capacity / lanes;
   c->head = 0;
-  c->p_games.clear();                // a pool or an actor belongs to the lanes it was
-  c->actor = false;                  // created on
+  c->p_env.games.clear();            // a pool or an actor belongs to the lanes it was
+  c->a_env.games.clear();            // created on
   prio_rebuild(c);
   return DDQ_OK;
 }
@@ -1181,7 +1176,9 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
   return DDQ_OK;
 }
 
-// ---- Snake actor (expgain.py:30-111 + gamesim/SnakeGame.py on this ctx) ----
+// ---- Snake environments (expgain.py:30-111 + gamesim/SnakeGame.py on this ctx):
+// the actor, the evaluator and the actor pool on one render, one validation,
+// one per-game stream and one move ----
 }  // extern "C"
 
 namespace {
@@ -1193,12 +1190,19 @@ uint64_t mix64(uint64_t x) {   // splitmix64
   return x ^ (x >> 31);
 }
 
-// draw k of the actor's stream: splitmix64(seed ^ splitmix64(k))
-uint64_t actor_next(ddq_ctx* c) { return mix64(c->a_seed ^ mix64(c->a_draws++)); }
+// seed of game g's stream among a create call's games (ddq.actor.game_seed)
+uint64_t game_seed(uint64_t seed, int g) { return mix64(mix64(seed) ^ (uint64_t)g); }
 
-uint64_t actor_randrange(ddq_ctx* c, uint64_t n) {   // high 64 bits of r * n
-  return (uint64_t)(((unsigned __int128)actor_next(c) * n) >> 64);
-}
+// A game's stream: draw k is splitmix64(seed ^ splitmix64(k)), k = draws
+struct Stream {
+  uint64_t seed;
+  uint64_t& draws;
+  uint64_t next() { return mix64(seed ^ mix64(draws++)); }
+  uint64_t randrange(uint64_t n) {   // high 64 bits of r * n
+    return (uint64_t)(((unsigned __int128)next() * n) >> 64);
+  }
+  bool coin(double eps) { return (double)(next() >> 11) * 0x1.0p-53 < eps; }   // random() < eps
+};
 
 // expgain.epsilon (expgain.py:55-60)
 double actor_eps(int64_t it) {
@@ -1224,23 +1228,66 @@ bool snake_body(const int8_t* b, std::vector<Cell>* body) {
   return true;
 }
 
-// the preprocessor: gray_scale, then the nearest-neighbour zoom through the maps
-void actor_render(const ddq_ctx* c, std::vector<uint8_t>* out) {
-  const int S = c->S;
-  out->resize((size_t)kC * S * S);
+// a create call's zoom maps and n start boards; single: ddq_actor_create's
+// one init_board
+int env_check(ddq_ctx* c, const int32_t* row_map, const int32_t* col_map, const int8_t* boards,
+              int n, bool single) {
+  for (int i = 0; i < c->S; ++i)
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+  for (int g = 0; g < n; ++g) {
+    char who[32] = "init_board";
+    if (!single) snprintf(who, sizeof(who), "init_boards[%d]", g);
+    std::vector<Cell> body;
+    if (!snake_body(boards + 100 * g, &body) || body.size() < 2)
+      return fail(c, DDQ_EINVAL, "%s: snake cells must be the codes 0..k-1, k >= 2", who);
+    if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
+      return fail(c, DDQ_EINVAL, "%s: head and neck are not neighbours", who);
+  }
+  return DDQ_OK;
+}
+
+// n fresh games on their start boards, and the maps; the seeds are the caller's
+template <class G>
+void env_reset(ddq_ctx::Env<G>* e, int n, const int8_t* boards, const int32_t* row_map,
+               const int32_t* col_map, int S) {
+  e->games.assign(n, G{});
+  for (int g = 0; g < n; ++g) {
+    memcpy(e->games[g].init, boards + 100 * g, 100);
+    for (auto& b : e->games[g].boards) memcpy(b, e->games[g].init, 100);
+  }
+  e->row.assign(row_map, row_map + S);
+  e->col.assign(col_map, col_map + S);
+}
+
+// the preprocessor: gray_scale, then the nearest-neighbour zoom through the
+// maps; out: u8 (4,S,S)
+void env_render(const int8_t boards[4][100], const std::vector<int32_t>& row,
+                const std::vector<int32_t>& col, int S, uint8_t* out) {
   for (int f = 0; f < kC; ++f)
     for (int i = 0; i < S; ++i)
       for (int j = 0; j < S; ++j) {
-        const int v = c->a_boards[f][c->a_row[i] * 10 + c->a_col[j]];
-        (*out)[((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
+        const int v = boards[f][row[i] * 10 + col[j]];
+        out[((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
       }
 }
 
+// every game's state (idle ones included) in one batched forward: the greedy actions
+template <class G>
+int env_greedy(ddq_ctx* c, const ddq_ctx::Env<G>& e, std::vector<int32_t>* greedy) {
+  const int n = (int)e.games.size();
+  const size_t fs = (size_t)kC * c->S * c->S;
+  std::vector<uint8_t> frames(n * fs);
+  for (int g = 0; g < n; ++g)
+    env_render(e.games[g].boards, e.row, e.col, c->S, frames.data() + g * fs);
+  greedy->resize(n);
+  return ddq_select_action(c, frames.data(), n, greedy->data());
+}
+
 // SnakeGame.cpu_play on board cur: the board after the move into next (not
-// when the game is over); returns the reward (-1: game over).  randrange(n)
-// draws the new apple's place among the n empty cells.
-template <class R>
-int snake_play(const int8_t* cur, int act, int8_t* next, R&& randrange) {
+// when the game is over); returns the reward (-1: game over).  The new apple's
+// place among the n empty cells is rng.randrange(n).
+int snake_play(const int8_t* cur, int act, int8_t* next, Stream& rng) {
   std::vector<Cell> body;
   snake_body(cur, &body);
   const int hdx = body[0].x - body[1].x, hdy = body[0].y - body[1].y;
@@ -1260,43 +1307,29 @@ int snake_play(const int8_t* cur, int act, int8_t* next, R&& randrange) {
     std::vector<int> empty;
     for (int i = 0; i < 100; ++i)
       if (next[i] == -1) empty.push_back(i);
-    if (!empty.empty()) next[empty[randrange(empty.size())]] = -2;
+    if (!empty.empty()) next[empty[rng.randrange(empty.size())]] = -2;
   }
   return eat ? 1 : 0;
 }
 
-// one generate_experience (expgain.py:82-111)
-int actor_step(ddq_ctx* c, double eps) {
-  std::vector<uint8_t> frames;
-  actor_render(c, &frames);
-  int32_t act = 0;
-  // ExpGain.select_action: the coin first; the net is asked only when greedy
-  if ((double)(actor_next(c) >> 11) * 0x1.0p-53 < eps) {
-    act = (int32_t)actor_randrange(c, kA);
-  } else {
-    const int rc = ddq_select_action(c, frames.data(), 1, &act);
-    if (rc != DDQ_OK) return rc;
-  }
-  // SnakeGame.cpu_play on the newest board
+// One move of a game: cpu_play on the newest board, then the next state's
+// boards -- the history shifted by one, or four start boards when the episode
+// ends (reset_game): a game over, or `last`, the caller's move limit reached
+// with this move.  Returns the reward.
+int env_move(ddq_ctx::Game& g, int act, bool last = false) {
+  Stream rng{g.seed, g.draws};
   int8_t next[100];
-  const int reward = snake_play(c->a_boards[3], act, next,
-                                [c](uint64_t n) { return actor_randrange(c, n); });
-  const bool over = reward < 0;
-  if (over) {
-    const int rc = ddq_replay_add(c, act, reward, nullptr);
-    if (rc != DDQ_OK) return rc;
-    for (auto& b : c->a_boards) memcpy(b, c->a_init, 100);   // reset_game
+  const int reward = snake_play(g.boards[3], act, next, rng);
+  if (reward < 0 || last) {
+    for (auto& b : g.boards) memcpy(b, g.init, 100);
   } else {
-    memmove(c->a_boards[0], c->a_boards[1], 300);
-    memcpy(c->a_boards[3], next, 100);
-    actor_render(c, &frames);
-    const int rc = ddq_replay_add(c, act, reward, frames.data());
-    if (rc != DDQ_OK) return rc;
+    memmove(g.boards[0], g.boards[1], 300);
+    memcpy(g.boards[3], next, 100);
   }
-  c->a_steps += 1;
-  c->a_games += over;
-  c->a_reward += reward;
-  return DDQ_OK;
+  g.steps += 1;
+  g.games += reward < 0;
+  g.reward += reward;
+  return reward;
 }
 
 }  // namespace
@@ -1307,36 +1340,40 @@ int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_ma
                      const int32_t* col_map, uint64_t seed) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!init_board || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
-  for (int i = 0; i < c->S; ++i)
-    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
-      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
-  std::vector<Cell> body;
-  if (!snake_body(init_board, &body) || body.size() < 2)
-    return fail(c, DDQ_EINVAL, "init_board: snake cells must be the codes 0..k-1, k >= 2");
-  if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
-    return fail(c, DDQ_EINVAL, "init_board: head and neck are not neighbours");
+  const int rc = env_check(c, row_map, col_map, init_board, 1, true);
+  if (rc != DDQ_OK) return rc;
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (c->lanes > 1)
     return fail(c, DDQ_ESTATE, "ddq_actor_create on a laned ring (%d lanes): use ddq_actors_create",
                 c->lanes);
-  memcpy(c->a_init, init_board, 100);
-  for (auto& b : c->a_boards) memcpy(b, init_board, 100);
-  c->a_row.assign(row_map, row_map + c->S);
-  c->a_col.assign(col_map, col_map + c->S);
-  c->a_seed = seed;
-  c->a_draws = 0;
-  c->a_steps = c->a_games = c->a_reward = 0;
-  c->actor = true;
+  env_reset(&c->a_env, 1, init_board, row_map, col_map, c->S);
+  c->a_env.games[0].seed = seed;     // the one game's stream takes the seed verbatim
   return DDQ_OK;
 }
 
+// one generate_experience (expgain.py:82-111) per step
 int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  if (c->a_env.games.empty()) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
   if (nsteps < 1) return fail(c, DDQ_EINVAL, "nsteps must be >= 1 (got %d)", nsteps);
   const double eps = actor_eps(iter_num);
+  ddq_ctx::Game& g = c->a_env.games[0];
+  std::vector<uint8_t> frames((size_t)kC * c->S * c->S);
   for (int i = 0; i < nsteps; ++i) {
-    const int rc = actor_step(c, eps);
+    // ExpGain.select_action: the coin first; the net is asked only when greedy
+    Stream rng{g.seed, g.draws};
+    int32_t act = 0;
+    if (rng.coin(eps)) {
+      act = (int32_t)rng.randrange(kA);
+    } else {
+      env_render(g.boards, c->a_env.row, c->a_env.col, c->S, frames.data());
+      const int rc = ddq_select_action(c, frames.data(), 1, &act);
+      if (rc != DDQ_OK) return rc;
+    }
+    const int reward = env_move(g, act);
+    // add_experience: the next state's frames, none after a game over
+    if (reward >= 0) env_render(g.boards, c->a_env.row, c->a_env.col, c->S, frames.data());
+    const int rc = ddq_replay_add(c, act, reward, reward < 0 ? nullptr : frames.data());
     if (rc != DDQ_OK) return rc;
   }
   return DDQ_OK;
@@ -1344,11 +1381,12 @@ int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
 
 int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
-  if (boards) memcpy(boards, c->a_boards, 400);
+  if (c->a_env.games.empty()) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  const ddq_ctx::Game& g = c->a_env.games[0];
+  if (boards) memcpy(boards, g.boards, 400);
   if (stats) {
-    stats[0] = c->a_steps; stats[1] = c->a_games; stats[2] = c->a_reward;
-    stats[3] = (int64_t)c->a_draws;
+    stats[0] = g.steps; stats[1] = g.games; stats[2] = g.reward;
+    stats[3] = (int64_t)g.draws;
   }
   return DDQ_OK;
 }
@@ -1366,26 +1404,10 @@ int ddq_eval_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards, const
   if (max_moves < 0) return fail(c, DDQ_EINVAL, "max_moves must be >= 0 (got %d)", max_moves);
   if (max_episodes < 1)
     return fail(c, DDQ_EINVAL, "max_episodes must be >= 1 (got %d)", max_episodes);
-  for (int i = 0; i < c->S; ++i)
-    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
-      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
-  for (int g = 0; g < ngames; ++g) {
-    const int8_t* b = init_boards + 100 * g;
-    std::vector<Cell> body;
-    if (!snake_body(b, &body) || body.size() < 2)
-      return fail(c, DDQ_EINVAL, "init_boards[%d]: snake cells must be the codes 0..k-1, k >= 2", g);
-    if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
-      return fail(c, DDQ_EINVAL, "init_boards[%d]: head and neck are not neighbours", g);
-  }
-  c->e_games.assign(ngames, ddq_ctx::EvalGame{});
-  for (int g = 0; g < ngames; ++g) {
-    ddq_ctx::EvalGame& eg = c->e_games[g];
-    eg.seed = mix64(mix64(seed) ^ (uint64_t)g);
-    memcpy(eg.init, init_boards + 100 * g, 100);
-    for (auto& b : eg.boards) memcpy(b, eg.init, 100);
-  }
-  c->e_row.assign(row_map, row_map + c->S);
-  c->e_col.assign(col_map, col_map + c->S);
+  const int rc = env_check(c, row_map, col_map, init_boards, ngames, false);
+  if (rc != DDQ_OK) return rc;
+  env_reset(&c->e_env, ngames, init_boards, row_map, col_map, c->S);
+  for (int g = 0; g < ngames; ++g) c->e_env.games[g].seed = game_seed(seed, g);
   c->e_eps = epsilon;
   c->e_max_moves = max_moves;
   c->e_max_ep = max_episodes;
@@ -1395,46 +1417,25 @@ int ddq_eval_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards, const
 
 int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (c->e_games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  if (c->e_env.games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
   if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
-  const int n = (int)c->e_games.size(), S = c->S;
-  const size_t fs = (size_t)kC * S * S;
-  std::vector<uint8_t> frames(n * fs);
-  std::vector<int32_t> greedy(n);
+  std::vector<int32_t> greedy;
   for (int m = 0; m < nmoves; ++m) {
-    // every game's state, idle ones included, in one batched forward
-    for (int g = 0; g < n; ++g)
-      for (int f = 0; f < kC; ++f)
-        for (int i = 0; i < S; ++i)
-          for (int j = 0; j < S; ++j) {
-            const int v = c->e_games[g].boards[f][c->e_row[i] * 10 + c->e_col[j]];
-            frames[g * fs + ((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
-          }
-    const int rc = ddq_select_action(c, frames.data(), n, greedy.data());
+    const int rc = env_greedy(c, c->e_env, &greedy);
     if (rc != DDQ_OK) return rc;
-    for (int g = 0; g < n; ++g) {
-      ddq_ctx::EvalGame& eg = c->e_games[g];
+    for (size_t g = 0; g < c->e_env.games.size(); ++g) {
+      ddq_ctx::EvalGame& eg = c->e_env.games[g];
       if ((int32_t)eg.log.size() >= 4 * c->e_max_ep) continue;   // its log is full: idle
-      auto next_draw = [&eg]() { return mix64(eg.seed ^ mix64(eg.draws++)); };
-      auto randrange = [&](uint64_t k) {
-        return (uint64_t)(((unsigned __int128)next_draw() * k) >> 64);
-      };
+      Stream rng{eg.seed, eg.draws};
       int act = greedy[g];
-      if (c->e_eps > 0.0 && (double)(next_draw() >> 11) * 0x1.0p-53 < c->e_eps)
-        act = (int)randrange(kA);
-      int8_t next[100];
-      const int reward = snake_play(eg.boards[3], act, next, randrange);
-      eg.reward += reward;
-      eg.score += reward;
+      if (c->e_eps > 0.0 && rng.coin(c->e_eps)) act = (int)rng.randrange(kA);   // greedy: no coin
       eg.moves += 1;
-      const bool over = reward < 0;
-      if (over || (c->e_max_moves > 0 && eg.moves >= c->e_max_moves)) {
-        eg.log.insert(eg.log.end(), {eg.move, eg.score, eg.moves, over ? 0 : 1});
+      const bool last = c->e_max_moves > 0 && eg.moves >= c->e_max_moves;
+      const int reward = env_move(eg, act, last);
+      eg.score += reward;
+      if (reward < 0 || last) {      // game over wins over max_moves on the same move
+        eg.log.insert(eg.log.end(), {eg.move, eg.score, eg.moves, reward < 0 ? 0 : 1});
         eg.score = eg.moves = 0;
-        for (auto& b : eg.boards) memcpy(b, eg.init, 100);   // reset_game
-      } else {
-        memmove(eg.boards[0], eg.boards[1], 300);
-        memcpy(eg.boards[3], next, 100);
       }
       eg.move += 1;
     }
@@ -1446,11 +1447,11 @@ int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
 int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, int8_t* boards,
                   uint64_t* draws) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (c->e_games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  if (c->e_env.games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
   int64_t eps = 0, rew = 0, dr = 0;
   const size_t per = 4 * (size_t)c->e_max_ep;
-  for (size_t g = 0; g < c->e_games.size(); ++g) {
-    const ddq_ctx::EvalGame& eg = c->e_games[g];
+  for (size_t g = 0; g < c->e_env.games.size(); ++g) {
+    const ddq_ctx::EvalGame& eg = c->e_env.games[g];
     eps += (int64_t)eg.log.size() / 4;
     rew += eg.reward;
     dr += (int64_t)eg.draws;
@@ -1473,81 +1474,44 @@ int ddq_actors_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards,
   if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
   if (ngames < 1 || ngames > c->B)
     return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, c->B);
-  for (int i = 0; i < c->S; ++i)
-    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
-      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
-  for (int g = 0; g < ngames; ++g) {
-    const int8_t* b = init_boards + 100 * g;
-    std::vector<Cell> body;
-    if (!snake_body(b, &body) || body.size() < 2)
-      return fail(c, DDQ_EINVAL, "init_boards[%d]: snake cells must be the codes 0..k-1, k >= 2", g);
-    if (std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) != 1)
-      return fail(c, DDQ_EINVAL, "init_boards[%d]: head and neck are not neighbours", g);
-  }
+  const int rc = env_check(c, row_map, col_map, init_boards, ngames, false);
+  if (rc != DDQ_OK) return rc;
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (ngames != c->lanes)
     return fail(c, DDQ_EINVAL, "ngames %d != the ring's %d lanes (ddq_replay_set_lanes)", ngames,
                 c->lanes);
-  c->p_games.assign(ngames, ddq_ctx::PoolGame{});
-  for (int g = 0; g < ngames; ++g) {
-    ddq_ctx::PoolGame& pg = c->p_games[g];
-    pg.seed = mix64(mix64(seed) ^ (uint64_t)g);
-    memcpy(pg.init, init_boards + 100 * g, 100);
-    for (auto& b : pg.boards) memcpy(b, pg.init, 100);
-  }
-  c->p_row.assign(row_map, row_map + c->S);
-  c->p_col.assign(col_map, col_map + c->S);
+  env_reset(&c->p_env, ngames, init_boards, row_map, col_map, c->S);
+  for (int g = 0; g < ngames; ++g) c->p_env.games[g].seed = game_seed(seed, g);
   return DDQ_OK;
 }
 
 int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (c->p_games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  if (c->p_env.games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
   if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
   const double eps = actor_eps(iter_num);
-  const int n = (int)c->p_games.size(), S = c->S;
-  const size_t fs = (size_t)kC * S * S;
-  std::vector<uint8_t> frames(n * fs);
-  std::vector<int32_t> greedy(n);
-  auto render = [&](const ddq_ctx::PoolGame& pg, uint8_t* out) {
-    for (int f = 0; f < kC; ++f)
-      for (int i = 0; i < S; ++i)
-        for (int j = 0; j < S; ++j) {
-          const int v = pg.boards[f][c->p_row[i] * 10 + c->p_col[j]];
-          out[((size_t)f * S + i) * S + j] = v == -1 ? 0 : (v == -2 ? 255 : 200);
-        }
-  };
+  const int n = (int)c->p_env.games.size();
+  const size_t fs = (size_t)kC * c->S * c->S;
+  std::vector<int32_t> greedy;
   for (int m = 0; m < nmoves; ++m) {
-    for (int g = 0; g < n; ++g) render(c->p_games[g], frames.data() + g * fs);
-    const int rc = ddq_select_action(c, frames.data(), n, greedy.data());
+    const int rc = env_greedy(c, c->p_env, &greedy);
     if (rc != DDQ_OK) return rc;
     const int64_t h = c->head;
     for (int g = 0; g < n; ++g) {
-      ddq_ctx::PoolGame& pg = c->p_games[g];
-      auto next_draw = [&pg]() { return mix64(pg.seed ^ mix64(pg.draws++)); };
-      auto randrange = [&](uint64_t k) {
-        return (uint64_t)(((unsigned __int128)next_draw() * k) >> 64);
-      };
+      ddq_ctx::Game& pg = c->p_env.games[g];
+      Stream rng{pg.seed, pg.draws};
       int act = greedy[g];
-      if ((double)(next_draw() >> 11) * 0x1.0p-53 < eps) act = (int)randrange(kA);   // always a coin
-      int8_t next[100];
-      const int reward = snake_play(pg.boards[3], act, next, randrange);
-      const bool over = reward < 0;
-      // add_experience into lane g's slot h
+      if (rng.coin(eps)) act = (int)rng.randrange(kA);   // always a coin
+      const int reward = env_move(pg, act);
+      // add_experience into lane g's slot h; after a game over the slot keeps
+      // its old frames
       const int64_t slot = (int64_t)g * c->lane_len + h;
       c->r_action[slot] = (uint8_t)act;
       c->r_reward[slot] = (int16_t)reward;
-      c->r_nonterm[slot] = over ? 0 : 1;
-      if (over) {   // the slot keeps its old frames
-        for (auto& b : pg.boards) memcpy(b, pg.init, 100);   // reset_game
-      } else {
-        memmove(pg.boards[0], pg.boards[1], 300);
-        memcpy(pg.boards[3], next, 100);
-        render(pg, c->r_state.data() + (size_t)slot * fs);
-      }
-      pg.steps += 1;
-      pg.games += over;
-      pg.reward += reward;
+      c->r_nonterm[slot] = reward < 0 ? 0 : 1;
+      if (reward >= 0)
+        env_render(pg.boards, c->p_env.row, c->p_env.col, c->S,
+                   c->r_state.data() + (size_t)slot * fs);
     }
     c->head = (h + 1) % c->lane_len;
     c->valid = std::min(c->lane_len, c->valid + 1);
@@ -1558,10 +1522,10 @@ int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
 
 int ddq_actors_read(ddq_ctx* c, int8_t* boards, int64_t* stats, int64_t* totals) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (c->p_games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  if (c->p_env.games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
   int64_t tot[4] = {0, 0, 0, 0};
-  for (size_t g = 0; g < c->p_games.size(); ++g) {
-    const ddq_ctx::PoolGame& pg = c->p_games[g];
+  for (size_t g = 0; g < c->p_env.games.size(); ++g) {
+    const ddq_ctx::Game& pg = c->p_env.games[g];
     const int64_t st[4] = {pg.steps, pg.games, pg.reward, (int64_t)pg.draws};
     for (int k = 0; k < 4; ++k) {
       tot[k] += st[k];

@@ -33,6 +33,16 @@ static thread_local std::string g_last_error;
 static constexpr int kMaxRanks = 64;
 static constexpr int64_t kShardPad = 64 * kMaxRanks;
 
+// The device buffers of one Snake environment: its games' state, the zoom maps
+// and the games' states as NHWC input of the forward.
+template <class Game>
+struct EnvBufs {
+  Game* games = nullptr;
+  uint8_t* maps = nullptr;
+  float* in = nullptr;
+  int n = 0;                       // games playing; 0: not created
+};
+
 struct ddq_ctx {
   int device = 0;
   ddq_net_desc desc{};
@@ -68,27 +78,18 @@ struct ddq_ctx {
   float *act_h4 = nullptr, *act_part = nullptr, *act_q = nullptr;
   __bf16 *act_p1s = nullptr, *act_p2s = nullptr;
   int32_t* act_out = nullptr;
-  // device-resident actor (ddq_actor_create): its state, zoom maps and NHWC input
-  ActorState* a_state = nullptr;
-  uint8_t* a_maps = nullptr;
-  float* a_in = nullptr;
-  bool actor = false;
-  // device-resident evaluator (ddq_eval_create): B games' state and input, the
-  // zoom maps, the per-game episode logs (grown on demand)
-  EvalGame* e_games = nullptr;
+  // device-resident Snake environments (env_create): the single actor
+  // (ddq_actor_create, one game), the evaluator (ddq_eval_create) and the actor
+  // pool (ddq_actors_create), each with room for B games
+  EnvBufs<ActorState> a_env, p_env;
+  EnvBufs<EvalGame> e_env;
+  // evaluator: the per-game episode logs (grown on demand)
   int32_t* e_log = nullptr;
   size_t e_log_cap = 0;            // int32 elements allocated
-  uint8_t* e_maps = nullptr;
-  float* e_in = nullptr;
-  int e_n = 0, e_max_moves = 0, e_max_ep = 0;   // e_n = 0: no evaluator
+  int e_max_moves = 0, e_max_ep = 0;
   uint64_t e_thresh = 0;
   int64_t e_moves = 0;             // lock-step moves enqueued since create
-  // device actor pool (ddq_actors_create): B games' state and input, the zoom
-  // maps, the ring's per-lane head / valid at create
-  ActorState* p_games = nullptr;
-  uint8_t* p_maps = nullptr;
-  float* p_in = nullptr;
-  int p_n = 0;                     // 0: no pool
+  // pool: the ring's per-lane head / valid at create, moves enqueued since
   int64_t p_h0 = 0, p_v0 = 0, p_moves = 0;
   // index log (ddq_index_log_enable)
   int32_t* log_buf = nullptr;
@@ -748,8 +749,8 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   c->lanes = lanes;
   c->lane_len = c->capacity / lanes;
   c->head = 0;
-  c->p_n = 0;                        // a pool or an actor belongs to the lanes it was
-  c->actor = false;                  // created on
+  c->p_env.n = 0;                    // a pool or an actor belongs to the lanes it was
+  c->a_env.n = 0;                    // created on
   char* m = reinterpret_cast<char*>(c->r_meta);
   HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lanes), &c->lanes, 4, hipMemcpyHostToDevice));
   HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lane_len), &c->lane_len, 8, hipMemcpyHostToDevice));
@@ -1387,13 +1388,36 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
   return DDQ_OK;
 }
 
-// ---------------- device-resident actor ----------------
+}  // extern "C"
+
+// ---------------- device-resident Snake environments ----------------
+// The single actor (ddq_actor_*), the policy evaluator (ddq_eval_*) and the
+// actor pool (ddq_actors_*): one kernel body under three roles (env.h), one
+// set-up path (env_create) and one lock-step move (env_move) here.
+
 // expgain.epsilon (expgain.py:55-60) in double, same operation order
 static double actor_epsilon(int64_t it) {
   const double lo = 0.1, hi = 1.0, limit = 50000.0;
   if (it > 50000) return lo;
   const int64_t left = std::max<int64_t>(50000 - it, 0);
   return lo + (hi - lo) * (double)left / limit;
+}
+
+// explore iff random() = (r >> 11) * 2^-53 < epsilon, i.e. (r >> 11) < ceil(epsilon * 2^53)
+static uint64_t env_thresh(double epsilon) {
+  return (uint64_t)std::ceil(epsilon * 9007199254740992.0);
+}
+
+static uint64_t env_mix64(uint64_t x) {   // splitmix64
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// seed of game g's stream: splitmix64(splitmix64(seed) ^ g) (ddq.actor.game_seed)
+static uint64_t env_game_seed(uint64_t seed, int g) {
+  return env_mix64(env_mix64(seed) ^ (uint64_t)g);
 }
 
 // init_board: snake cells are exactly the codes 0..k-1 (k >= 2), head and neck
@@ -1419,61 +1443,125 @@ static const char* actor_board_error(const int8_t* b) {
   return nullptr;
 }
 
-static ActorEnv actor_env(const ddq_ctx* c) {
-  ActorEnv e{};
-  e.state = c->a_state; e.maps = c->a_maps; e.actor_in = c->a_in; e.S = c->nb.S;
-  e.r_state = c->r_state; e.r_action = c->r_action; e.r_reward = c->r_reward;
-  e.r_nonterm = c->r_nonterm; e.meta = c->r_meta;
-  e.prio = c->prio_on ? c->d_prio : nullptr;
-  return e;
+// row_map / col_map checked and packed into the kernel's [2S] byte maps
+static int env_pack_maps(ddq_ctx* c, const int32_t* row_map, const int32_t* col_map,
+                         std::vector<uint8_t>* maps) {
+  const int S = c->nb.S;
+  maps->resize(2 * (size_t)S);
+  for (int i = 0; i < S; ++i) {
+    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
+      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
+    (*maps)[i] = (uint8_t)row_map[i];
+    (*maps)[S + i] = (uint8_t)col_map[i];
+  }
+  return DDQ_OK;
 }
+
+// n start boards; single: the one board of ddq_actor_create's init_board
+static int env_check_boards(ddq_ctx* c, const int8_t* boards, int n, bool single) {
+  for (int g = 0; g < n; ++g)
+    if (const char* why = actor_board_error(boards + 100 * g))
+      return single ? fail(c, DDQ_EINVAL, "init_board: %s", why)
+                    : fail(c, DDQ_EINVAL, "init_boards[%d]: %s", g, why);
+  return DDQ_OK;
+}
+
+// a game at create: zero counters, its stream's seed, five copies of its start board
+template <class Game>
+static Game env_new_game(uint64_t seed, const int8_t* board) {
+  Game g{};
+  g.seed = seed;
+  for (int f = 0; f < 5; ++f) memcpy(g.boards + f * 100, board, 100);
+  return g;
+}
+
+template <class Game>
+static EnvIO env_io(const ddq_ctx* c, const EnvBufs<Game>& b) {
+  return EnvIO{b.maps, b.in, c->nb.S, b.n};
+}
+
+static EnvRing env_ring(const ddq_ctx* c) {
+  return EnvRing{c->r_state,   c->r_action, c->r_reward,
+                 c->r_nonterm, c->r_meta,   c->prio_on ? c->d_prio : nullptr};
+}
+
+static ActorRole actor_role(const ddq_ctx* c) { return ActorRole{c->a_env.games, env_ring(c)}; }
+static EvalRole eval_role(const ddq_ctx* c) {
+  return EvalRole{c->e_env.games, c->e_log, c->e_max_moves, c->e_max_ep};
+}
+static PoolRole pool_role(const ddq_ctx* c) {
+  return PoolRole{c->p_env.games, env_ring(c), c->lane_len, c->p_h0, c->p_v0};
+}
+
+// (Re)create an environment: its buffers allocated once with room for `room`
+// games, the games and the maps filled, then the render-only launch (play = 0)
+// of the start states into b->in.  b->n stays 0 when any of it fails.  The
+// role's own ctx fields are set before the call.
+template <class Game, class Role>
+static int env_create(ddq_ctx* c, EnvBufs<Game>* b, int room, const std::vector<Game>& gs,
+                      const std::vector<uint8_t>& maps, Role (*role)(const ddq_ctx*),
+                      const char* what) {
+  const int S = c->nb.S;
+  b->n = 0;
+  if (!b->games) TRY(dalloc(c, &b->games, (size_t)room));
+  if (!b->maps) TRY(dalloc(c, &b->maps, maps.size()));
+  if (!b->in) TRY(dalloc(c, &b->in, (size_t)room * S * S * 4));
+  HIP_TRY(c, scopy(c, b->games, gs.data(), gs.size() * sizeof(Game), hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, b->maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
+  b->n = (int)gs.size();
+  const hipError_t e = launch_env(role(c), env_io(c, *b), c->act_q, 0, 0, c->stream);
+  if (e != hipSuccess) {
+    b->n = 0;
+    return fail(c, DDQ_EHIP, "%s render failed: %s", what, hipGetErrorString(e));
+  }
+  return DDQ_OK;
+}
+
+// One lock-step move: the Q forward of ddq_select_action at n = b.n on the
+// environment's own input (the act_* scratch is shared with ddq_select_action
+// and the other environments: calls on a ctx are serialised), then the
+// environment kernel.
+// (Eager enqueue on purpose: the move's launch arguments never change, so it
+// replays from a captured graph, and that was built and measured for the
+// evaluator -- 72.3 us per move against 73.1 eager at 64x64, N = 32, the device
+// being the limit at 19 us of host enqueue per move;
+// profiles/eval_rate_graph_ab.json.  Not faster beyond the noise, so it is
+// not kept.)
+template <class Role, class Game>
+static int env_move(ddq_ctx* c, const Role& r, const EnvBufs<Game>& b, uint64_t thresh) {
+  HIP_TRY(c, launch_act(c->nb, b.in, b.n, c->act_p3, c->act_h4, c->act_part, c->act_q, nullptr,
+                        c->act_p1s, c->act_p2s, c->stream));
+  HIP_TRY(c, launch_env(r, env_io(c, b), c->act_q, thresh, 1, c->stream));
+  return DDQ_OK;
+}
+
+extern "C" {
 
 int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_map,
                      const int32_t* col_map, uint64_t seed) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!init_board || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
-  const int S = c->nb.S;
-  std::vector<uint8_t> maps(2 * (size_t)S);
-  for (int i = 0; i < S; ++i) {
-    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
-      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
-    maps[i] = (uint8_t)row_map[i];
-    maps[S + i] = (uint8_t)col_map[i];
-  }
-  if (const char* why = actor_board_error(init_board))
-    return fail(c, DDQ_EINVAL, "init_board: %s", why);
+  std::vector<uint8_t> maps;
+  TRY(env_pack_maps(c, row_map, col_map, &maps));
+  TRY(env_check_boards(c, init_board, 1, true));
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (c->lanes > 1)
     return fail(c, DDQ_ESTATE, "ddq_actor_create on a laned ring (%d lanes): use ddq_actors_create",
                 c->lanes);
   TRY(set_dev(c));
-  if (!c->a_state) TRY(dalloc(c, &c->a_state, 1));
-  if (!c->a_maps) TRY(dalloc(c, &c->a_maps, maps.size()));
-  if (!c->a_in) TRY(dalloc(c, &c->a_in, (size_t)S * S * 4));
-  ActorState st{};
-  st.seed = seed;
-  for (int f = 0; f < 5; ++f) memcpy(st.boards + f * 100, init_board, 100);
-  HIP_TRY(c, hipMemcpyAsync(c->a_state, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, scopy(c, c->a_maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
-  HIP_TRY(c, launch_actor_env(actor_env(c), c->act_q, 0, 0, c->stream));   // render only
-  c->actor = true;
-  return DDQ_OK;
+  // the one game's stream takes the seed verbatim
+  const std::vector<ActorState> gs{env_new_game<ActorState>(seed, init_board)};
+  return env_create(c, &c->a_env, 1, gs, maps, actor_role, "actor");
 }
 
 int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  if (!c->a_env.n) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
   if (nsteps < 1) return fail(c, DDQ_EINVAL, "nsteps must be >= 1 (got %d)", nsteps);
   TRY(set_dev(c));
-  // explore iff random() = (r >> 11) * 2^-53 < epsilon, i.e. (r >> 11) < ceil(epsilon * 2^53)
-  const uint64_t thresh = (uint64_t)std::ceil(actor_epsilon(iter_num) * 9007199254740992.0);
-  const ActorEnv e = actor_env(c);
-  for (int i = 0; i < nsteps; ++i) {
-    // the forward of ddq_select_action with one state, on the actor's own input
-    HIP_TRY(c, launch_act(c->nb, c->a_in, 1, c->act_p3, c->act_h4, c->act_part, c->act_q,
-                          nullptr, c->act_p1s, c->act_p2s, c->stream));
-    HIP_TRY(c, launch_actor_env(e, c->act_q, thresh, 1, c->stream));
-  }
+  const uint64_t thresh = env_thresh(actor_epsilon(iter_num));
+  const ActorRole r = actor_role(c);
+  for (int i = 0; i < nsteps; ++i) TRY(env_move(c, r, c->a_env, thresh));
   // host mirror of the ring: one transition per step, as ddq_replay_add
   c->head = (c->head + nsteps) % c->capacity;
   c->valid = std::min(c->capacity, c->valid + nsteps);
@@ -1482,10 +1570,10 @@ int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
 
 int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->actor) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
+  if (!c->a_env.n) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
   TRY(set_dev(c));
   ActorState st;
-  HIP_TRY(c, scopy(c, &st, c->a_state, sizeof(st), hipMemcpyDeviceToHost));
+  HIP_TRY(c, scopy(c, &st, c->a_env.games, sizeof(st), hipMemcpyDeviceToHost));
   if (boards) memcpy(boards, st.boards, 400);
   if (stats) {
     stats[0] = st.steps; stats[1] = st.games; stats[2] = st.reward_sum;
@@ -1494,43 +1582,12 @@ int ddq_actor_read(ddq_ctx* c, int8_t* boards, int64_t* stats) {
   return DDQ_OK;
 }
 
-// ---------------- device-resident policy evaluation ----------------
-static EvalEnv eval_env(const ddq_ctx* c) {
-  EvalEnv e{};
-  e.games = c->e_games; e.log = c->e_log; e.maps = c->e_maps; e.eval_in = c->e_in;
-  e.S = c->nb.S; e.ngames = c->e_n; e.max_moves = c->e_max_moves; e.max_episodes = c->e_max_ep;
-  return e;
-}
-
-// one lock-step move: the Q forward of the games' states at n = ngames on the
-// evaluator's own input (the act_* scratch is shared with ddq_select_action and
-// the actor: calls on a ctx are serialised), then the environment kernel
-static int enqueue_eval_move(ddq_ctx* c) {
-  HIP_TRY(c, launch_act(c->nb, c->e_in, c->e_n, c->act_p3, c->act_h4, c->act_part, c->act_q,
-                        nullptr, c->act_p1s, c->act_p2s, c->stream));
-  HIP_TRY(c, launch_eval_env(eval_env(c), c->act_q, c->e_thresh, 1, c->stream));
-  return DDQ_OK;
-}
-
-// (Eager enqueue on purpose: the move's launch arguments never change, so it
-// replays from a captured graph, and that was built and measured -- 72.3 us
-// per move against 73.1 eager at 64x64, N = 32, the device being the limit at
-// 19 us of host enqueue per move; profiles/eval_rate_graph_ab.json.  Not
-// faster beyond the noise, so it is not kept.)
-// seed of game i's stream: splitmix64(splitmix64(seed) ^ i) (ddq.actor.game_seed)
-static uint64_t eval_mix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 int ddq_eval_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards, const int32_t* row_map,
                     const int32_t* col_map, uint64_t seed, double epsilon, int32_t max_moves,
                     int32_t max_episodes) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
-  const int S = c->nb.S, B = c->nb.B;
+  const int B = c->nb.B;
   if (ngames < 1 || ngames > B)
     return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, B);
   if (!(epsilon >= 0.0 && epsilon <= 1.0))
@@ -1538,63 +1595,37 @@ int ddq_eval_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards, const
   if (max_moves < 0) return fail(c, DDQ_EINVAL, "max_moves must be >= 0 (got %d)", max_moves);
   if (max_episodes < 1)
     return fail(c, DDQ_EINVAL, "max_episodes must be >= 1 (got %d)", max_episodes);
-  std::vector<uint8_t> maps(2 * (size_t)S);
-  for (int i = 0; i < S; ++i) {
-    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
-      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
-    maps[i] = (uint8_t)row_map[i];
-    maps[S + i] = (uint8_t)col_map[i];
-  }
-  for (int g = 0; g < ngames; ++g)
-    if (const char* why = actor_board_error(init_boards + 100 * g))
-      return fail(c, DDQ_EINVAL, "init_boards[%d]: %s", g, why);
+  std::vector<uint8_t> maps;
+  TRY(env_pack_maps(c, row_map, col_map, &maps));
+  TRY(env_check_boards(c, init_boards, ngames, false));
   TRY(set_dev(c));
-  c->e_n = 0;
-  if (!c->e_games) TRY(dalloc(c, &c->e_games, (size_t)B));
-  if (!c->e_maps) TRY(dalloc(c, &c->e_maps, maps.size()));
-  if (!c->e_in) TRY(dalloc(c, &c->e_in, (size_t)B * S * S * 4));
+  c->e_env.n = 0;                    // before the log it plays into is replaced
   const size_t nlog = (size_t)ngames * max_episodes * 4;
   if (nlog > c->e_log_cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->e_log) {
-      c->allocs.erase(std::find(c->allocs.begin(), c->allocs.end(), (void*)c->e_log));
-      hipFree(c->e_log);
-      c->e_log = nullptr;
-      c->e_log_cap = 0;
-    }
+    dfree(c, c->e_log);
+    c->e_log_cap = 0;
     TRY(dalloc(c, &c->e_log, nlog));
     c->e_log_cap = nlog;
   }
-  std::vector<EvalGame> gs(ngames);
-  const uint64_t base = eval_mix64(seed);
-  for (int g = 0; g < ngames; ++g) {
-    gs[g] = EvalGame{};
-    gs[g].seed = eval_mix64(base ^ (uint64_t)g);
-    for (int f = 0; f < 5; ++f) memcpy(gs[g].boards + f * 100, init_boards + 100 * g, 100);
-  }
   HIP_TRY(c, hipMemsetAsync(c->e_log, 0, nlog * sizeof(int32_t), c->stream));
-  HIP_TRY(c, scopy(c, c->e_games, gs.data(), gs.size() * sizeof(EvalGame), hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->e_maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
-  c->e_n = ngames;
   c->e_max_moves = max_moves;
   c->e_max_ep = max_episodes;
-  // explore iff random() = (r >> 11) * 2^-53 < epsilon; epsilon = 0: no coin at all
-  c->e_thresh = (uint64_t)std::ceil(epsilon * 9007199254740992.0);
+  c->e_thresh = env_thresh(epsilon);   // epsilon = 0: no coin at all
   c->e_moves = 0;
-  const hipError_t e = launch_eval_env(eval_env(c), c->act_q, 0, 0, c->stream);   // render only
-  if (e != hipSuccess) {
-    c->e_n = 0;
-    return fail(c, DDQ_EHIP, "eval render failed: %s", hipGetErrorString(e));
-  }
-  return DDQ_OK;
+  std::vector<EvalGame> gs(ngames);
+  for (int g = 0; g < ngames; ++g)
+    gs[g] = env_new_game<EvalGame>(env_game_seed(seed, g), init_boards + 100 * g);
+  return env_create(c, &c->e_env, B, gs, maps, eval_role, "eval");
 }
 
 int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->e_n) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  if (!c->e_env.n) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
   if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
   TRY(set_dev(c));
-  for (int i = 0; i < nmoves; ++i) TRY(enqueue_eval_move(c));
+  const EvalRole r = eval_role(c);
+  for (int i = 0; i < nmoves; ++i) TRY(env_move(c, r, c->e_env, c->e_thresh));
   c->e_moves += nmoves;
   return DDQ_OK;
 }
@@ -1602,11 +1633,12 @@ int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
 int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, int8_t* boards,
                   uint64_t* draws) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->e_n) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
+  if (!c->e_env.n) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
   TRY(set_dev(c));
-  const int n = c->e_n;
+  const int n = c->e_env.n;
   std::vector<EvalGame> gs(n);
-  HIP_TRY(c, scopy(c, gs.data(), c->e_games, gs.size() * sizeof(EvalGame), hipMemcpyDeviceToHost));
+  HIP_TRY(c, scopy(c, gs.data(), c->e_env.games, gs.size() * sizeof(EvalGame),
+                   hipMemcpyDeviceToHost));
   if (log)
     HIP_TRY(c, scopy(c, log, c->e_log, (size_t)n * c->e_max_ep * 4 * sizeof(int32_t),
                      hipMemcpyDeviceToHost));
@@ -1623,81 +1655,42 @@ int ddq_eval_read(ddq_ctx* c, int64_t* stats, int32_t* episodes, int32_t* log, i
   return DDQ_OK;
 }
 
-// ---------------- device actor pool ----------------
-static PoolEnv pool_env(const ddq_ctx* c) {
-  PoolEnv e{};
-  e.games = c->p_games; e.maps = c->p_maps; e.pool_in = c->p_in; e.S = c->nb.S;
-  e.ngames = c->p_n; e.lane_len = c->lane_len; e.h0 = c->p_h0; e.v0 = c->p_v0;
-  e.r_state = c->r_state; e.r_action = c->r_action; e.r_reward = c->r_reward;
-  e.r_nonterm = c->r_nonterm; e.meta = c->r_meta;
-  e.prio = c->prio_on ? c->d_prio : nullptr;
-  return e;
-}
-
 int ddq_actors_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards,
                       const int32_t* row_map, const int32_t* col_map, uint64_t seed) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!init_boards || !row_map || !col_map) return fail(c, DDQ_EINVAL, "null argument");
-  const int S = c->nb.S, B = c->nb.B;
+  const int B = c->nb.B;
   if (ngames < 1 || ngames > B)
     return fail(c, DDQ_EINVAL, "ngames must be in [1,B] (got %d, B = %d)", ngames, B);
-  std::vector<uint8_t> maps(2 * (size_t)S);
-  for (int i = 0; i < S; ++i) {
-    if (row_map[i] < 0 || row_map[i] >= 10 || col_map[i] < 0 || col_map[i] >= 10)
-      return fail(c, DDQ_EINVAL, "zoom map entry %d outside [0,10)", i);
-    maps[i] = (uint8_t)row_map[i];
-    maps[S + i] = (uint8_t)col_map[i];
-  }
-  for (int g = 0; g < ngames; ++g)
-    if (const char* why = actor_board_error(init_boards + 100 * g))
-      return fail(c, DDQ_EINVAL, "init_boards[%d]: %s", g, why);
+  std::vector<uint8_t> maps;
+  TRY(env_pack_maps(c, row_map, col_map, &maps));
+  TRY(env_check_boards(c, init_boards, ngames, false));
   if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (ngames != c->lanes)
     return fail(c, DDQ_EINVAL, "ngames %d != the ring's %d lanes (ddq_replay_set_lanes)", ngames,
                 c->lanes);
   TRY(set_dev(c));
-  c->p_n = 0;
-  if (!c->p_games) TRY(dalloc(c, &c->p_games, (size_t)B));
-  if (!c->p_maps) TRY(dalloc(c, &c->p_maps, maps.size()));
-  if (!c->p_in) TRY(dalloc(c, &c->p_in, (size_t)B * S * S * 4));
-  std::vector<ActorState> gs(ngames);
-  const uint64_t base = eval_mix64(seed);
-  for (int g = 0; g < ngames; ++g) {
-    gs[g] = ActorState{};
-    gs[g].seed = eval_mix64(base ^ (uint64_t)g);
-    for (int f = 0; f < 5; ++f) memcpy(gs[g].boards + f * 100, init_boards + 100 * g, 100);
-  }
-  HIP_TRY(c, scopy(c, c->p_games, gs.data(), gs.size() * sizeof(ActorState),
-                   hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->p_maps, maps.data(), maps.size(), hipMemcpyHostToDevice));
-  c->p_n = ngames;
+  // the games' slots come from the ring's per-lane head / valid now
   c->p_h0 = c->head;
   c->p_v0 = c->valid;
   c->p_moves = 0;
-  const hipError_t e = launch_pool_env(pool_env(c), c->act_q, 0, 0, c->stream);   // render only
-  if (e != hipSuccess) {
-    c->p_n = 0;
-    return fail(c, DDQ_EHIP, "pool render failed: %s", hipGetErrorString(e));
-  }
-  return DDQ_OK;
+  std::vector<ActorState> gs(ngames);
+  for (int g = 0; g < ngames; ++g)
+    gs[g] = env_new_game<ActorState>(env_game_seed(seed, g), init_boards + 100 * g);
+  return env_create(c, &c->p_env, B, gs, maps, pool_role, "pool");
 }
 
 int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->p_n) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  if (!c->p_env.n) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
   if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
   // the games' slots come from (h0, v0) and their own step counters
   if (c->head != (c->p_h0 + c->p_moves) % c->lane_len)
     return fail(c, DDQ_ESTATE, "the ring's head moved since ddq_actors_create: create the pool again");
   TRY(set_dev(c));
-  const uint64_t thresh = (uint64_t)std::ceil(actor_epsilon(iter_num) * 9007199254740992.0);
-  const PoolEnv e = pool_env(c);
-  for (int i = 0; i < nmoves; ++i) {
-    // the forward of ddq_select_action at n = ngames, on the pool's own input
-    HIP_TRY(c, launch_act(c->nb, c->p_in, c->p_n, c->act_p3, c->act_h4, c->act_part, c->act_q,
-                          nullptr, c->act_p1s, c->act_p2s, c->stream));
-    HIP_TRY(c, launch_pool_env(e, c->act_q, thresh, 1, c->stream));
-  }
+  const uint64_t thresh = env_thresh(actor_epsilon(iter_num));
+  const PoolRole r = pool_role(c);
+  for (int i = 0; i < nmoves; ++i) TRY(env_move(c, r, c->p_env, thresh));
   // host mirror of the ring: one transition per lane and move
   c->p_moves += nmoves;
   c->head = (c->head + nmoves) % c->lane_len;
@@ -1707,11 +1700,11 @@ int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
 
 int ddq_actors_read(ddq_ctx* c, int8_t* boards, int64_t* stats, int64_t* totals) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->p_n) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
+  if (!c->p_env.n) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
   TRY(set_dev(c));
-  const int n = c->p_n;
+  const int n = c->p_env.n;
   std::vector<ActorState> gs(n);
-  HIP_TRY(c, scopy(c, gs.data(), c->p_games, gs.size() * sizeof(ActorState),
+  HIP_TRY(c, scopy(c, gs.data(), c->p_env.games, gs.size() * sizeof(ActorState),
                    hipMemcpyDeviceToHost));
   int64_t tot[4] = {0, 0, 0, 0};
   for (int g = 0; g < n; ++g) {

@@ -27,7 +27,7 @@ ParamLayout make_layout(int S);
 //
 // Laned ring (ddq_replay_set_lanes): lanes > 1 contiguous lanes of lane_len =
 // capacity / lanes slots, lane g = slots [g lane_len, (g + 1) lane_len), each a
-// ring of its own.  Lock-step writers fill it (pool.h), so the lanes share one
+// ring of its own.  Lock-step writers fill it (env.h: PoolRole), so the lanes share one
 // head in [0, lane_len) and one valid in [0, lane_len]: head / valid are then
 // the per-lane values.  lanes 0 or 1: one ring, lane_len == capacity.
 constexpr int kNstepMax = 8;   // DDQ_NSTEP_MAX
@@ -267,37 +267,19 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
                       __bf16* pool2s, hipStream_t s,
                       void (*mark)(void*, const char*) = nullptr, void* mark_arg = nullptr);
-// Device-resident Snake actor (actor.h).  boards: the 4-frame history of 10x10
-// board codes [x*10+y] (SnakeGame.encode_state), oldest first, then init_board;
-// draws: position in the actor's RNG stream splitmix64(seed ^ splitmix64(k)).
+// Device-resident Snake environment (env.h): one kernel body, three roles.
+// ActorState: one acting game.  boards: the 4-frame history of 10x10 board
+// codes [x*10+y] (SnakeGame.encode_state), oldest first, then init_board;
+// draws: position in the game's RNG stream splitmix64(seed ^ splitmix64(k)).
 struct ActorState {
   uint64_t seed, draws;
   int64_t steps, games, reward_sum;
   int8_t boards[5 * 100];
   int8_t pad[4];
 };
-struct ActorEnv {
-  ActorState* state;
-  const uint8_t* maps;              // row_map[S] then col_map[S], entries in [0,10)
-  float* actor_in;                  // the state as f32 NHWC (S,S,4): the forward's input
-  int S;
-  uint8_t* r_state;
-  uint8_t* r_action;
-  int16_t* r_reward;
-  uint8_t* r_nonterm;
-  ReplayMeta* meta;
-  const PrioTree* prio;             // device copy of the tree; nullptr: prioritization off
-};
-// One workgroup: (play != 0) epsilon-greedy action from q[0..4) and the coin
-// against thresh = ceil(epsilon * 2^53), one game step, the transition into
-// ring slot meta->head, head / valid advanced; then the render of the next
-// state into that slot (not after a game over) and into actor_in.
-hipError_t launch_actor_env(const ActorEnv& e, const float* q, uint64_t thresh, int play,
-                            hipStream_t s);
-// Device-resident policy evaluation (eval.h): ngames independent Snake games in
-// lock step, one workgroup each.  EvalGame: one game's RNG stream (as the
-// actor's), its lock-step move counter, the records in its log, the running
-// episode's score / moves and its boards (4-frame history, then its start board).
+// EvalGame: one evaluated game's RNG stream (as the actor's), its lock-step move
+// counter, the records in its log, the running episode's score / moves and its
+// boards (4-frame history, then its start board).
 struct EvalGame {
   uint64_t seed, draws;
   int64_t reward_sum;
@@ -305,44 +287,63 @@ struct EvalGame {
   int8_t boards[5 * 100];
   int8_t pad[4];
 };
-struct EvalEnv {
-  EvalGame* games;                  // [ngames]
-  int32_t* log;                     // [ngames][max_episodes][4]: end_move, score, moves, ended_by
-  const uint8_t* maps;              // row_map[S] then col_map[S]
-  float* eval_in;                   // [ngames] states as f32 NHWC (S,S,4): the forward's input
-  int S, ngames, max_moves, max_episodes;
-};
-// ngames workgroups: (play != 0) game g's action from q[4g..4g+4) (the coin
-// only when thresh > 0), one game step, the episode record when the game is
-// over or max_moves is reached, then the render of its next state into its
-// slice of eval_in.  A game whose log is full does nothing.
-hipError_t launch_eval_env(const EvalEnv& e, const float* q, uint64_t thresh, int play,
-                           hipStream_t s);
-// Device actor pool (pool.h): ngames == lanes Snake games in lock step, one
-// workgroup each, game g adding into lane g of a laned ring.  A game's state is
-// the actor's (ActorState); h0 / v0: the ring's per-lane head / valid when the
-// pool was created (launch constants: a game's slot comes from them and its
-// own step counter).
-struct PoolEnv {
-  ActorState* games;                // [ngames]
-  const uint8_t* maps;              // row_map[S] then col_map[S]
-  float* pool_in;                   // [ngames] states as f32 NHWC (S,S,4): the forward's input
+// What every role's launch has: ngames workgroups, game g reading q[4g..4g+4)
+// and rendering its next state into slice g of `in`.
+struct EnvIO {
+  const uint8_t* maps;              // row_map[S] then col_map[S], entries in [0,10)
+  float* in;                        // [ngames] states as f32 NHWC (S,S,4): the forward's input
   int S, ngames;
-  int64_t lane_len, h0, v0;
-  uint8_t* r_state;
-  uint8_t* r_action;
-  int16_t* r_reward;
-  uint8_t* r_nonterm;
+};
+// the replay ring an acting role adds into
+struct EnvRing {
+  uint8_t* state;
+  uint8_t* action;
+  int16_t* reward;
+  uint8_t* nonterm;
   ReplayMeta* meta;
   const PrioTree* prio;             // device copy of the tree; nullptr: prioritization off
 };
-// ngames workgroups: (play != 0) game g's epsilon-greedy action from
-// q[4g..4g+4) and the coin against thresh, one game step, the transition into
-// slot g lane_len + (h0 + steps_g) mod lane_len, the render of its next state
-// into that slot (not after a game over) and into its slice of pool_in;
+// A role is the launch argument that says what its games differ in: the state
+// type, whether the coin is drawn even at thresh == 0, whether a ring slot is
+// rendered, and (env.h) env_idle / env_commit.
+// Single actor (ddq_actor_*): one game, the transition into ring slot
+// meta->head read on the device, head / valid advanced there.
+struct ActorRole {
+  using Game = ActorState;
+  static constexpr bool kCoinAlways = true, kRing = true;
+  ActorState* games;
+  EnvRing ring;
+};
+// Actor pool (ddq_actors_*): ngames == lanes games, game g adding into lane g of
+// a laned ring at slot g lane_len + (h0 + steps_g) mod lane_len; h0 / v0: the
+// ring's per-lane head / valid when the pool was created (launch constants);
 // workgroup 0 publishes the per-lane head / valid.
-hipError_t launch_pool_env(const PoolEnv& e, const float* q, uint64_t thresh, int play,
-                           hipStream_t s);
+struct PoolRole {
+  using Game = ActorState;
+  static constexpr bool kCoinAlways = true, kRing = true;
+  ActorState* games;
+  EnvRing ring;
+  int64_t lane_len, h0, v0;
+};
+// Policy evaluation (ddq_eval_*): the episode record when the game is over or
+// max_moves is reached; a game whose log is full does nothing.
+struct EvalRole {
+  using Game = EvalGame;
+  static constexpr bool kCoinAlways = false, kRing = false;
+  EvalGame* games;                  // [ngames]
+  int32_t* log;                     // [ngames][max_episodes][4]: end_move, score, moves, ended_by
+  int max_moves, max_episodes;
+};
+// ngames workgroups of the role's kernel: (play != 0) game g's epsilon-greedy
+// action from its row of q and the coin against thresh = ceil(epsilon * 2^53),
+// one game step, the role's commit; then the render of its next state into the
+// ring slot (ring roles, not after a game over) and into its slice of io.in.
+hipError_t launch_env(const ActorRole& r, const EnvIO& io, const float* q, uint64_t thresh,
+                      int play, hipStream_t s);
+hipError_t launch_env(const EvalRole& r, const EnvIO& io, const float* q, uint64_t thresh, int play,
+                      hipStream_t s);
+hipError_t launch_env(const PoolRole& r, const EnvIO& io, const float* q, uint64_t thresh, int play,
+                      hipStream_t s);
 // Device-resident training monitor (monitor.h).  MonitorRecord is
 // ddq_monitor_record (include/ddq_hip.h), field for field.
 struct MonitorRecord {

@@ -2512,11 +2512,8 @@ __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
 
 // prioritized replay: the writers' rule (the tree's own kernels: prio.hip)
 #include "prio.h"
-// the device-resident actor's environment step (after launch_act's forward)
-#include "actor.h"
-// the device-resident evaluator's environment step: one game per workgroup
-#include "eval.h"
-// the actor pool's environment step: one game per workgroup, one ring lane each
-#include "pool.h"
+// the Snake environment step after launch_act's forward, one game per workgroup:
+// the device-resident actor, the actor pool (one ring lane each), the evaluator
+#include "env.h"
 // the training monitor's reduction: one workgroup per chunk, one record
 #include "monitor.h"

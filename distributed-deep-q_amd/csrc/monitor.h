@@ -2,7 +2,7 @@
 // reference's NetLogger.write appends after every step (netutils.py:72-96) --
 // the loss, the RMS of every blob's gradient and of every blob's parameters --
 // taken by ONE launch and appended to a device ring of MonitorRecord.  Included
-// by kernels.hip after eval.h.
+// by kernels.hip after env.h.
 //
 // One workgroup per chunk of the host-built chunk table (at most kMonChunk
 // floats of one blob of theta_Q, theta_P or the gradient buffer): every element

@@ -1,7 +1,7 @@
 // Proportional prioritized replay on the device (ddq_replay_set_priority,
 // include/ddq_hip.h): the device helpers of the sum tree of kernels.h
 // (PrioTree) -- the leaf update and the writer rule the ring's writers
-// (ddq_replay_add, actor.h, pool.h) apply.  The tree's own kernels (rebuild,
+// (ddq_replay_add, env.h's ring roles) apply.  The tree's own kernels (rebuild,
 // draw, commit) are a translation unit of their own, prio.hip, so that the code
 // object of kernels.hip keeps the layout it has without them.
 //
