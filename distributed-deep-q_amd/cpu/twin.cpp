@@ -81,6 +81,11 @@ struct ddq_ctx {
   std::vector<float> theta[2], grad, opt;
   int first = 1;                 // the next apply is the first since a reset
   int64_t iter = 0;
+  // Adam (ddq_set_adam): opt holds m, opt2 v; gnorm: the last pre-clip norm
+  bool adam_on = false;
+  ddq_adam_cfg adam{0.f, 0.f, 0.f, 0.f};
+  std::vector<float> opt2;
+  float gnorm = 0.f;
   // minibatch (Caffe shapes)
   std::vector<float> state, next_state, action, reward, nonterm;
   std::vector<int32_t> idx;
@@ -1132,10 +1137,12 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_sa", c->q_sa.data(), c->B},         {"P_sa", c->p_sa.data(), c->B},
       {"target_Q_sa", c->target.data(), c->B}, {"loss", &c->loss, 1},
       {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B},
-      {"is_weight", c->isw.data(), c->B}};
+      {"is_weight", c->isw.data(), c->B},       {"grad_norm", &c->gnorm, 1}};
   for (auto& e : t)
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
+      if (!strcmp(name, "grad_norm") && !(c->adam_on && c->adam.max_grad_norm > 0.f))
+        return fail(c, DDQ_ESTATE, "blob grad_norm exists while Adam's gradient clipping is on");
       if (!strcmp(name, "is_weight") && !c->prio_on)
         return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       if (!strcmp(name, "Qn_out") && c->obj.target != DDQ_TARGET_DOUBLE)
@@ -1537,11 +1544,86 @@ int ddq_actors_read(ddq_ctx* c, int8_t* boards, int64_t* stats, int64_t* totals)
   return DDQ_OK;
 }
 
+// ---- Adam with global-norm clipping (include/ddq_hip.h; csrc/adam.h on the device) ----
+// (-ffp-contract=off: every operation rounds on its own, as the kernel's)
+static int adam_apply(ddq_ctx* c, float lr) {
+  const ddq_adam_cfg& a = c->adam;
+  const int64_t n = c->L.total;
+  c->iter++;                     // the bookkeeping first: t counts this update
+  const double t = (double)c->iter;
+  const float omb1 = (float)(1.0 - (double)a.beta1), omb2 = (float)(1.0 - (double)a.beta2);
+  const float c1 = (float)(1.0 - std::pow((double)a.beta1, t));
+  const float c2 = (float)(1.0 - std::pow((double)a.beta2, t));
+  const bool clip = a.max_grad_norm > 0.f;
+  float s = 1.0f;
+  if (clip) {
+    double tot = 0.0;
+    for (int64_t i = 0; i < n; ++i) tot += (double)c->grad[i] * (double)c->grad[i];
+    const float nrm = (float)std::sqrt(tot);
+    s = nrm > a.max_grad_norm ? a.max_grad_norm / nrm : 1.0f;
+    c->gnorm = nrm;
+  }
+  float* th = c->theta[0].data();
+  float* m = c->opt.data();
+  float* v = c->opt2.data();
+  if (c->first) {                // first apply after a reset: m = v = 0
+    std::fill(c->opt.begin(), c->opt.end(), 0.f);
+    std::fill(c->opt2.begin(), c->opt2.end(), 0.f);
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const float g = clip ? s * c->grad[i] : c->grad[i];
+    m[i] = a.beta1 * m[i] + omb1 * g;
+    v[i] = a.beta2 * v[i] + omb2 * (g * g);
+    th[i] = th[i] - (lr * (m[i] / c1)) / (sqrtf(v[i] / c2) + a.eps);
+  }
+  c->first = 0;
+  return DDQ_OK;
+}
+
+int ddq_set_adam(ddq_ctx* c, const ddq_adam_cfg* a) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!a) return fail(c, DDQ_EINVAL, "null adam cfg");
+  if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f))
+    return fail(c, DDQ_EINVAL, "beta1 and beta2 must be in [0, 1) (got %g, %g)", (double)a->beta1,
+                (double)a->beta2);
+  if (!(std::isfinite(a->eps) && a->eps > 0.f))
+    return fail(c, DDQ_EINVAL, "eps must be finite and > 0 (got %g)", (double)a->eps);
+  if (!(std::isfinite(a->max_grad_norm) && a->max_grad_norm >= 0.f))
+    return fail(c, DDQ_EINVAL, "max_grad_norm must be 0 (off) or finite and > 0 (got %g)",
+                (double)a->max_grad_norm);
+  if (!c->adam_on) c->opt2.assign(c->opt.size(), 0.f);
+  c->adam_on = true;
+  c->adam = *a;
+  return DDQ_OK;
+}
+
+int ddq_get_adam(const ddq_ctx* c, ddq_adam_cfg* a) {
+  if (!c || !a) return fail(nullptr, DDQ_EINVAL, "null argument");
+  if (!c->adam_on) return fail(nullptr, DDQ_ESTATE, "ddq_get_adam before ddq_set_adam");
+  *a = c->adam;
+  return DDQ_OK;
+}
+
+int ddq_adam_state(ddq_ctx* c, float* m, float* v, int64_t n, int64_t* t) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->adam_on) return fail(c, DDQ_ESTATE, "ddq_adam_state before ddq_set_adam");
+  if ((m || v) && n != c->L.total) return fail(c, DDQ_EINVAL, "size mismatch");
+  if (m) std::copy(c->opt.begin(), c->opt.begin() + n, m);
+  if (v) std::copy(c->opt2.begin(), c->opt2.begin() + n, v);
+  if (t) *t = c->iter;
+  return DDQ_OK;
+}
+
 // ---- apply (server.py:49-124) ----
 int ddq_apply_async(ddq_ctx* c, const ddq_update_cfg* u) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!u) return fail(c, DDQ_EINVAL, "null update cfg");
-  if (u->rule < 0 || u->rule > 3) return fail(c, DDQ_EINVAL, "unknown update rule %d", u->rule);
+  if (u->rule < 0 || u->rule > DDQ_RULE_ADAM)
+    return fail(c, DDQ_EINVAL, "unknown update rule %d", u->rule);
+  if (u->rule == DDQ_RULE_ADAM) {
+    if (!c->adam_on) return fail(c, DDQ_ESTATE, "DDQ_RULE_ADAM before ddq_set_adam");
+    return adam_apply(c, u->lr);
+  }
   const Layout& L = c->L;
   const bool first = c->first != 0;
   float* th = c->theta[0].data();
@@ -1564,6 +1646,7 @@ int ddq_apply(ddq_ctx* c, const ddq_update_cfg* u) { return ddq_apply_async(c, u
 int ddq_reset_optimizer(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   std::fill(c->opt.begin(), c->opt.end(), 0.f);
+  std::fill(c->opt2.begin(), c->opt2.end(), 0.f);
   c->first = 1;
   c->iter = 0;
   c->steps = 0;

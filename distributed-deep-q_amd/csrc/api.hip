@@ -72,6 +72,7 @@ struct ddq_ctx {
   uint32_t* pset_q = nullptr;
   int32_t pset_cap = 0;
   bool idx_bound = false;          // nb.idx holds the bound minibatch's slots
+  bool adam_on = false;            // ddq_set_adam was called: nb.opt2 / gn_part / gnorm exist
   // acting scratch
   uint8_t* act_u8 = nullptr;
   float *act_in = nullptr, *act_p3 = nullptr;
@@ -1341,10 +1342,12 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_sa", c->nb.q_sa, B},         {"P_sa", c->nb.p_sa, B},
       {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1},
       {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B},
-      {"is_weight", c->nb.isw, B}};
+      {"is_weight", c->nb.isw, B},       {"grad_norm", c->nb.gnorm, 1}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
+      if (!strcmp(name, "grad_norm") && !(c->adam_on && c->nb.adam_clip > 0.f))
+        return fail(c, DDQ_ESTATE, "blob grad_norm exists while Adam's gradient clipping is on");
       if (!strcmp(name, "Qn_out") && c->nb.obj_target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
       if (!strcmp(name, "is_weight") && !c->nb.isw)
@@ -1722,7 +1725,27 @@ int ddq_actors_read(ddq_ctx* c, int8_t* boards, int64_t* stats, int64_t* totals)
 // ---------------- apply ----------------
 static int check_cfg(ddq_ctx* c, const ddq_update_cfg* u) {
   if (!u) return fail(c, DDQ_EINVAL, "null update cfg");
-  if (u->rule < 0 || u->rule > 3) return fail(c, DDQ_EINVAL, "unknown update rule %d", u->rule);
+  if (u->rule < 0 || u->rule > DDQ_RULE_ADAM)
+    return fail(c, DDQ_EINVAL, "unknown update rule %d", u->rule);
+  if (u->rule == DDQ_RULE_ADAM && !c->adam_on)
+    return fail(c, DDQ_ESTATE, "DDQ_RULE_ADAM before ddq_set_adam");
+  return DDQ_OK;
+}
+
+// The apply launch of one update (every caller of launch_apply).  Adam with
+// clipping on: the gradient-norm launch first, over the buffer the apply reads
+// (under all-reduce: the summed gradient).
+static int enqueue_apply(ddq_ctx* c, const NetBuffers& nb, const ddq_update_cfg& u, int period,
+                         bool booked, const Prefetch* pf = nullptr,
+                         void (*mark)(void*, const char*) = nullptr, void* marg = nullptr) {
+  const bool adam = u.rule == DDQ_RULE_ADAM;
+  if (adam && nb.adam_clip > 0.f) {
+    if (mark) mark(marg, "grad_norm");
+    HIP_TRY(c, launch_grad_norm(nb, c->stream));
+  }
+  if (mark) mark(marg, adam ? "adam_apply" : "apply");
+  HIP_TRY(c, launch_apply(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay, period,
+                          booked, c->stream, pf));
   return DDQ_OK;
 }
 
@@ -1730,9 +1753,56 @@ int ddq_apply_async(ddq_ctx* c, const ddq_update_cfg* u) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(check_cfg(c, u));
   TRY(set_dev(c));
-  HIP_TRY(c, launch_apply(c->nb, u->rule, u->lr, u->decay, u->eps, u->momentum, u->weight_decay,
-                          0, false, c->stream));
+  TRY(enqueue_apply(c, c->nb, *u, 0, false));
   c->applied++;
+  return DDQ_OK;
+}
+
+// ---------------- Adam ----------------
+int ddq_set_adam(ddq_ctx* c, const ddq_adam_cfg* a) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!a) return fail(c, DDQ_EINVAL, "null adam cfg");
+  if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f))
+    return fail(c, DDQ_EINVAL, "beta1 and beta2 must be in [0, 1) (got %g, %g)", (double)a->beta1,
+                (double)a->beta2);
+  if (!(std::isfinite(a->eps) && a->eps > 0.f))
+    return fail(c, DDQ_EINVAL, "eps must be finite and > 0 (got %g)", (double)a->eps);
+  if (!(std::isfinite(a->max_grad_norm) && a->max_grad_norm >= 0.f))
+    return fail(c, DDQ_EINVAL, "max_grad_norm must be 0 (off) or finite and > 0 (got %g)",
+                (double)a->max_grad_norm);
+  if (c->async_on)
+    return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx");
+  TRY(set_dev(c));
+  NetBuffers& nb = c->nb;
+  if (!c->adam_on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!nb.opt2) TRY(dalloc(c, &nb.opt2, (size_t)nb.L.total + kShardPad));
+    if (!nb.gn_part) TRY(dalloc(c, &nb.gn_part, (size_t)kGnBlocks));
+    if (!nb.gnorm) TRY(dalloc(c, &nb.gnorm, 1));
+    c->adam_on = true;
+  }
+  invalidate_graph(c);   // captured steps hold the constants as launch arguments
+  nb.adam_beta1 = a->beta1; nb.adam_beta2 = a->beta2;
+  nb.adam_eps = a->eps; nb.adam_clip = a->max_grad_norm;
+  return DDQ_OK;
+}
+
+int ddq_get_adam(const ddq_ctx* c, ddq_adam_cfg* a) {
+  if (!c || !a) return fail(nullptr, DDQ_EINVAL, "null argument");
+  if (!c->adam_on) return fail(nullptr, DDQ_ESTATE, "ddq_get_adam before ddq_set_adam");
+  *a = ddq_adam_cfg{c->nb.adam_beta1, c->nb.adam_beta2, c->nb.adam_eps, c->nb.adam_clip};
+  return DDQ_OK;
+}
+
+int ddq_adam_state(ddq_ctx* c, float* m, float* v, int64_t n, int64_t* t) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->adam_on) return fail(c, DDQ_ESTATE, "ddq_adam_state before ddq_set_adam");
+  if ((m || v) && n != c->nb.L.total) return fail(c, DDQ_EINVAL, "size mismatch");
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (m) TRY(copy_out(c, m, c->nb.opt, n, 0));
+  if (v) TRY(copy_out(c, v, c->nb.opt2, n, 0));
+  if (t) HIP_TRY(c, scopy(c, t, c->nb.iter, 8, hipMemcpyDeviceToHost));
   return DDQ_OK;
 }
 
@@ -1746,6 +1816,7 @@ int ddq_reset_optimizer(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(set_dev(c));
   HIP_TRY(c, hipMemsetAsync(c->nb.opt, 0, c->nb.L.total * 4, c->stream));
+  if (c->nb.opt2) HIP_TRY(c, hipMemsetAsync(c->nb.opt2, 0, c->nb.L.total * 4, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->nb.opt_init, 0, 4, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->nb.iter, 0, 8, c->stream));
   c->applied = 0;
@@ -1883,9 +1954,13 @@ static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void
     if (mark) mark(marg, "prio_commit");
     HIP_TRY(c, launch_prio_commit_draw(nb, bump, prio_next, prio_seed, c->stream));
   }
-  hipError_t e = nb.small ? launch_small_bwd(nb, c->stream, mark, marg, book >= 0, book, bump,
+  // the draw counter advances once per step: without the fused apply the slab
+  // reduce's bookkeeping would advance it (apply_book's bump), but on a
+  // prioritized step the commit launch above already has (an Adam step)
+  ReplayMeta* bbump = (nb.prio.leaf && !nb.fa.on) ? nullptr : bump;
+  hipError_t e = nb.small ? launch_small_bwd(nb, c->stream, mark, marg, book >= 0, book, bbump,
                                              overlap ? fc4_bucket_start : nullptr, c, pf)
-                          : launch_backward(nb, c->stream, mark, marg, book >= 0, book, bump,
+                          : launch_backward(nb, c->stream, mark, marg, book >= 0, book, bbump,
                                             overlap ? fc4_bucket_start : nullptr, c, pf);
   if (e != hipSuccess && !c->comm_err.empty()) {
     std::string m = c->comm_err;
@@ -1944,10 +2019,7 @@ static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const Net
                                   c->stream));
       }
     }
-    if (mark) mark(marg, "apply");
-    HIP_TRY(c, launch_apply(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
-                            cfg->target_period, true, c->stream, pf));
-    return DDQ_OK;
+    return enqueue_apply(c, nb, u, cfg->target_period, true, pf, mark, marg);
   }
   const int W = c->nranks;
   const size_t len = (size_t)c->shard_len;
@@ -2004,11 +2076,18 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
   nb.book_inc = step_inc(c, cfg);
   // exchange-free steps: fc4's weight update rides on the slab-reduce launch
   const int ex = has_exchange(c, cfg) ? cfg->exchange : DDQ_EXCHANGE_NONE;
-  const bool ar_overlap = ex == DDQ_EXCHANGE_ALLREDUCE && cfg->overlap && c->comm;
+  // (an Adam step's all-reduce is one call on the ctx stream: cfg->overlap is
+  // for the fused fc4 apply, which Adam does not take)
+  const bool ar_overlap = ex == DDQ_EXCHANGE_ALLREDUCE && cfg->overlap && c->comm &&
+                          cfg->update.rule != DDQ_RULE_ADAM;
   // (deepq16: fc4's parameters are final and applied inside the fc4 chain,
   // K2, before any bucket could be summed: the overlapped all-reduce takes the
   // plain apply launch there)
-  if ((ex == DDQ_EXCHANGE_NONE || (ar_overlap && !nb.small)) && fused_apply_ok(nb.L)) {
+  // (Adam keeps two state words: its update is a launch of its own after the
+  // gradient launches, the sequencing of an exchanged step; fc4's gradient is
+  // then stored whatever DDQ_STEP_NO_GRAD_STORE says)
+  const bool adam = cfg->update.rule == DDQ_RULE_ADAM;
+  if (!adam && (ex == DDQ_EXCHANGE_NONE || (ar_overlap && !nb.small)) && fused_apply_ok(nb.L)) {
     const ddq_update_cfg& u = cfg->update;
     nb.fa.on = 1;
     nb.fa.ext = ar_overlap ? 1 : 0;
@@ -2024,14 +2103,19 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
   // for every layout make_layout builds; and every caller of a prioritized step
   // passes the draw counter (B <= 256, no async exchange).  Were one of these
   // ever to change, the step would commit with no counter to advance: stop.
-  if (nb.prio.leaf && (!nb.fa.on || !bump))
+  // An Adam step is the one prioritized step without the fused apply: its commit
+  // launch advances the counter (and draws the next set), the slab reduce's
+  // bookkeeping then does not (enqueue_fwd_bwd_x), and the apply launch's
+  // prefetch blocks gather the set the commit launch drew (predrawn).
+  if (nb.prio.leaf && (!(nb.fa.on || adam) || !bump))
     return fail(c, DDQ_ESTATE, "internal: a prioritized step without the fused apply or the draw "
                                "counter");
   if (pre && fused_prefetch(c, cfg)) {
     // the step's bookkeeping advances the draw counter (bump) before the apply
     // launch draws the next minibatch with it
-    const Prefetch pf = make_prefetch(*pre, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                      c->r_meta, cfg->seed);
+    Prefetch pf = make_prefetch(*pre, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
+                                c->r_meta, cfg->seed);
+    if (nb.prio.leaf && !nb.fa.on) pf.predrawn = 1;
     // fused apply: the slab-reduce launch carries the draw + gather too
     TRY(enqueue_fwd_bwd_x(c, nb, mark, marg, cfg->target_period > 0 ? cfg->target_period : 0,
                           c->r_meta, ar_overlap, nb.fa.on ? &pf : nullptr, pre, cfg->seed));
@@ -2129,6 +2213,11 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (cfg->exchange != DDQ_EXCHANGE_NONE && c->nranks > 1 && !c->comm && !c->local)
     return fail(c, DDQ_ESTATE, "no communicator");
   if (has_exchange(c, cfg)) TRY(prio_refuse(c, "an exchanged step"));
+  if (cfg->update.rule == DDQ_RULE_ADAM && has_exchange(c, cfg) &&
+      cfg->exchange != DDQ_EXCHANGE_ALLREDUCE)
+    return fail(c, DDQ_EINVAL, "DDQ_RULE_ADAM runs without an exchange or under "
+                               "DDQ_EXCHANGE_ALLREDUCE only (exchange %d shards one state buffer)",
+                cfg->exchange);
   return DDQ_OK;
 }
 
@@ -2362,6 +2451,8 @@ int ddq_async_begin(ddq_ctx* c, const ddq_step_cfg* cfg) {
   TRY(prio_refuse(c, "ddq_async_begin"));
   TRY(check_step(c, cfg));
   if (cfg->exchange != DDQ_EXCHANGE_ASYNC) return fail(c, DDQ_EINVAL, "cfg exchange is not async");
+  if (cfg->update.rule == DDQ_RULE_ADAM)
+    return fail(c, DDQ_EINVAL, "the async exchange does not take DDQ_RULE_ADAM");
   if (c->mon.ring && c->mon_period > 0)
     return fail(c, DDQ_ESTATE, "the async exchange takes no monitor records: disable the monitor or "
                                "enable it with period 0");
@@ -2984,8 +3075,7 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
       const NetBuffers& nb = c->nb;
       const int64_t len = c->shard_len;
       if (ex == DDQ_EXCHANGE_NONE) {
-        HIP_TRY(c, launch_apply(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
-                                cfg->target_period, true, c->stream));
+        TRY(enqueue_apply(c, nb, u, cfg->target_period, true));
         continue;
       }
       if (ex == DDQ_EXCHANGE_ALLREDUCE) {   // gather every gradient first (summed below)
@@ -3012,8 +3102,7 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
         TRY(set_dev(c));
         TRY(wait_all(c));
         HIP_TRY(c, launch_sum_slices(c->nb.grad, c->gstage, W, P, P, c->stream));
-        HIP_TRY(c, launch_apply(c->nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
-                                cfg->target_period, true, c->stream));
+        TRY(enqueue_apply(c, c->nb, u, cfg->target_period, true));
       }
     }
     if (ex == DDQ_EXCHANGE_SHARDED || ex == DDQ_EXCHANGE_SERVER) {

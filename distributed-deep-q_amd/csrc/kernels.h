@@ -152,6 +152,12 @@ struct NetBuffers {
   // them there and scales dQ and the loss terms by them); prio: the tree
   float* isw = nullptr;
   PrioTree prio{};
+  // Adam (ddq_set_adam, adam.h): opt holds the first moment, opt2 the second;
+  // gn_part: the gradient-norm launch's partials; gnorm: the last pre-clip norm
+  float* opt2 = nullptr;
+  double* gn_part = nullptr;
+  float* gnorm = nullptr;
+  float adam_beta1 = 0.f, adam_beta2 = 0.f, adam_eps = 0.f, adam_clip = 0.f;
   // deepq16 step (small.h, small_bwd.h): fc4 chain partials and its fan-in words
   int small;                        // S == 16, B <= 256: the four-launch step
   int small_G = 1;                  // its fc4 chain's image chunks (B > 32: ceil(B / 32))
@@ -230,6 +236,13 @@ Prefetch make_prefetch(const NetBuffers& next, const uint8_t* st, const uint8_t*
 hipError_t launch_apply(const NetBuffers& nb, int rule, float lr, float decay, float eps,
                         float momentum, float wd, int period, bool booked, hipStream_t s,
                         const Prefetch* pre = nullptr);
+// rule DDQ_RULE_ADAM (4): launch_apply launches adam_apply_kernel (adam.h) in
+// the apply kernel's place, with nb's Adam constants and lr; the fused apply
+// must be off.  With nb.adam_clip > 0 the caller launches launch_grad_norm
+// first: the gradient buffer's sum of squares as kGnBlocks double partials
+constexpr int kRuleAdam = 4;
+constexpr int kGnBlocks = 128;
+hipError_t launch_grad_norm(const NetBuffers& nb, hipStream_t s);
 hipError_t launch_relayout(const NetBuffers& nb, int z, hipStream_t s);
 // owner apply of shard [off, off+len) with W gradient slices (stride `slice`)
 // applied in rank order; then, after the theta all-gather, launch_refresh

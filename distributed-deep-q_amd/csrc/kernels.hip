@@ -1839,6 +1839,12 @@ Prefetch make_prefetch(const NetBuffers& next, const uint8_t* st, const uint8_t*
   return pf;
 }
 
+// the Adam rule's apply launch (adam.h, included at the end of this file: its
+// kernels are emitted after every other kernel of the code object, which keep
+// the offsets they have without it)
+hipError_t launch_adam_apply(const NetBuffers& nb, const ApplyArgs& a, const Prefetch& pf,
+                             hipStream_t s);
+
 hipError_t launch_apply(const NetBuffers& nb, int rule, float lr, float decay, float eps,
                         float momentum, float wd, int period, bool booked, hipStream_t s,
                         const Prefetch* pre) {
@@ -1846,6 +1852,7 @@ hipError_t launch_apply(const NetBuffers& nb, int rule, float lr, float decay, f
   if (pre) pf = *pre;
   ApplyArgs a = apply_args(nb, rule, lr, decay, eps, momentum, wd, period);
   if (!booked) ddq_launch(apply_book_kernel, dim3(1), dim3(1), 0, s, nb.iter, nb.opt_init, period);
+  if (rule == kRuleAdam) return launch_adam_apply(nb, a, pf, s);
   // fused steps: the slab-reduce launch already updated every parameter --
   // or, with its fc4 gradient summed over the ranks under the conv backward
   // (fa.ext), fc4's weights: the rest (summed after the reduce) here
@@ -2517,3 +2524,5 @@ __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
 #include "env.h"
 // the training monitor's reduction: one workgroup per chunk, one record
 #include "monitor.h"
+// the Adam rule's two kernels (two state words: not a case of apply_rule)
+#include "adam.h"

@@ -23,7 +23,7 @@ CPU_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", 
 MODES = ("gpu", "cpu")
 
 DDQ_OK, DDQ_EINVAL, DDQ_ENOMEM, DDQ_EHIP, DDQ_ERCCL, DDQ_ESTATE, DDQ_ERANGE = 0, -1, -2, -3, -4, -5, -6
-RULES = {"sgd": 0, "rmsprop": 1, "adagrad": 2, "momentum": 3}
+RULES = {"sgd": 0, "rmsprop": 1, "adagrad": 2, "momentum": 3, "adam": 4}
 
 
 class DDQError(RuntimeError):
@@ -75,6 +75,12 @@ class PriorityCfg(ctypes.Structure):
     """include/ddq_hip.h ddq_priority_cfg (16 bytes)."""
     _fields_ = [("enabled", ctypes.c_int32), ("alpha", ctypes.c_float),
                 ("beta", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+class AdamCfg(ctypes.Structure):
+    """include/ddq_hip.h ddq_adam_cfg (16 bytes)."""
+    _fields_ = [("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("eps", ctypes.c_float), ("max_grad_norm", ctypes.c_float)]
 
 
 PRIO_ONE, PRIO_MAX = 1 << 16, 1 << 24      # a leaf of 1.0; the largest leaf
@@ -159,6 +165,9 @@ _SIGS = {
     "ddq_apply_async": (ctypes.c_int, [_P, ctypes.POINTER(UpdateCfg)]),
     "ddq_reset_optimizer": (ctypes.c_int, [_P]),
     "ddq_get_optimizer_state": (ctypes.c_int, [_P, _P, _i64]),
+    "ddq_set_adam": (ctypes.c_int, [_P, ctypes.POINTER(AdamCfg)]),
+    "ddq_get_adam": (ctypes.c_int, [_P, ctypes.POINTER(AdamCfg)]),
+    "ddq_adam_state": (ctypes.c_int, [_P, _P, _P, _i64, ctypes.POINTER(_i64)]),
     "ddq_comm_get_unique_id": (ctypes.c_int, [_P]),
     "ddq_comm_init": (ctypes.c_int, [_P, _P, _i32, _i32]),
     "ddq_allreduce_grads": (ctypes.c_int, [_P]),

@@ -21,7 +21,7 @@ NUM_ACTIONS = 4     # barista/constants.py:8
 NFRAME = 4          # expgain.py:9
 
 BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0,
-         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1}
+         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1, "grad_norm": 0}
 
 # include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
 MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
@@ -222,7 +222,7 @@ class DeepQNet:
         self._check(self.lib.ddq_read_blob(self.ctx, name.encode(), ptr(out), n))
         if BLOBS[name] == 4:
             return out.reshape(B, 4, 1, 1)
-        if name == "loss":
+        if BLOBS[name] == 0:
             return out.reshape(())
         return out.reshape(B, 1, 1, 1)
 
@@ -389,6 +389,32 @@ class DeepQNet:
               weight_decay=0.0005):
         cfg = _lib.update_cfg(rule, lr, decay, eps, momentum, weight_decay)
         self._check(self.lib.ddq_apply(self.ctx, ctypes.byref(cfg)))
+
+    def set_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, max_grad_norm=0.0):
+        """Configure the "adam" rule (ddq_set_adam): torch.optim.Adam without
+        amsgrad or weight decay, eps added outside the square root;
+        max_grad_norm > 0 clips the gradient to that global L2 norm first (blob
+        ``grad_norm``: the last pre-clip norm), 0 turns clipping off.  Needed
+        once before ``apply("adam")`` or a ``step_cfg("adam", ...)`` step; a net
+        that changes rule should ``reset_optimizer()``."""
+        a = _lib.AdamCfg(float(beta1), float(beta2), float(eps), float(max_grad_norm))
+        self._check(self.lib.ddq_set_adam(self.ctx, ctypes.byref(a)))
+
+    def get_adam(self):
+        """{"beta1", "beta2", "eps", "max_grad_norm"} as set_adam takes them."""
+        a = _lib.AdamCfg()
+        self._check(self.lib.ddq_get_adam(self.ctx, ctypes.byref(a)))
+        return {"beta1": float(a.beta1), "beta2": float(a.beta2), "eps": float(a.eps),
+                "max_grad_norm": float(a.max_grad_norm)}
+
+    def adam_state(self):
+        """(m, v, t): Adam's first and second moments (flat, as get_flat) and the
+        number of updates applied since the last reset_optimizer()."""
+        m = np.empty(self.num_params, np.float32)
+        v = np.empty(self.num_params, np.float32)
+        t = ctypes.c_int64()
+        self._check(self.lib.ddq_adam_state(self.ctx, ptr(m), ptr(v), m.size, ctypes.byref(t)))
+        return m, v, int(t.value)
 
     def reset_optimizer(self):
         self._check(self.lib.ddq_reset_optimizer(self.ctx))

@@ -14,8 +14,9 @@ Semantics kept:
   model message (dict order: Q* then P*);
 * a push increments ``iteration`` then applies the gradient with the selected
   rule -- sgd (:81-83), rmsprop with the one-step-lagged cache (:86-105,
-  default), adagrad (:108-124) -- each on arrival, i.e. with the reference's
-  unbounded staleness;
+  default), adagrad (:108-124), or (no reference counterpart) ``adam`` with the
+  ``adam=dict(beta1, beta2, eps, max_grad_norm)`` constants -- each on arrival,
+  i.e. with the reference's unbounded staleness;
 * ``snapshot_frequency`` (:74-77): every that many iterations the model is
   handed to ``on_snapshot(name, params)`` (Celery's ``saveSnapshot`` in the
   reference; a callback here);
@@ -49,10 +50,14 @@ def get_snapshot_name(iteration):
 class ParamServer:
     def __init__(self, frame=16, batch=32, update="rmsprop", lr=1e-4, rmsprop_decay=0.9,
                  special_update=10, snapshot_freq=500, stats_freq=500, device=0,
-                 on_snapshot=None, mode="gpu", on_stats=None):
-        if update not in ("sgd", "rmsprop", "adagrad"):
-            raise ValueError("update must be one of adagrad, rmsprop, sgd")
+                 on_snapshot=None, mode="gpu", on_stats=None, adam=None):
+        if update not in ("sgd", "rmsprop", "adagrad", "adam"):
+            raise ValueError("update must be one of adagrad, adam, rmsprop, sgd")
         self.net = DeepQNet(batch=batch, frame=frame, device=device, mode=mode)
+        # no reference counterpart: Adam (optionally under a global gradient-norm
+        # clip), adam = DeepQNet.set_adam's keywords
+        if update == "adam":
+            self.net.set_adam(**(adam or {}))
         self.update = update
         self.learning_rate = float(lr)
         self.rmsprop_decay = float(rmsprop_decay)

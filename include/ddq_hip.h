@@ -56,6 +56,8 @@ extern "C" {
                               (ddq_replay_set_priority, ddq_replay_get_priority,
                               ddq_replay_priorities, ddq_replay_set_priorities,
                               ddq_replay_update_priorities_async; blob "is_weight"),
+                              likewise; and the Adam rule (DDQ_RULE_ADAM, ddq_set_adam,
+                              ddq_get_adam, ddq_adam_state; blob "grad_norm"),
                               likewise */
 
 enum ddq_status {
@@ -95,11 +97,12 @@ enum ddq_rule {
   DDQ_RULE_SGD = 0,            /* server.py:81-83   theta -= lr*g             */
   DDQ_RULE_RMSPROP = 1,        /* server.py:86-105  lagged cache (default)    */
   DDQ_RULE_ADAGRAD = 2,        /* server.py:108-124                           */
-  DDQ_RULE_MOMENTUM_CAFFE = 3  /* solver.prototxt:4-11 semantics (optional)   */
+  DDQ_RULE_MOMENTUM_CAFFE = 3, /* solver.prototxt:4-11 semantics (optional)   */
+  DDQ_RULE_ADAM = 4            /* Adam + global-norm clip (ddq_set_adam below) */
 };
 
 typedef struct ddq_update_cfg {
-  int32_t rule;          /* enum ddq_rule                                     */
+  int32_t rule;          /* enum ddq_rule; DDQ_RULE_ADAM reads only lr below  */
   float lr;              /* server.py:268 default 1e-4 (momentum: base_lr)    */
   float decay;           /* rmsprop decay, server.py:270 default 0.9          */
   float eps;             /* 1e-8 inside the sqrt, server.py:105,124           */
@@ -163,7 +166,8 @@ typedef struct ddq_step_cfg {
  * (at S = 16 the block is stored regardless: the fused step's last launch
  * applies it from there).
  * The update is unchanged, bit for bit.  No effect on exchanged steps (their
- * gradient is what is exchanged). */
+ * gradient is what is exchanged) nor on DDQ_RULE_ADAM steps (the gradient
+ * buffer is the Adam launch's input). */
 #define DDQ_STEP_NO_GRAD_STORE 1
 
 /* ---------------- context ---------------------------------------------- */
@@ -447,7 +451,8 @@ int ddq_forward_q(ddq_ctx* ctx);
  * counterpart, "Q_out.diff" (B*4): the head's dQ of the last pass (the diff the
  * loss layer hands to Q_out), and "Qn_out" (B*4): Q(s',.) under theta_Q of the
  * last pass with the double target (DDQ_ESTATE under DDQ_TARGET_MAX: nothing
- * computed it). */
+ * computed it), and "grad_norm" (1): the pre-clip gradient norm of the last
+ * clipped Adam apply (DDQ_ESTATE unless ddq_set_adam turned clipping on). */
 int ddq_read_blob(ddq_ctx* ctx, const char* name, float* dst, int64_t n);
 /* Argmax/ReLU routing bytes of pool layer 1..3 of the Q tower for the last
  * forward_backward, in Caffe (B,C,H/2,W/2) order: 0..3 = first-max position
@@ -585,9 +590,58 @@ int ddq_actors_read(ddq_ctx* ctx, int8_t* boards, int64_t* stats, int64_t* total
  * current gradient buffer.  Optimizer state lives on device. */
 int ddq_apply(ddq_ctx* ctx, const ddq_update_cfg* cfg);
 int ddq_apply_async(ddq_ctx* ctx, const ddq_update_cfg* cfg);
-/* Forget rmsprop/adagrad/momentum state (server.py:229-231 clear()). */
+/* Forget rmsprop/adagrad/momentum/Adam state (server.py:229-231 clear()). */
 int ddq_reset_optimizer(ddq_ctx* ctx);
 int ddq_get_optimizer_state(ddq_ctx* ctx, float* dst, int64_t n);
+
+/* ---------------- Adam with global-norm gradient clipping ------------------ */
+/* (Kingma & Ba 2015; torch.optim.Adam without amsgrad or weight decay; no
+ * reference counterpart.)  DDQ_RULE_ADAM keeps two state words per parameter:
+ * the first moment m in the buffer every rule uses (ddq_get_optimizer_state
+ * returns it) and the second moment v in a buffer ddq_set_adam allocates.
+ * Per element, in fp32, every operation rounded on its own (no fused
+ * multiply-add), with lr from ddq_update_cfg and the rest from ddq_adam_cfg:
+ *     omb1 = (float)(1.0 - (double)beta1)          omb2 likewise
+ *     c1   = (float)(1.0 - pow((double)beta1, (double)t))   c2 likewise
+ *     g'   = s * g                       (only when clipping is on)
+ *     m    = beta1 * m + omb1 * g'       (first apply after a reset: m = v = 0)
+ *     v    = beta2 * v + omb2 * (g' * g')
+ *     theta = theta - (lr * (m / c1)) / (sqrtf(v / c2) + eps)
+ * t is the device iteration counter after the apply's bookkeeping: the number of
+ * updates applied since ddq_reset_optimizer, this one included.  The Adam launch
+ * reads it from device memory, so captured graphs replay it.  A ctx that changes
+ * its rule should call ddq_reset_optimizer: the other rules read m as their
+ * state word, and t counts every rule's updates.
+ * Clipping (max_grad_norm = c > 0): one launch before the apply ("grad_norm" in
+ * ddq_profile_step) sums the squares of the gradient buffer in double, a fixed
+ * number of partials in a fixed order, no atomics; the Adam launch ("adam_apply")
+ * adds the partials in index order, nrm = (float)sqrt(total),
+ * s = nrm > c ? c / nrm : 1.0f.  The gradient buffer is not modified
+ * (ddq_get_grads and the monitor see g); under DDQ_EXCHANGE_ALLREDUCE the norm is
+ * that of the summed gradient.  ddq_read_blob("grad_norm", 1) returns the last
+ * nrm (DDQ_ESTATE with clipping off).
+ * An Adam step runs the gradient launches and then the apply launch, the
+ * sequencing of an exchanged step (no update inside the slab-reduce launch), in
+ * eager, graph and pipelined mode, with every objective, n and prioritized
+ * replay.  DDQ_RULE_ADAM before ddq_set_adam: DDQ_ESTATE.  With
+ * DDQ_EXCHANGE_SHARDED, DDQ_EXCHANGE_SERVER or DDQ_EXCHANGE_ASYNC (they shard
+ * one state buffer and apply W gradients per launch; not supported here) and in
+ * ddq_async_begin: DDQ_EINVAL, nothing changes.  DDQ_EXCHANGE_NONE and
+ * DDQ_EXCHANGE_ALLREDUCE (RCCL and the in-process group) work. */
+typedef struct ddq_adam_cfg {   /* 16 bytes */
+  float beta1, beta2;           /* in [0, 1)                                    */
+  float eps;                    /* finite, > 0; added outside the sqrt          */
+  float max_grad_norm;          /* 0 = no clipping; else finite, > 0            */
+} ddq_adam_cfg;
+/* The first call synchronises, drops captured graphs and allocates v (zeroed);
+ * later calls only change the constants, and also drop graphs.  DDQ_EINVAL: a
+ * value out of range.  DDQ_ESTATE: the async exchange has begun. */
+int ddq_set_adam(ddq_ctx* ctx, const ddq_adam_cfg* cfg);
+/* DDQ_ESTATE before ddq_set_adam. */
+int ddq_get_adam(const ddq_ctx* ctx, ddq_adam_cfg* cfg);
+/* Synchronise and read m and v (n == ddq_num_params) and t; any pointer may be
+ * NULL.  DDQ_ESTATE before ddq_set_adam.  ddq_reset_optimizer zeroes all three. */
+int ddq_adam_state(ddq_ctx* ctx, float* m, float* v, int64_t n, int64_t* t);
 
 /* ---------------- communication (RCCL over xGMI) ----------------------- */
 /* Replace the HTTP/Redis gradient round trip (baristanet.py:105-123,
