@@ -43,6 +43,64 @@ struct EnvBufs {
   int n = 0;                       // games playing; 0: not created
 };
 
+// One graph holds kGraphSteps steps back to back (the launch of a graph
+// costs ~9 us of device idle, measured, so it is paid once per kGraphSteps
+// steps), plus a one-step graph for the remainder.  The device-side counters
+// make every captured step read its own iteration / RNG state.
+static constexpr int kGraphSteps = 8;
+
+// The execs of one family of captured step graphs and the cfg they hold.
+template <int N>
+struct GraphFamily {
+  hipGraphExec_t exec[N] = {};
+  ddq_step_cfg cfg{};
+  bool keyed = false;
+  bool holds(const ddq_step_cfg* c) const { return keyed && memcmp(&cfg, c, sizeof(cfg)) == 0; }
+  void key(const ddq_step_cfg* c) { cfg = *c; keyed = true; }
+  void reset() {
+    for (auto& g : exec) {
+      if (g) hipGraphExecDestroy(g);
+      g = nullptr;
+    }
+    keyed = false;
+  }
+};
+
+// Every captured graph of a ctx.  An exec bakes in the pointers and launch
+// arguments of its capture, so:
+//  - whatever replaces one of those (the stream, the index log, the objective,
+//    the ring's layout, the communicator, ...) calls invalidate_graph, which
+//    drops every exec of every family;
+//  - an exec is replayed only while its family holds() the caller's cfg, byte
+//    for byte;
+//  - ensure_graph / ensure_pipe, when they have to capture, drop every family
+//    first; a cfg change seen by the tick or the round graphs drops that family;
+//  - the round graph's phase is reset together with its exec.
+struct StepGraphs {
+  GraphFamily<2> plain;   // ddq_step_graph_async: [0] one step, [1] kGraphSteps steps
+  // ddq_step_pipelined_async, on minibatch set p:
+  struct Pipe : GraphFamily<2 * 2 + 2 + 2 * (kGraphSteps + 1)> {
+    hipGraphExec_t& step(int p, int f) { return exec[2 * p + f]; }   // one step, f: prefetching
+    hipGraphExec_t& chain(int p) { return exec[4 + p]; }   // kGraphSteps prefetching steps
+    // r = 2..kGraphSteps steps, the last one not prefetching (the end of a fused chain)
+    hipGraphExec_t& tail(int p, int r) { return exec[6 + p * (kGraphSteps + 1) + r]; }
+  } pipe;
+  // async round-robin rounds as one graph
+  struct Round : GraphFamily<1> {
+    int64_t phase = -1;   // iteration % period the graph was captured at
+    void reset() { GraphFamily::reset(); phase = -1; }
+  } round;
+  // ticket-order ticks of this rank's own gradient, one per (P pull due,
+  // special update due): ddq_async_tick replays instead of re-enqueueing
+  GraphFamily<4> tick;
+  void reset() {
+    plain.reset();
+    pipe.reset();
+    round.reset();
+    tick.reset();
+  }
+};
+
 struct ddq_ctx {
   int device = 0;
   ddq_net_desc desc{};
@@ -124,34 +182,15 @@ struct ddq_ctx {
   bool acapture = false;           // capturing async rounds: grad_ev recorded before the
   bool grad_ev_captured = false;   // capture began is not waited on (the graph launch
                                    // follows that work on the stream anyway)
-  hipGraphExec_t agexec = nullptr; // kAsync round-robin rounds as one graph
-  int agraph_rounds = 0;
-  int64_t agraph_phase = -1;       // iteration % period the graph was captured at
-  ddq_step_cfg acfg{};
-  // ticket-order ticks of this rank's own gradient as graphs, one per (P pull
-  // due, special update due): ddq_async_tick replays instead of re-enqueueing
-  hipGraphExec_t tgexec[4] = {nullptr, nullptr, nullptr, nullptr};
-  ddq_step_cfg tcfg{};
   std::string comm_err;
   // ddq_inject_fault: armed failpoint, consumed by the next eager step
   int fault = 0;
   std::string small_off;           // why the small-map step is off at S = 16 (empty: on)
-  // graph
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;     // one step
-  hipGraphExec_t gexec_k = nullptr;   // kGraphSteps steps
-  ddq_step_cfg gcfg{};
-  bool have_graph = false;
-  // pipelined stepping: a second minibatch set and graphs [parity][prefetch]
+  StepGraphs graphs;
+  // pipelined stepping: a second minibatch set
   float *mb2_state = nullptr, *mb2_next = nullptr, *mb2_action = nullptr;
   float *mb2_reward = nullptr, *mb2_nonterm = nullptr;
   int32_t* mb2_idx = nullptr;
-  hipGraphExec_t pexec[2][2] = {};  // one step on set p, [f] = prefetching
-  hipGraphExec_t pexec_k[2] = {};   // kGraphSteps prefetching steps starting on set p
-  hipGraphExec_t ptail[2][9] = {};  // r = 1..kGraphSteps steps from set p, the last one
-                                    // not prefetching (the end of a fused chain)
-  ddq_step_cfg pcfg{};
-  bool have_pipe = false;
   int64_t steps = 0;
   int64_t applied = 0;               // host mirror of the device iteration counter
   // profiling marks: a kernel's own dispatch start / stop events
@@ -235,39 +274,7 @@ static int set_dev(ddq_ctx* c) {
   return DDQ_OK;
 }
 
-static void invalidate_graph(ddq_ctx* c) {
-  // (the async tick / round graphs too: they bake in the index log and the
-  // other captured pointers that ddq_index_log_enable / set_stream replace)
-  for (auto& g : c->tgexec) {
-    if (g) hipGraphExecDestroy(g);
-    g = nullptr;
-  }
-  if (c->agexec) hipGraphExecDestroy(c->agexec);
-  c->agexec = nullptr;
-  c->agraph_rounds = 0;
-  if (c->gexec) hipGraphExecDestroy(c->gexec);
-  if (c->gexec_k) hipGraphExecDestroy(c->gexec_k);
-  c->gexec_k = nullptr;
-  if (c->graph) hipGraphDestroy(c->graph);
-  c->gexec = nullptr;
-  c->graph = nullptr;
-  c->have_graph = false;
-  for (auto& row : c->pexec)
-    for (auto& g : row) {
-      if (g) hipGraphExecDestroy(g);
-      g = nullptr;
-    }
-  for (auto& g : c->pexec_k) {
-    if (g) hipGraphExecDestroy(g);
-    g = nullptr;
-  }
-  for (auto& row : c->ptail)
-    for (auto& g : row) {
-      if (g) hipGraphExecDestroy(g);
-      g = nullptr;
-    }
-  c->have_pipe = false;
-}
+static void invalidate_graph(ddq_ctx* c) { c->graphs.reset(); }
 
 extern "C" {
 
@@ -1224,60 +1231,60 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
 }
 
 // ---------------- compute ----------------
+// The profile marks of a step (ddq_profile_step): m(name) names the kernel
+// launched next; without fn (every other caller) it does nothing.
+struct Marks {
+  void (*fn)(void*, const char*) = nullptr;
+  void* arg = nullptr;
+  void operator()(const char* name) const {
+    if (fn) fn(arg, name);
+  }
+};
+
 // Double target (ddq_set_objective): Q(s',.) under theta_Q for the minibatch view
 // the pass trains on, the pass's first launch group -- ddq_forward_q's kernels
 // at n = B over nb.next_state in the acting scratch (the actor, pool and
 // evaluator are serial on the same stream), into the ctx's Qn_out buffer.  It
 // depends on theta_Q and the bound view only: stream order after the previous
 // step's apply is enough.  Profile names: "qn_<kernel>".
-struct QnMark {
-  void (*mark)(void*, const char*);
-  void* arg;
-};
 static void qn_mark(void* a, const char* name) {
-  const QnMark* m = reinterpret_cast<const QnMark*>(a);
   const std::string s = std::string("qn_") + name;
-  m->mark(m->arg, s.c_str());
+  (*reinterpret_cast<const Marks*>(a))(s.c_str());
 }
-static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
-                              void* marg) {
+static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
   if (nb.obj_target != DDQ_TARGET_DOUBLE) return DDQ_OK;
-  QnMark qm{mark, marg};
   HIP_TRY(c, launch_act(nb, nb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
-                        nullptr, c->act_p1s, c->act_p2s, c->stream, mark ? qn_mark : nullptr, &qm));
+                        nullptr, c->act_p1s, c->act_p2s, c->stream, m.fn ? qn_mark : nullptr, &m));
   return DDQ_OK;
 }
 
 // book >= 0: this backward feeds a step's apply; its slab reduce also does
 // the apply bookkeeping with target period `book` (saves a launch).
-static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
-                           void* marg, int book = -1, ReplayMeta* bump = nullptr) {
-  TRY(enqueue_qn_forward(c, nb, mark, marg));
+static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, Marks m = {}, int book = -1,
+                           ReplayMeta* bump = nullptr) {
+  TRY(enqueue_qn_forward(c, nb, m));
   if (nb.small) {
-    HIP_TRY(c, launch_small_fwd_head(nb, c->stream, mark, marg));
+    HIP_TRY(c, launch_small_fwd_head(nb, c->stream, m.fn, m.arg));
   } else {
-    HIP_TRY(c, launch_forward(nb, 2, c->stream, mark, marg, false));
-    if (mark) mark(marg, "head");
+    HIP_TRY(c, launch_forward(nb, 2, c->stream, m.fn, m.arg, false));
+    m("head");
     HIP_TRY(c, launch_head(nb, c->stream));
   }
   // one stream: forking the weight-gradient kernels onto a side stream cost
   // more in cross-stream graph edges (6-14 us idle each, measured) than the
   // overlap returned, as every kernel here fills the GPU on its own
   if (nb.small)
-    HIP_TRY(c, launch_small_bwd(nb, c->stream, mark, marg, book >= 0, book, bump, nullptr, nullptr,
+    HIP_TRY(c, launch_small_bwd(nb, c->stream, m.fn, m.arg, book >= 0, book, bump, nullptr, nullptr,
                                 nullptr));
   else
-    HIP_TRY(c, launch_backward(nb, c->stream, mark, marg, book >= 0, book, bump));
+    HIP_TRY(c, launch_backward(nb, c->stream, m.fn, m.arg, book >= 0, book, bump));
   return DDQ_OK;
-}
-static int enqueue_fwd_bwd(ddq_ctx* c, void (*mark)(void*, const char*), void* marg) {
-  return enqueue_fwd_bwd(c, c->nb, mark, marg);
 }
 
 int ddq_forward_backward_async(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(set_dev(c));
-  return enqueue_fwd_bwd(c, nullptr, nullptr);
+  return enqueue_fwd_bwd(c, c->nb);
 }
 
 int ddq_forward_backward(ddq_ctx* c, float* loss) {
@@ -1736,14 +1743,13 @@ static int check_cfg(ddq_ctx* c, const ddq_update_cfg* u) {
 // clipping on: the gradient-norm launch first, over the buffer the apply reads
 // (under all-reduce: the summed gradient).
 static int enqueue_apply(ddq_ctx* c, const NetBuffers& nb, const ddq_update_cfg& u, int period,
-                         bool booked, const Prefetch* pf = nullptr,
-                         void (*mark)(void*, const char*) = nullptr, void* marg = nullptr) {
+                         bool booked, const Prefetch* pf = nullptr, Marks m = {}) {
   const bool adam = u.rule == DDQ_RULE_ADAM;
   if (adam && nb.adam_clip > 0.f) {
-    if (mark) mark(marg, "grad_norm");
+    m("grad_norm");
     HIP_TRY(c, launch_grad_norm(nb, c->stream));
   }
-  if (mark) mark(marg, adam ? "adam_apply" : "apply");
+  m(adam ? "adam_apply" : "apply");
   HIP_TRY(c, launch_apply(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay, period,
                           booked, c->stream, pf));
   return DDQ_OK;
@@ -1901,6 +1907,15 @@ static int step_inc(const ddq_ctx* c, const ddq_step_cfg* cfg) {
              ? c->nranks
              : 1;
 }
+// host mirrors of the device counters after n more steps
+static void count_steps(ddq_ctx* c, const ddq_step_cfg* cfg, int n) {
+  c->steps += n;
+  c->applied += (int64_t)n * step_inc(c, cfg);
+}
+// the target period as the apply bookkeeping takes it (0: no P <- Q sync)
+static int book_period(const ddq_step_cfg* cfg) {
+  return cfg->target_period > 0 ? cfg->target_period : 0;
+}
 static bool is_async(const ddq_ctx* c, const ddq_step_cfg* cfg) {
   return has_exchange(c, cfg) && cfg->exchange == DDQ_EXCHANGE_ASYNC;
 }
@@ -1932,16 +1947,15 @@ static hipError_t fc4_bucket_start(void* arg) {
   return hipEventRecord(c->cev[2], c->cs);
 }
 
-static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void*, const char*),
-                             void* marg, int book, ReplayMeta* bump, bool overlap,
-                             const Prefetch* pf = nullptr, const NetBuffers* prio_next = nullptr,
-                             uint64_t prio_seed = 0) {
-  TRY(enqueue_qn_forward(c, nb, mark, marg));
+static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, Marks m, int book, ReplayMeta* bump,
+                             bool overlap, const Prefetch* pf = nullptr,
+                             const NetBuffers* prio_next = nullptr, uint64_t prio_seed = 0) {
+  TRY(enqueue_qn_forward(c, nb, m));
   if (nb.small) {
-    HIP_TRY(c, launch_small_fwd_head(nb, c->stream, mark, marg, bump, nb.fa.on ? pf : nullptr));
+    HIP_TRY(c, launch_small_fwd_head(nb, c->stream, m.fn, m.arg, bump, nb.fa.on ? pf : nullptr));
   } else {
-    HIP_TRY(c, launch_forward(nb, 2, c->stream, mark, marg, false));
-    if (mark) mark(marg, "head");
+    HIP_TRY(c, launch_forward(nb, 2, c->stream, m.fn, m.arg, false));
+    m("head");
     // fused apply: the draw counter advances here (pipelined: with the next
     // step's draw, kernels.hip head_draw)
     HIP_TRY(c, launch_head(nb, c->stream, bump, nb.fa.on ? pf : nullptr));
@@ -1951,16 +1965,16 @@ static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void
   // a next step is being prefetched, draws its index set and weights (the
   // prefetch blocks below then gather with predrawn = 1)
   if (nb.prio.leaf && bump) {
-    if (mark) mark(marg, "prio_commit");
+    m("prio_commit");
     HIP_TRY(c, launch_prio_commit_draw(nb, bump, prio_next, prio_seed, c->stream));
   }
   // the draw counter advances once per step: without the fused apply the slab
   // reduce's bookkeeping would advance it (apply_book's bump), but on a
   // prioritized step the commit launch above already has (an Adam step)
   ReplayMeta* bbump = (nb.prio.leaf && !nb.fa.on) ? nullptr : bump;
-  hipError_t e = nb.small ? launch_small_bwd(nb, c->stream, mark, marg, book >= 0, book, bbump,
+  hipError_t e = nb.small ? launch_small_bwd(nb, c->stream, m.fn, m.arg, book >= 0, book, bbump,
                                              overlap ? fc4_bucket_start : nullptr, c, pf)
-                          : launch_backward(nb, c->stream, mark, marg, book >= 0, book, bbump,
+                          : launch_backward(nb, c->stream, m.fn, m.arg, book >= 0, book, bbump,
                                             overlap ? fc4_bucket_start : nullptr, c, pf);
   if (e != hipSuccess && !c->comm_err.empty()) {
     std::string m = c->comm_err;
@@ -1982,14 +1996,13 @@ static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, void (*mark)(void
 //             one by one in rank order (server.py:196-209 on arrival) ->
 //             all-gather -> refresh.
 static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb,
-                                  void (*mark)(void*, const char*), void* marg, bool overlap,
-                                  const Prefetch* pf = nullptr) {
+                                  Marks m, bool overlap, const Prefetch* pf = nullptr) {
   const ddq_update_cfg& u = cfg->update;
   const ParamLayout& L = nb.L;
   const int ex = has_exchange(c, cfg) ? cfg->exchange : DDQ_EXCHANGE_NONE;
   if (ex == DDQ_EXCHANGE_NONE || ex == DDQ_EXCHANGE_ALLREDUCE) {
     if (ex == DDQ_EXCHANGE_ALLREDUCE) {
-      if (mark) mark(marg, "allreduce");
+      m("allreduce");
       if (overlap && nb.fa.on) {
         // fc4's weights were summed under the conv backward and applied by
         // the slab-reduce launch (nb.fa.ext), whose stream waited for that
@@ -2019,11 +2032,11 @@ static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const Net
                                   c->stream));
       }
     }
-    return enqueue_apply(c, nb, u, cfg->target_period, true, pf, mark, marg);
+    return enqueue_apply(c, nb, u, cfg->target_period, true, pf, m);
   }
   const int W = c->nranks;
   const size_t len = (size_t)c->shard_len;
-  if (mark) mark(marg, ex == DDQ_EXCHANGE_SHARDED ? "reduce_scatter" : "all_to_all");
+  m(ex == DDQ_EXCHANGE_SHARDED ? "reduce_scatter" : "all_to_all");
   if (ex == DDQ_EXCHANGE_SHARDED)
     NCCL_TRY(c, ncclReduceScatter(nb.grad, c->gsl, len, ncclFloat, ncclSum, c->comm, c->stream));
   else if (W > 1) {
@@ -2037,21 +2050,44 @@ static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const Net
     }
     NCCL_TRY(c, ncclGroupEnd());
   }
-  if (mark) mark(marg, "apply_shard");
+  m("apply_shard");
   HIP_TRY(c, launch_apply_shard(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
                                 c->gsl, (int64_t)c->rank * len, (int64_t)len, (int64_t)len,
                                 ex == DDQ_EXCHANGE_SHARDED ? 1 : W, c->stream, nullptr, -1, pf,
                                 nullptr, -1, c->rank,
                                 ex == DDQ_EXCHANGE_SHARDED ? nullptr
                                                            : nb.grad + (size_t)c->rank * len));
-  if (mark) mark(marg, "all_gather");
+  m("all_gather");
   NCCL_TRY(c, ncclAllGather(nb.theta[0] + (size_t)c->rank * len, nb.theta[0], len, ncclFloat,
                             c->comm, c->stream));
   // the owner's shard was refreshed by its apply: the other ranks' shards
   // only (no launch when one rank owns every parameter)
-  if (mark) mark(marg, "refresh");
+  m("refresh");
   HIP_TRY(c, launch_refresh(nb, c->stream, -1, (int64_t)c->rank * len,
                             (int64_t)(c->rank + 1) * len));
+  return DDQ_OK;
+}
+
+// The draw of a minibatch and its gather into nb's set, on `stream`.
+static int enqueue_draw(ddq_ctx* c, const NetBuffers& nb, uint64_t seed, hipStream_t stream,
+                        Marks m = {}) {
+  if (c->prio_on) {   // one workgroup descends the sum tree, then the plain gather
+    m("prio_sample");
+    HIP_TRY(c, launch_prio_sample(nb, c->r_meta, seed, stream));
+    m("gather");
+    HIP_TRY(c, launch_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
+                             stream));
+  } else if (nb.B <= 256) {   // one kernel: every gather workgroup draws the same index set
+    m("sample_gather");
+    HIP_TRY(c, launch_sample_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
+                                    c->r_meta, seed, stream));
+  } else {
+    m("sample");
+    HIP_TRY(c, launch_sample(nb, c->r_meta, seed, stream));
+    m("gather");
+    HIP_TRY(c, launch_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
+                             stream));
+  }
   return DDQ_OK;
 }
 
@@ -2070,8 +2106,7 @@ static bool fused_prefetch(const ddq_ctx* c, const ddq_step_cfg* cfg) {
 }
 
 static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
-                              const NetBuffers* pre, void (*mark)(void*, const char*), void* marg,
-                              ReplayMeta* bump) {
+                              const NetBuffers* pre, Marks m, ReplayMeta* bump) {
   NetBuffers nb = nb_in;
   nb.book_inc = step_inc(c, cfg);
   // exchange-free steps: fc4's weight update rides on the slab-reduce launch
@@ -2094,7 +2129,7 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
     nb.fa.store_grad = ar_overlap || !(cfg->flags & DDQ_STEP_NO_GRAD_STORE);
     nb.fc4_wait = ar_overlap ? c->cev[2] : nullptr;
     nb.fa.rule = u.rule;
-    nb.fa.period = cfg->target_period > 0 ? cfg->target_period : 0;
+    nb.fa.period = book_period(cfg);
     nb.fa.lr = u.lr; nb.fa.decay = u.decay; nb.fa.eps = u.eps;
     nb.fa.momentum = u.momentum; nb.fa.wd = u.weight_decay;
   }
@@ -2117,21 +2152,18 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
                                 c->r_meta, cfg->seed);
     if (nb.prio.leaf && !nb.fa.on) pf.predrawn = 1;
     // fused apply: the slab-reduce launch carries the draw + gather too
-    TRY(enqueue_fwd_bwd_x(c, nb, mark, marg, cfg->target_period > 0 ? cfg->target_period : 0,
-                          c->r_meta, ar_overlap, nb.fa.on ? &pf : nullptr, pre, cfg->seed));
-    return enqueue_exchange_apply(c, cfg, nb, mark, marg, ar_overlap, nb.fa.on ? nullptr : &pf);
+    TRY(enqueue_fwd_bwd_x(c, nb, m, book_period(cfg), c->r_meta, ar_overlap,
+                          nb.fa.on ? &pf : nullptr, pre, cfg->seed));
+    return enqueue_exchange_apply(c, cfg, nb, m, ar_overlap, nb.fa.on ? nullptr : &pf);
   }
-  if (pre) {
+  if (pre) {   // (B > 256: the two-launch draw)
     HIP_TRY(c, hipEventRecord(nb.ev[6], c->stream));
     HIP_TRY(c, hipStreamWaitEvent(nb.side, nb.ev[6], 0));
-    HIP_TRY(c, launch_sample(*pre, c->r_meta, cfg->seed, nb.side));
-    HIP_TRY(c, launch_gather(*pre, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             nb.side));
+    TRY(enqueue_draw(c, *pre, cfg->seed, nb.side));
     HIP_TRY(c, hipEventRecord(nb.ev[7], nb.side));
   }
-  TRY(enqueue_fwd_bwd_x(c, nb, mark, marg, cfg->target_period > 0 ? cfg->target_period : 0, bump,
-                        ar_overlap, nullptr, nullptr, cfg->seed));
-  TRY(enqueue_exchange_apply(c, cfg, nb, mark, marg, ar_overlap));
+  TRY(enqueue_fwd_bwd_x(c, nb, m, book_period(cfg), bump, ar_overlap, nullptr, nullptr, cfg->seed));
+  TRY(enqueue_exchange_apply(c, cfg, nb, m, ar_overlap));
   if (pre) HIP_TRY(c, hipStreamWaitEvent(c->stream, nb.ev[7], 0));
   return DDQ_OK;
 }
@@ -2141,38 +2173,20 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
 // tests the device iteration against the period, so the launch is the same
 // every step and replays from a captured graph.
 static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
-                         const NetBuffers* pre, void (*mark)(void*, const char*), void* marg,
-                         ReplayMeta* bump = nullptr) {
-  TRY(enqueue_train_body(c, cfg, nb_in, pre, mark, marg, bump));
+                         const NetBuffers* pre, Marks m, ReplayMeta* bump) {
+  TRY(enqueue_train_body(c, cfg, nb_in, pre, m, bump));
   if (c->mon.ring && c->mon_period > 0) {
-    if (mark) mark(marg, "monitor");
+    m("monitor");
     HIP_TRY(c, launch_monitor(c->mon, c->mon_period, -1, c->stream));
   }
   return DDQ_OK;
 }
 
-static int enqueue_step(ddq_ctx* c, const ddq_step_cfg* cfg, void (*mark)(void*, const char*),
-                        void* marg) {
-  if (c->prio_on) {   // one workgroup descends the sum tree, then the plain gather
-    if (mark) mark(marg, "prio_sample");
-    HIP_TRY(c, launch_prio_sample(c->nb, c->r_meta, cfg->seed, c->stream));
-    if (mark) mark(marg, "gather");
-    HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             c->stream));
-    return enqueue_train(c, cfg, c->nb, nullptr, mark, marg, c->r_meta);
-  }
-  if (c->nb.B <= 256) {   // one kernel: every gather workgroup draws the same index set
-    if (mark) mark(marg, "sample_gather");
-    HIP_TRY(c, launch_sample_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                    c->r_meta, cfg->seed, c->stream));
-    return enqueue_train(c, cfg, c->nb, nullptr, mark, marg, c->r_meta);
-  }
-  if (mark) mark(marg, "sample");
-  HIP_TRY(c, launch_sample(c->nb, c->r_meta, cfg->seed, c->stream));
-  if (mark) mark(marg, "gather");
-  HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                           c->stream));
-  return enqueue_train(c, cfg, c->nb, nullptr, mark, marg);
+static int enqueue_step(ddq_ctx* c, const ddq_step_cfg* cfg, Marks m = {}) {
+  TRY(enqueue_draw(c, c->nb, cfg->seed, c->stream, m));
+  // (only the two-launch draw advanced the draw counter itself)
+  const bool bump = c->prio_on || c->nb.B <= 256;
+  return enqueue_train(c, cfg, c->nb, nullptr, m, bump ? c->r_meta : nullptr);
 }
 
 // minibatch set p: 0 = the ctx's own buffers, 1 = the pipelining twin
@@ -2256,18 +2270,10 @@ static int check_monitor_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
 // this worker's own push, async_owner_apply)
 static int async_compute(ddq_ctx* c, const ddq_step_cfg* cfg, bool drawn = false) {
   NetBuffers nb = c->nb;
-  if (nb.B <= 256) {   // one draw + gather launch; the head advances the counter
-    nb.head_bump = 1;
-    if (!drawn)
-      HIP_TRY(c, launch_sample_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                      c->r_meta, cfg->seed, c->stream));
-    TRY(enqueue_fwd_bwd_x(c, nb, nullptr, nullptr, -1, c->r_meta, false));
-  } else {
-    HIP_TRY(c, launch_sample(nb, c->r_meta, cfg->seed, c->stream));
-    HIP_TRY(c, launch_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             c->stream));
-    TRY(enqueue_fwd_bwd_x(c, nb, nullptr, nullptr, -1, nullptr, false));
-  }
+  const bool one = nb.B <= 256;   // one draw + gather launch; the head advances the counter
+  nb.head_bump = one;
+  if (!drawn) TRY(enqueue_draw(c, nb, cfg->seed, c->stream));
+  TRY(enqueue_fwd_bwd_x(c, nb, {}, -1, one ? c->r_meta : nullptr, false));
   HIP_TRY(c, hipEventRecord(c->grad_ev, c->stream));
   c->ready_seen = false;
   c->grad_ev_captured = c->acapture;
@@ -2487,6 +2493,69 @@ int ddq_async_ready(ddq_ctx* c, int32_t* ready) {
   return DDQ_OK;
 }
 
+// ---- graph capture ----
+// The scope of a capture of async ticks (what: the graph's name in errors;
+// null: a capture of other steps, nothing to guard).  fork() has the comm
+// stream join the capture (its owner duties follow the graph's start); a
+// grad_ev recorded before the capture began is not waited on inside it
+// (acapture / grad_ev_captured); and the captured ticks' host bookkeeping is
+// undone when the scope ends, whether or not the body succeeded.
+struct AsyncCapture {
+  ddq_ctx* c;
+  const char* what;
+  int64_t applied = 0, ticks = 0;
+  std::vector<int64_t> last;
+  AsyncCapture(ddq_ctx* c_, const char* what_) : c(c_), what(what_) {
+    if (!what) return;
+    applied = c->applied;
+    ticks = c->async_ticks;
+    last = c->last_pull;
+    c->acapture = true;
+    c->grad_ev_captured = false;
+  }
+  ~AsyncCapture() {
+    if (!what) return;
+    c->acapture = false;
+    c->applied = applied;
+    c->async_ticks = ticks;
+    c->last_pull = last;
+  }
+  int fork() const {
+    if (!what) return DDQ_OK;
+    hipError_t e = hipEventRecord(c->cev[0], c->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->cs, c->cev[0], 0);
+    if (e != hipSuccess) return fail(c, DDQ_EHIP, "%s fork: %s", what, hipGetErrorString(e));
+    return DDQ_OK;
+  }
+};
+
+// `body`'s launches on the ctx stream as one instantiated, uploaded exec.
+static int capture_exec(ddq_ctx* c, hipGraphExec_t* out, const std::function<int()>& body,
+                        const char* async_what = nullptr) {
+  HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  hipGraph_t g = nullptr;
+  int rc;
+  hipError_t e;
+  {
+    const AsyncCapture scope(c, async_what);
+    rc = scope.fork();
+    if (rc == DDQ_OK) rc = body();
+    e = hipStreamEndCapture(c->stream, &g);
+  }
+  if (rc != DDQ_OK) {
+    if (g) hipGraphDestroy(g);
+    return rc;
+  }
+  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+  hipGraphDestroy(g);
+  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+  // upload now: the first launch of a never-uploaded exec pays the upload on
+  // the stream (measured ~0.3 ms in the first timed chunk otherwise)
+  HIP_TRY(c, hipGraphUpload(*out, c->stream));
+  return DDQ_OK;
+}
+
 static int after_async_graph(ddq_ctx* c);
 
 // This rank's own tick (worker == rank) as a graph.  Its launches depend on
@@ -2494,35 +2563,14 @@ static int after_async_graph(ddq_ctx* c);
 // iteration is a special update (and the first apply of all: eager), so two
 // bits pick the graph; the capture leaves the host bookkeeping as it was.
 static int ensure_tick_graph(ddq_ctx* c, const ddq_step_cfg* cfg, int key) {
-  if (memcmp(&c->tcfg, cfg, sizeof(*cfg)) != 0) {
-    for (auto& g : c->tgexec)
-      if (g) { hipGraphExecDestroy(g); g = nullptr; }
-    c->tcfg = *cfg;
+  auto& t = c->graphs.tick;
+  if (!t.holds(cfg)) {
+    t.reset();
+    t.key(cfg);
   }
-  if (c->tgexec[key]) return DDQ_OK;
-  const int64_t applied = c->applied, ticks = c->async_ticks;
-  const std::vector<int64_t> last = c->last_pull;
-  HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  c->acapture = true;
-  c->grad_ev_captured = false;
-  int rc = DDQ_OK;
-  hipError_t e = hipEventRecord(c->cev[0], c->stream);   // the comm stream joins
-  if (e == hipSuccess) e = hipStreamWaitEvent(c->cs, c->cev[0], 0);
-  if (e != hipSuccess) rc = fail(c, DDQ_EHIP, "tick graph fork: %s", hipGetErrorString(e));
-  if (rc == DDQ_OK) rc = rccl_async_tick(c, cfg, c->rank);
-  hipGraph_t g = nullptr;
-  e = hipStreamEndCapture(c->stream, &g);
-  c->acapture = false;
-  c->applied = applied;
-  c->async_ticks = ticks;
-  c->last_pull = last;
-  if (rc != DDQ_OK) { if (g) hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-  e = hipGraphInstantiate(&c->tgexec[key], g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-  HIP_TRY(c, hipGraphUpload(c->tgexec[key], c->stream));
-  return DDQ_OK;
+  if (t.exec[key]) return DDQ_OK;
+  return capture_exec(c, &t.exec[key], [&] { return rccl_async_tick(c, cfg, c->rank); },
+                      "tick graph");
 }
 
 int ddq_async_tick(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t worker) {
@@ -2541,7 +2589,7 @@ int ddq_async_tick(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t worker) {
     const bool special = cfg->target_period > 0 && it % cfg->target_period == 0;
     const int key = (pull_p ? 2 : 0) | (special ? 1 : 0);
     TRY(ensure_tick_graph(c, cfg, key));
-    HIP_TRY(c, hipGraphLaunch(c->tgexec[key], c->stream));
+    HIP_TRY(c, hipGraphLaunch(c->graphs.tick.exec[key], c->stream));
     TRY(after_async_graph(c));
     async_advance(c, worker, it);
     return DDQ_OK;
@@ -2579,35 +2627,15 @@ static int async_round_eager(ddq_ctx* c, const ddq_step_cfg* cfg) {
 }
 
 static int ensure_async_graph(ddq_ctx* c, const ddq_step_cfg* cfg, int K) {
-  if (c->agexec && memcmp(&c->acfg, cfg, sizeof(*cfg)) == 0) return DDQ_OK;
-  if (c->agexec) hipGraphExecDestroy(c->agexec);
-  c->agexec = nullptr;
-  const int64_t applied = c->applied, ticks = c->async_ticks;
-  const std::vector<int64_t> last = c->last_pull;
-  HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  c->acapture = true;
-  c->grad_ev_captured = false;
-  // the comm stream joins the capture (its owner duties follow the graph's start)
-  int rc = DDQ_OK;
-  hipError_t e = hipEventRecord(c->cev[0], c->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(c->cs, c->cev[0], 0);
-  if (e != hipSuccess) rc = fail(c, DDQ_EHIP, "async graph fork: %s", hipGetErrorString(e));
-  for (int k = 0; k < K && rc == DDQ_OK; ++k) rc = rccl_async_round(c, cfg);
-  hipGraph_t g = nullptr;
-  e = hipStreamEndCapture(c->stream, &g);
-  c->acapture = false;
-  c->applied = applied;             // the capture ran the ticks' host bookkeeping
-  c->async_ticks = ticks;
-  c->last_pull = last;
-  if (rc != DDQ_OK) { if (g) hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-  e = hipGraphInstantiate(&c->agexec, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-  HIP_TRY(c, hipGraphUpload(c->agexec, c->stream));
-  c->acfg = *cfg;
-  c->agraph_rounds = K;
-  c->agraph_phase = async_phase(c, cfg);
+  auto& r = c->graphs.round;
+  if (r.holds(cfg)) return DDQ_OK;
+  r.reset();
+  TRY(capture_exec(c, &r.exec[0], [&]() -> int {
+    for (int k = 0; k < K; ++k) TRY(rccl_async_round(c, cfg));
+    return DDQ_OK;
+  }, "async graph"));
+  r.key(cfg);
+  r.phase = async_phase(c, cfg);
   return DDQ_OK;
 }
 
@@ -2638,10 +2666,9 @@ static int async_graph_steps(ddq_ctx* c, const ddq_step_cfg* cfg, int nsteps) {
   while (i < nsteps) {
     const bool steady = c->rr_rounds >= 1;
     if (steady && nsteps - i >= K &&
-        (c->agexec == nullptr || memcmp(&c->acfg, cfg, sizeof(*cfg)) != 0 ||
-         async_phase(c, cfg) == c->agraph_phase)) {
+        (!c->graphs.round.holds(cfg) || async_phase(c, cfg) == c->graphs.round.phase)) {
       TRY(ensure_async_graph(c, cfg, K));
-      HIP_TRY(c, hipGraphLaunch(c->agexec, c->stream));
+      HIP_TRY(c, hipGraphLaunch(c->graphs.round.exec[0], c->stream));
       TRY(after_async_graph(c));
       for (int k = 0; k < K; ++k)
         for (int w = 0; w < c->nranks; ++w) async_advance(c, w, c->applied + 1);
@@ -2675,48 +2702,29 @@ int ddq_step_async(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (c->steps == 0) TRY(initial_target_sync(c, cfg));
   c->nb.fault_k2_short = c->fault == DDQ_FAULT_MEET_TIMEOUT;   // (this step's launches only)
   c->fault = 0;
-  const int rc = enqueue_step(c, cfg, nullptr, nullptr);
+  const int rc = enqueue_step(c, cfg);
   c->nb.fault_k2_short = 0;
   TRY(rc);
-  c->steps++;
-  c->applied += step_inc(c, cfg);
+  count_steps(c, cfg, 1);
   c->idx_bound = true;
   return DDQ_OK;
 }
 
-static int capture_steps(ddq_ctx* c, const ddq_step_cfg* cfg, int k, hipGraphExec_t* out) {
-  HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = DDQ_OK;
-  for (int i = 0; i < k && rc == DDQ_OK; ++i) rc = enqueue_step(c, cfg, nullptr, nullptr);
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(c->stream, &g);
-  if (rc != DDQ_OK) { if (g) hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-  // upload now: the first launch of a never-uploaded exec pays the upload on
-  // the stream (measured ~0.3 ms in the first timed chunk otherwise)
-  HIP_TRY(c, hipGraphUpload(*out, c->stream));
-  return DDQ_OK;
-}
-
-// One graph holds kGraphSteps steps back to back (the launch of a graph
-// costs ~9 us of device idle, measured, so it is paid once per kGraphSteps
-// steps), plus a one-step graph for the remainder.  The device-side counters
-// make every captured step read its own iteration / RNG state.
-static constexpr int kGraphSteps = 8;
-
 static int ensure_graph(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (is_async(c, cfg)) return DDQ_OK;   // captured when a round starts at its phase
   TRY(check_not_async(c));
-  if (!c->have_graph || memcmp(&c->gcfg, cfg, sizeof(*cfg)) != 0) {
-    invalidate_graph(c);
-    TRY(capture_steps(c, cfg, 1, &c->gexec));
-    TRY(capture_steps(c, cfg, kGraphSteps, &c->gexec_k));
-    c->gcfg = *cfg;
-    c->have_graph = true;
-  }
+  auto& g = c->graphs.plain;
+  if (g.holds(cfg)) return DDQ_OK;
+  invalidate_graph(c);
+  auto capture = [&](hipGraphExec_t* out, int k) {
+    return capture_exec(c, out, [&]() -> int {
+      for (int i = 0; i < k; ++i) TRY(enqueue_step(c, cfg));
+      return DDQ_OK;
+    });
+  };
+  TRY(capture(&g.exec[0], 1));
+  TRY(capture(&g.exec[1], kGraphSteps));
+  g.key(cfg);
   return DDQ_OK;
 }
 
@@ -2727,18 +2735,18 @@ int ddq_step_graph_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps) {
   if (is_async(c, cfg)) return async_graph_steps(c, cfg, nsteps);
   TRY(ensure_graph(c, cfg));
   if (c->steps == 0 && nsteps > 0) TRY(initial_target_sync(c, cfg));
+  const auto& g = c->graphs.plain;
   int i = 0;
   for (; i + kGraphSteps <= nsteps; i += kGraphSteps)
-    HIP_TRY(c, hipGraphLaunch(c->gexec_k, c->stream));
-  for (; i < nsteps; ++i) HIP_TRY(c, hipGraphLaunch(c->gexec, c->stream));
+    HIP_TRY(c, hipGraphLaunch(g.exec[1], c->stream));
+  for (; i < nsteps; ++i) HIP_TRY(c, hipGraphLaunch(g.exec[0], c->stream));
   if (nsteps > 0) c->idx_bound = true;
-  c->steps += nsteps;
-  c->applied += (int64_t)nsteps * step_inc(c, cfg);
+  count_steps(c, cfg, nsteps);
   return DDQ_OK;
 }
 
 // nsteps training steps as a chain of graph replays in which step t+1's
-// sample + gather overlap step t.  Graph [p][f] trains on minibatch set p
+// sample + gather overlap step t.  Graph step(p, f) trains on minibatch set p
 // and (f = 1) prefetches into set 1-p; the chain starts on the parity that
 // makes the LAST step train on set 0, so afterwards the ctx's minibatch,
 // indices and counters are exactly those of nsteps sequential steps.
@@ -2747,22 +2755,6 @@ int ddq_step_graph_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps) {
 // not advance the counter) and every step's bookkeeping advances it, as in
 // the plain graph step; chains longer than kGraphSteps + 1 replay
 // kGraphSteps-step graphs (an even count: they start and end on set p).
-static int capture_exec(ddq_ctx* c, hipGraphExec_t* out, const std::function<int()>& body) {
-  HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = body();
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(c->stream, &g);
-  if (rc != DDQ_OK) { if (g) hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  if (e != hipSuccess) return fail(c, DDQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-  // upload now: the first launch of a never-uploaded exec pays the upload on
-  // the stream (measured ~0.3 ms in the first timed chunk otherwise)
-  HIP_TRY(c, hipGraphUpload(*out, c->stream));
-  return DDQ_OK;
-}
-
 static int ensure_pipe(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (is_async(c, cfg))
     return fail(c, DDQ_EINVAL, "the async exchange runs round-robin rounds (ddq_step_async, "
@@ -2777,40 +2769,29 @@ static int ensure_pipe(ddq_ctx* c, const ddq_step_cfg* cfg) {
     TRY(dalloc(c, &c->mb2_nonterm, (size_t)B));
     TRY(dalloc(c, &c->mb2_idx, (size_t)B));
   }
+  auto& g = c->graphs.pipe;
+  if (g.holds(cfg)) return DDQ_OK;
+  invalidate_graph(c);
   const bool fpf = fused_prefetch(c, cfg);
   ReplayMeta* bump = fpf ? c->r_meta : nullptr;
-  if (!c->have_pipe || memcmp(&c->pcfg, cfg, sizeof(*cfg)) != 0) {
-    invalidate_graph(c);
-    for (int p = 0; p < 2; ++p) {
-      for (int f = 0; f < 2; ++f) {
-        const NetBuffers cur = mb_view(c, p), nxt = mb_view(c, 1 - p);
-        TRY(capture_exec(c, &c->pexec[p][f], [&]() -> int {
-          return enqueue_train(c, cfg, cur, f ? &nxt : nullptr, nullptr, nullptr, bump);
-        }));
+  // r steps on alternating sets from set p; pf_last: the last one prefetches too
+  auto capture = [&](hipGraphExec_t* out, int p, int r, bool pf_last) {
+    return capture_exec(c, out, [&]() -> int {
+      for (int k = 0; k < r; ++k) {
+        const int q = p ^ (k & 1);
+        const NetBuffers cur = mb_view(c, q), nxt = mb_view(c, 1 - q);
+        TRY(enqueue_train(c, cfg, cur, (k + 1 < r || pf_last) ? &nxt : nullptr, {}, bump));
       }
-      if (fpf) {
-        TRY(capture_exec(c, &c->pexec_k[p], [&]() -> int {
-          for (int k = 0; k < kGraphSteps; ++k) {
-            const int q = p ^ (k & 1);
-            const NetBuffers cur = mb_view(c, q), nxt = mb_view(c, 1 - q);
-            TRY(enqueue_train(c, cfg, cur, &nxt, nullptr, nullptr, bump));
-          }
-          return DDQ_OK;
-        }));
-        for (int r = 2; r <= kGraphSteps; ++r)
-          TRY(capture_exec(c, &c->ptail[p][r], [&]() -> int {
-            for (int k = 0; k < r; ++k) {
-              const int q = p ^ (k & 1);
-              const NetBuffers cur = mb_view(c, q), nxt = mb_view(c, 1 - q);
-              TRY(enqueue_train(c, cfg, cur, k + 1 < r ? &nxt : nullptr, nullptr, nullptr, bump));
-            }
-            return DDQ_OK;
-          }));
-      }
-    }
-    c->pcfg = *cfg;
-    c->have_pipe = true;
+      return DDQ_OK;
+    });
+  };
+  for (int p = 0; p < 2; ++p) {
+    for (int f = 0; f < 2; ++f) TRY(capture(&g.step(p, f), p, 1, f));
+    if (!fpf) continue;
+    TRY(capture(&g.chain(p), p, kGraphSteps, true));
+    for (int r = 2; r <= kGraphSteps; ++r) TRY(capture(&g.tail(p, r), p, r, false));
   }
+  g.key(cfg);
   return DDQ_OK;
 }
 
@@ -2833,42 +2814,24 @@ int ddq_step_pipelined_async(ddq_ctx* c, const ddq_step_cfg* cfg, int32_t nsteps
   const bool fpf = fused_prefetch(c, cfg);
   if (c->steps == 0) TRY(initial_target_sync(c, cfg));
   c->idx_bound = true;
+  auto& g = c->graphs.pipe;
   int p = (nsteps - 1) & 1;
-  const NetBuffers first = mb_view(c, p);
-  if (c->prio_on) {
-    HIP_TRY(c, launch_prio_sample(first, c->r_meta, cfg->seed, c->stream));
-    HIP_TRY(c, launch_gather(first, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             c->stream));
-  } else if (fpf) {
-    HIP_TRY(c, launch_sample_gather(first, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                    c->r_meta, cfg->seed, c->stream));
-  } else {
-    HIP_TRY(c, launch_sample(first, c->r_meta, cfg->seed, c->stream));
-    HIP_TRY(c, launch_gather(first, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             c->stream));
-  }
+  TRY(enqueue_draw(c, mb_view(c, p), cfg->seed, c->stream));
   for (int i = 0; i < nsteps;) {
+    int r = 1;   // steps this launch takes
     if (fpf && nsteps - i > kGraphSteps) {
-      HIP_TRY(c, hipGraphLaunch(c->pexec_k[p], c->stream));   // ends on set p again
-      c->steps += kGraphSteps;
-      c->applied += (int64_t)kGraphSteps * step_inc(c, cfg);
-      i += kGraphSteps;
-      continue;
-    }
-    if (fpf && nsteps - i > 1) {   // the chain's last r steps: one graph
-      const int r = nsteps - i;
-      HIP_TRY(c, hipGraphLaunch(c->ptail[p][r], c->stream));
-      c->steps += r;
-      c->applied += (int64_t)r * step_inc(c, cfg);
+      r = kGraphSteps;
+      HIP_TRY(c, hipGraphLaunch(g.chain(p), c->stream));   // ends on set p again
+    } else if (fpf && nsteps - i > 1) {   // the chain's last r steps: one graph
+      r = nsteps - i;
+      HIP_TRY(c, hipGraphLaunch(g.tail(p, r), c->stream));
       p ^= (r - 1) & 1;   // == 0: every chain ends on set 0
-      i += r;
-      continue;
+    } else {
+      HIP_TRY(c, hipGraphLaunch(g.step(p, i + 1 < nsteps), c->stream));
+      p ^= 1;
     }
-    HIP_TRY(c, hipGraphLaunch(c->pexec[p][i + 1 < nsteps ? 1 : 0], c->stream));
-    c->steps++;
-    c->applied += step_inc(c, cfg);
-    p ^= 1;
-    ++i;
+    count_steps(c, cfg, r);
+    i += r;
   }
   return DDQ_OK;
 }
@@ -3053,18 +3016,9 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
       if (c->steps == 0) TRY(initial_target_sync(c, cfg));
       NetBuffers nb = c->nb;
       nb.book_inc = step_inc(c, cfg);
-      ReplayMeta* bump = nullptr;
-      if (nb.B <= 256) {
-        HIP_TRY(c, launch_sample_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                        c->r_meta, cfg->seed, c->stream));
-        bump = c->r_meta;
-      } else {
-        HIP_TRY(c, launch_sample(nb, c->r_meta, cfg->seed, c->stream));
-        HIP_TRY(c, launch_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                 c->r_meta, c->stream));
-      }
-      TRY(enqueue_fwd_bwd_x(c, nb, nullptr, nullptr,
-                            cfg->target_period > 0 ? cfg->target_period : 0, bump, false));
+      TRY(enqueue_draw(c, nb, cfg->seed, c->stream));
+      ReplayMeta* bump = nb.B <= 256 ? c->r_meta : nullptr;   // (the one-launch draw)
+      TRY(enqueue_fwd_bwd_x(c, nb, {}, book_period(cfg), bump, false));
     }
     TRY(record_all());
     // phase 2: exchange + (owner) apply
@@ -3125,8 +3079,7 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
       ddq_ctx* c = ctxs[r];
       TRY(set_dev(c));
       HIP_TRY(c, hipStreamSynchronize(c->stream));
-      c->steps++;
-      c->applied += step_inc(c, cfg);
+      count_steps(c, cfg, 1);
     }
     return DDQ_OK;
   }();
@@ -3292,12 +3245,11 @@ int ddq_profile_step(ddq_ctx* c, const ddq_step_cfg* cfg, char* names, float* us
   if (c->steps == 0) TRY(initial_target_sync(c, cfg));
   g_profiling = true;
   g_unmarked = 0;
-  const int rc = enqueue_step(c, cfg, mark_cb, c);
+  const int rc = enqueue_step(c, cfg, Marks{mark_cb, c});
   g_profiling = false;
   mark_settle(c);
   TRY(rc);
-  c->steps++;
-  c->applied += step_inc(c, cfg);
+  count_steps(c, cfg, 1);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (g_unmarked)   // (the step itself ran and counts)
     return fail(c, DDQ_ESTATE, "profile: %d kernel launch(es) of the step ran without a mark "
