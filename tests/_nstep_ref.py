@@ -1,7 +1,9 @@
 """n-step returns (ddq_replay_set_nstep, include/ddq_hip.h) restated in numpy /
 Python: the allowed start slots, the window and the gather over an exported
-ring, and the device index draw with the n-step predicate.  Shared by
-tests/test_nstep.py (CPU twin) and tests/test_gpu_nstep.py.
+ring, and the device index draw with the n-step predicate (the B > 64 form on
+_pool_host.wide_rounds, which also counts its rounds).  Shared by
+tests/test_nstep.py (CPU twin), tests/test_gpu_nstep.py and the large-batch
+tests (tests/test_large_batch.py, tests/test_gpu_large_batch.py).
 
 Per lane: L = lane_len, v = valid, h = head, x = the lane-local slot.  A plain
 ring is one lane of L = capacity.  R, g and w are np.float32 values and every
@@ -162,20 +164,14 @@ def draw_sorted(seed, ctr, B, head, valid, lanes, lane_len, n):
     return _slots(out, valid, lanes, lane_len)
 
 
-def draw_sorted_wide(seed, ctr, B, head, valid, lanes, lane_len, n):
+def draw_sorted_wide(seed, ctr, B, head, valid, lanes, lane_len, n, with_rounds=False):
     """The B > 64 form: sort, redraw the forbidden entries and the later ones of
-    equal neighbours with their sorted position, sort again."""
-    assert B > 64
+    equal neighbours with their sorted position, sort again (ph.wide_rounds, the
+    one loop).  with_rounds: (slots, rounds taken)."""
     draw_at, bad_x = _draw_fns(seed, ctr, head, valid, lanes, lane_len, n)
-    cand = [draw_at(0, t) for t in range(B)]
-    for rnd in range(1, ph.ROUNDS + 1):
-        cand.sort()
-        bad = [bad_x(cand[t]) or (t > 0 and cand[t] == cand[t - 1]) for t in range(B)]
-        if not any(bad):
-            break
-        assert rnd < ph.ROUNDS, "no distinct set"
-        cand = [draw_at(rnd, t) if bad[t] else cand[t] for t in range(B)]
-    return _slots(cand, valid, lanes, lane_len)
+    cand, rounds = ph.wide_rounds(draw_at, bad_x, B)
+    out = _slots(cand, valid, lanes, lane_len)
+    return (out, rounds) if with_rounds else out
 
 
 def draw(seed, ctr, B, head, valid, lanes, lane_len, n):

@@ -18,6 +18,10 @@ it -- the hash, the rank by (value, position), the redraw of forbidden values
 and of the later entries of a duplicate group with the rank as position -- on
 x in [0, lanes * valid), forbidden iff head >= 1 and x mod valid == head - 1,
 the final sorted x mapped to slots (x div valid) * lane_len + x mod valid.
+
+``wide_rounds``: the B > 64 (sort, redraw, sort again) loop, once, for this
+module's and tests/_nstep_ref.py's ``draw_sorted_wide``; it returns the round
+that found the set, which tests/test_large_batch.py holds to a cap.
 """
 import random
 
@@ -204,12 +208,11 @@ def _draw_fns(seed, ctr, head, valid, lanes):
     return draw_at, forbidden
 
 
-def draw_sorted_wide(seed, ctr, B, head, valid, lanes=1, lane_len=None):
-    """The same draw as the kernel's B > 64 path computes it: sort, redraw the
-    forbidden entries and the later ones of equal neighbours with their sorted
-    position as the hash's position input, sort again."""
+def wide_rounds(draw_at, forbidden, B):
+    """The B > 64 loop itself: (the sorted distinct x, the round that found them).
+    Round r is the r-th check of a sorted candidate set; the kernel gives up
+    after ROUNDS of them."""
     assert B > 64
-    draw_at, forbidden = _draw_fns(seed, ctr, head, valid, lanes)
     cand = [draw_at(0, t) for t in range(B)]
     for rnd in range(1, ROUNDS + 1):
         cand.sort()
@@ -218,9 +221,20 @@ def draw_sorted_wide(seed, ctr, B, head, valid, lanes=1, lane_len=None):
             break
         assert rnd < ROUNDS, "no distinct set"
         cand = [draw_at(rnd, t) if bad[t] else cand[t] for t in range(B)]
+    return cand, rnd
+
+
+def draw_sorted_wide(seed, ctr, B, head, valid, lanes=1, lane_len=None, with_rounds=False):
+    """The same draw as the kernel's B > 64 path computes it: sort, redraw the
+    forbidden entries and the later ones of equal neighbours with their sorted
+    position as the hash's position input, sort again.  with_rounds: (slots,
+    rounds taken)."""
+    draw_at, forbidden = _draw_fns(seed, ctr, head, valid, lanes)
+    cand, rounds = wide_rounds(draw_at, forbidden, B)
     if lanes > 1:
         cand = [(x // valid) * lane_len + x % valid for x in cand]
-    return np.array(cand, np.int32)
+    out = np.array(cand, np.int32)
+    return (out, rounds) if with_rounds else out
 
 
 def draw_sorted(seed, ctr, B, head, valid, lanes=1, lane_len=None):

@@ -11,6 +11,11 @@
 * RCCL with a 1-rank communicator: ticket ticks (ddq_async_tick) and the
   graph-captured round-robin rounds (ddq_step_graph_async) equal plain steps
   bit-exactly (staleness 0 at W = 1).
+
+B = 8 here.  make_group, minibatch_fn and
+world1_async_ticks_and_graph_equal_plain_steps take the batch and the ring size:
+tests/test_gpu_large_batch.py runs them at B = 264, where the worker's draw is
+two launches and the owner apply carries none.
 """
 import os
 import numpy as np
@@ -35,7 +40,7 @@ def ref():
     return ref_numpy
 
 
-def member_data(r):
+def member_data(r, N=N):
     rng = np.random.default_rng(r)
     return (rng.integers(0, 256, (N, 4, S, S)).astype(np.uint8),
             rng.integers(0, 4, N).astype(np.uint8),
@@ -43,7 +48,7 @@ def member_data(r):
             (rng.random(N) > 0.1).astype(np.uint8))
 
 
-def make_group(ddq, W, log=64):
+def make_group(ddq, W, log=64, B=B, N=N):
     from ddq.params import init_params_flat
     theta = init_params_flat(S, seed=42)
     nets, data = [], []
@@ -52,7 +57,7 @@ def make_group(ddq, W, log=64):
         n.set_flat(0, theta)
         n.set_flat(1, theta)
         n.replay_create(N)
-        d = member_data(r)
+        d = member_data(r, N)
         n.replay_import(*d, 0, N)
         n.index_log_enable(log)
         nets.append(n)
@@ -62,6 +67,8 @@ def make_group(ddq, W, log=64):
 
 
 def minibatch_fn(nets, data):
+    B, N = nets[0].batch, len(data[0][1])
+
     def mb(r, draw):
         st, ac, rw, nt = data[r]
         idx = nets[r].index_log(draw, 1)[0].astype(np.int64)
@@ -126,7 +133,7 @@ def test_group_async_refuses_other_steps_once_begun(ddq):
             n.close()
 
 
-def _world1_nets(ddq, count, seed=6):
+def _world1_nets(ddq, count, seed=6, B=B, N=N):
     from ddq.params import init_params_flat
     theta = init_params_flat(S, seed=42)
     rng = np.random.default_rng(seed)
@@ -145,12 +152,19 @@ def _world1_nets(ddq, count, seed=6):
 
 @pytest.mark.parametrize("period", [3, 0])
 def test_rccl_world1_async_ticks_and_graph_equal_plain_steps(ddq, period):
+    world1_async_ticks_and_graph_equal_plain_steps(ddq, period)
+
+
+def world1_async_ticks_and_graph_equal_plain_steps(ddq, period, B=B, N=N):
     """W = 1: staleness 0, so R pushes are R plain steps.  Net 0: ticket ticks
     (ddq_async_tick after ddq_async_ready); net 1: round-robin rounds as
     graphs (period / gcd(1, period) rounds per graph, eager rounds to align);
-    net 2: plain exchange-free steps."""
+    net 2: plain exchange-free steps.
+    (tests/test_gpu_large_batch.py runs it at B = 264 on a 700-slot ring.)
+    Returns (theta_0, the final theta_Q)."""
     R = 13
-    nets = _world1_nets(ddq, 3)
+    nets = _world1_nets(ddq, 3, B=B, N=N)
+    theta = nets[0].get_flat(0)
     try:
         for n in nets[:2]:
             n.comm_init(ddq.DeepQNet.comm_unique_id(), 1, 0)
@@ -172,6 +186,7 @@ def test_rccl_world1_async_ticks_and_graph_equal_plain_steps(ddq, period):
             np.testing.assert_array_equal(nets[1].get_flat(z), nets[2].get_flat(z))
         np.testing.assert_array_equal(nets[0].optimizer_state(), nets[2].optimizer_state())
         np.testing.assert_array_equal(nets[1].optimizer_state(), nets[2].optimizer_state())
+        return theta, nets[2].get_flat(0)
     finally:
         for n in nets:
             n.close()

@@ -12,6 +12,10 @@ ddq_exchange) against the param-server semantics of server.py:196-209.
     sharded / allreduce : theta' = apply(theta, sum_r g_r).
 * RCCL with a 1-rank communicator: every exchange (incl. the overlapped
   all-reduce inside the step graph) equals the exchange-free step bit-exactly.
+
+B = 8 here.  group_exchange_semantics and rccl_world1_exchange_equals_plain_step
+take the batch and the ring size: tests/test_gpu_large_batch.py runs them at
+B = 264, past the one-launch draw.
 """
 import numpy as np
 import pytest
@@ -67,13 +71,19 @@ def make_group(ddq, ref, W, S=16, B=8, N=120, seed=0):
 @pytest.mark.parametrize("exchange", ["server", "sharded", "allreduce"])
 @pytest.mark.parametrize("rule", ["rmsprop", "adagrad", "sgd"])
 def test_group_exchange_semantics(ddq, ref, exchange, rule):
+    group_exchange_semantics(ddq, ref, exchange, rule)
+
+
+def group_exchange_semantics(ddq, ref, exchange, rule, B=8, N=120):
+    """(tests/test_gpu_large_batch.py runs it at B = 264 on 700-slot rings.)
+    Returns the members' final theta_Q."""
     # Two steps: the second runs on the first's optimizer state.  (The lagged
     # rmsprop cache of server.py:86-105 lets a later gradient divide by an
     # earlier, tiny one -- steps of up to lr*|g|*1e4 -- so longer runs at
     # these raw-pixel gradient scales leave the finite range, in the
     # reference as here.)
     W, S, lr = 3, 16, 1e-4
-    nets, arr, theta = make_group(ddq, ref, W, S)
+    nets, arr, theta = make_group(ddq, ref, W, S, B, N)
     state = None
     for step in range(2):
         cfg = nets[0].step_cfg(rule, lr=lr, target_period=0, exchange=exchange, seed=40 + step)
@@ -116,6 +126,7 @@ def test_group_exchange_semantics(ddq, ref, exchange, rule):
             state = np.asarray(state, np.float32)
     for n in nets:
         n.close()
+    return theta
 
 
 def test_group_server_iteration_and_target_sync(ddq, ref):
@@ -138,7 +149,13 @@ def test_group_server_iteration_and_target_sync(ddq, ref):
 @pytest.mark.parametrize("exchange,overlap", [("allreduce", False), ("allreduce", True),
                                               ("sharded", False), ("server", False)])
 def test_rccl_world1_exchange_equals_plain_step(ddq, ref, exchange, overlap):
-    S, B, N = 16, 8, 96
+    rccl_world1_exchange_equals_plain_step(ddq, ref, exchange, overlap)
+
+
+def rccl_world1_exchange_equals_plain_step(ddq, ref, exchange, overlap, B=8, N=96, lr=1e-3):
+    """(tests/test_gpu_large_batch.py runs it at B = 264 on a 700-slot ring.)
+    Returns (theta_0, the final theta_Q)."""
+    S = 16
     rng = np.random.default_rng(4)
     theta = (ref.flatten(ref.init_params(S, seed=5)) * 3).astype(np.float32)
     st = rng.integers(0, 256, (N, 4, S, S)).astype(np.uint8)
@@ -153,7 +170,7 @@ def test_rccl_world1_exchange_equals_plain_step(ddq, ref, exchange, overlap):
         n.replay_import(st, ac, rw, nt, 0, N)
     nets[0].comm_init(ddq.DeepQNet.comm_unique_id(), 1, 0)
     for i, n in enumerate(nets):
-        cfg = n.step_cfg("rmsprop", lr=1e-3, target_period=3,
+        cfg = n.step_cfg("rmsprop", lr=lr, target_period=3,
                          exchange=exchange if i == 0 else "none", overlap=overlap, seed=9)
         n.step_graph(cfg, 5)
         n.step(cfg)
@@ -165,8 +182,10 @@ def test_rccl_world1_exchange_equals_plain_step(ddq, ref, exchange, overlap):
     for z in (0, 1):
         np.testing.assert_array_equal(nets[0].get_flat(z), nets[1].get_flat(z))
     np.testing.assert_array_equal(nets[0].optimizer_state(), nets[1].optimizer_state())
+    out = nets[0].get_flat(0)
     for n in nets:
         n.close()
+    return theta, out
 
 
 def _owner_state(nets):

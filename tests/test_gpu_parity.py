@@ -13,6 +13,11 @@ must match within fp32 rtol 1e-4"):
   * parameters and optimizer state: rtol 1e-4 for every element with |ref| >=
     1e-3 of the tensor's max, 1e-6 of the max below it;
   * the oracle runs in float64.
+
+The full pass runs at every frame 16..128 / 8, at B = 256 across the sweep, and
+past B = 256 at S = 16 (300) and on general frames: (24, 257), (40, 320) with
+its partial edge tiles, (64, 288) from the bench's state.
+fused_vs_separate_apply is also run by tests/test_gpu_large_batch.py at B = 264.
 """
 import glob
 import os
@@ -191,6 +196,9 @@ FULL_PASS_CASES = [
     (16, 12, "uniform", "x3"), (16, 100, "snake", "x3"),
     # S = 16 past the small-map step's B <= 256: the general kernels
     (16, 300, "snake", "x3"),
+    # general frames past B = 256: one image in the ninth 32-image group, a frame
+    # with partial edge tiles, the bench's own state
+    (24, 257, "snake", "x3"), (40, 320, "uniform", "x3"), (64, 288, "bench", "bench"),
 ]
 
 
@@ -403,7 +411,14 @@ def test_fused_apply_matches_separate_apply(ddq, ref, rule, B):
     optimizer state and P<-Q syncs over eager, pipelined and graph chains that
     cross sync steps.  B = 100: the fc4 chain's four image chunks, their
     partial sums reduced in the weight-gradient launch."""
-    S, N = 16, 300
+    fused_vs_separate_apply(ddq, ref, rule, B)
+
+
+def fused_vs_separate_apply(ddq, ref, rule, B, N=300):
+    """The body of test_fused_apply_matches_separate_apply on an N-slot ring
+    (tests/test_gpu_large_batch.py runs it at B = 264, where both nets take the
+    separate apply launch and the two-launch draw).  Returns theta_Q."""
+    S = 16
     rng = np.random.default_rng(31)
     theta = ref.flatten(ref.init_params(S, seed=8))
     st = rng.integers(0, 256, (N, 4, S, S)).astype(np.uint8)
@@ -435,6 +450,7 @@ def test_fused_apply_matches_separate_apply(ddq, ref, rule, B):
     np.testing.assert_array_equal(a.optimizer_state(), b.optimizer_state())
     np.testing.assert_array_equal(a.get_grads_flat(), b.get_grads_flat())
     assert not np.array_equal(a.get_flat(0), theta)
+    return a.get_flat(0)
 
 
 @pytest.mark.parametrize("S,rule,lr,frames", [(16, "rmsprop", 1e-4, "random"),

@@ -3,7 +3,10 @@ tests/_per_ref.py: the sum-tree draw exactly (rings of 64 to 5000 slots: three
 tree levels with ragged nodes, unfilled tails, four lanes, n = 3), the weights,
 the weighted head on the S = 16 four-launch step and the general kernels, the
 commit, the invariant under the host adds, the device actor and the actor pool,
-the three step modes byte-identical, off is off, the refusals.
+the three step modes byte-identical, off is off, the refusals.  Batches of more
+than one wave (B = 72 at S = 24, B = 100 and 256 at S = 16; rings of 5000 slots,
+four lanes and 600 slots at n = 3): the draw and the weights exactly, the commit
+with one slot repeated in every wave; the step modes and off-is-off at B = 100.
 """
 import numpy as np
 import pytest
@@ -21,6 +24,12 @@ SHAPES = [(16, 4), (16, 32), (32, 4), (32, 32)]
 RINGS = [("small", 64, 1, 40, 64, 1), ("5000", 5000, 1, 300, 300, 1),
          ("5000 full", 5000, 1, 4990, 5000, 1), ("laned 4x200", 800, 4, 100, 100, 1),
          ("n3", 130, 1, 7, 130, 3)]
+# batches of more than one wave (the draw's cross-wave minimum, the commit's scan
+# for a later b on the same slot, the 256-thread descent) and the small-map
+# step's four image chunks, on rings with room for them
+WIDE_SHAPES = [(16, 100), (16, 256), (24, 72)]
+WIDE_RINGS = [r for r in RINGS if r[0] in ("5000 full", "laned 4x200")] + \
+    [("n3 600", 600, 1, 7, 600, 3)]
 _RING = {}
 
 
@@ -79,8 +88,18 @@ def spread_leaves(allowed):
 # 1, 2 --------------------------------------------------------------- draw, weights
 @pytest.mark.parametrize("S,batch", SHAPES)
 def test_draw_and_weights_are_the_restatement(ddq, S, batch):
+    draw_and_weights(ddq, S, batch, RINGS)
+
+
+@pytest.mark.parametrize("S,batch", WIDE_SHAPES)
+def test_draw_and_weights_across_waves(ddq, S, batch):
+    """The descent on 128 and 256 threads, the minimum leaf taken across waves."""
+    draw_and_weights(ddq, S, batch, WIDE_RINGS)
+
+
+def draw_and_weights(ddq, S, batch, rings):
     dup = False
-    for name, cap, lanes, head, valid, n in RINGS:
+    for name, cap, lanes, head, valid, n in rings:
         L = cap // lanes
         ring = ring_for(cap, S)
         net = make_net(ddq, S, batch, ring, head, valid, lanes, n, PRIO)
@@ -170,9 +189,24 @@ def test_weight_one_is_the_unweighted_pass(ddq, S, batch):
 # 4 ------------------------------------------------------------------ the commit
 @pytest.mark.parametrize("S,batch", SHAPES)
 def test_commit_of_one_eager_step(ddq, S, batch):
-    ring = ring_for(130, S)
-    net = make_net(ddq, S, batch, ring, 7, 130, prio=PRIO)
-    allowed = nr.allowed_slots(7, 130, 130, 1)
+    commit_of_one_eager_step(ddq, S, batch, 130)
+
+
+@pytest.mark.parametrize("S,batch", WIDE_SHAPES)
+def test_commit_across_waves(ddq, S, batch):
+    """One slot fills most of the batch in every wave: the commit's scan for a
+    later b on the same slot crosses waves (the copies carry the same TD error,
+    so what pr.check_commit holds is one leaf written once, total and pmax
+    consistent), and the draw's minimum leaf is taken across the waves."""
+    idx = commit_of_one_eager_step(ddq, S, batch, 600)
+    waves = {b // 64 for b in range(batch) if idx[b] == 50}
+    assert waves == set(range((batch + 63) // 64)), waves
+
+
+def commit_of_one_eager_step(ddq, S, batch, cap):
+    ring = ring_for(cap, S)
+    net = make_net(ddq, S, batch, ring, 7, cap, prio=PRIO)
+    allowed = nr.allowed_slots(7, cap, cap, 1)
     set_leaves(net, {i: (pr.QMAX if i == 50 else 1) for i in allowed})
     q0, _, pmax0 = net.replay_priorities()
     net.step(net.step_cfg("sgd", lr=1e-6, target_period=5, seed=SEED))
@@ -184,6 +218,7 @@ def test_commit_of_one_eager_step(ddq, S, batch):
                     net.blob("target_Q_sa").reshape(batch), PRIO["eps"], PRIO["alpha"],
                     "S%d B%d" % (S, batch))
     done(net)
+    return idx
 
 
 def test_commit_does_not_resurrect_a_forbidden_slot(ddq):
@@ -346,13 +381,15 @@ def chain(ddq, S, batch, mode, prio):
     return out
 
 
-@pytest.mark.parametrize("S,batch", [(16, 32), (32, 4)])
+# (16, 100): the small-map step's four image chunks, then prio_commit on two waves
+@pytest.mark.parametrize("S,batch", [(16, 32), (32, 4), (16, 100)])
 def test_step_modes_agree(ddq, S, batch):
     eager = chain(ddq, S, batch, "eager", PRIO)
     q, total, pmax = eager["prio"]
     assert total == int(q.astype(np.int64).sum()) and eager["draws"] == STEPS
     pr.check_invariant(q, total, 7, 130, 130, 1)
-    assert len(set(q.tolist())) > 3 * batch // 2            # the chain committed
+    # the chain committed (B = 100: the ring has 129 leaves, half of them distinct)
+    assert len(set(q.tolist())) > min(3 * batch // 2, 64)
     for mode in ("graph", "pipelined"):
         other = chain(ddq, S, batch, mode, PRIO)
         for a, b in zip(eager["state"], other["state"]):
@@ -404,7 +441,7 @@ def test_act_and_train_is_the_eager_sequence(ddq):
 
 
 # 7 ------------------------------------------------------------------ off is off
-@pytest.mark.parametrize("S,batch", [(16, 32), (32, 4)])
+@pytest.mark.parametrize("S,batch", [(16, 32), (32, 4), (16, 100)])
 def test_off_is_off(ddq, S, batch):
     for mode in ("eager", "graph", "pipelined"):
         never, back = chain(ddq, S, batch, mode, None), chain(ddq, S, batch, mode, "off")
@@ -413,8 +450,9 @@ def test_off_is_off(ddq, S, batch):
         assert never["log"].tobytes() == back["log"].tobytes(), mode
         for a, b in zip(never["mb"], back["mb"]):
             assert a.tobytes() == b.tobytes(), mode
+    draw = ph.draw_sorted if batch <= 64 else ph.draw_sorted_wide
     for d in range(STEPS):
-        np.testing.assert_array_equal(never["log"][d], ph.draw_sorted(11, d, batch, 7, 130))
+        np.testing.assert_array_equal(never["log"][d], draw(11, d, batch, 7, 130))
     names = []
     for toggle in (False, True):
         net = make_net(ddq, S, batch, ring_for(130, S), 7, 130)

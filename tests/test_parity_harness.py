@@ -278,7 +278,7 @@ def test_nan_and_inf_are_mismatches():
 # time with the oracle: every FULL_PASS_CASES and pair case of at most
 # 16 * 16 * 300 input pixels per tower (about half a second each).  Left to the
 # assertion in ``close`` alone: FULL_PASS_CASES (64, 32, uniform), (64, 32,
-# bench) and the seven B = 256 cases at S >= 24.
+# bench), the seven B = 256 cases at S >= 24 and the three B > 256 cases there.
 def cheap(S, B):
     return S * S * B <= 16 * 16 * 300
 
@@ -295,8 +295,9 @@ def seeded_cases():
 
 def test_seeded_case_lists_are_covered():
     left = sorted((S, B, fr) for (S, B, fr, _) in FULL_PASS_CASES if not cheap(S, B))
-    assert left == [(24, 256, "snake"), (40, 256, "snake"), (64, 32, "bench"),
-                    (64, 32, "uniform"), (64, 256, "bench"), (72, 256, "uniform"),
+    assert left == [(24, 256, "snake"), (24, 257, "snake"), (40, 256, "snake"),
+                    (40, 320, "uniform"), (64, 32, "bench"), (64, 32, "uniform"),
+                    (64, 256, "bench"), (64, 288, "bench"), (72, 256, "uniform"),
                     (104, 256, "snake"), (120, 256, "snake"), (128, 256, "snake")]
     assert all(cheap(S, B) for (S, B, _, _), seed in seeded_cases() if seed is not None)
 
