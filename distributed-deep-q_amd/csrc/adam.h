@@ -150,9 +150,9 @@ hipError_t launch_grad_norm(const NetBuffers& nb, hipStream_t s) {
 }
 
 // launch_apply's Adam branch (after its bookkeeping launch, if any)
-hipError_t launch_adam_apply(const NetBuffers& nb, const ApplyArgs& a, const Prefetch& pf,
-                             hipStream_t s) {
-  if (!nb.opt2 || !nb.gn_part || !nb.gnorm || nb.fa.on) return hipErrorInvalidValue;
+hipError_t launch_adam_apply(const NetBuffers& nb, const StepPlan& plan, const ApplyArgs& a,
+                             const Prefetch& pf, hipStream_t s) {
+  if (!nb.opt2 || !nb.gn_part || !nb.gnorm || plan.fused()) return hipErrorInvalidValue;
   AdamArgs ad;
   ad.beta1 = nb.adam_beta1; ad.beta2 = nb.adam_beta2;
   ad.omb1 = (float)(1.0 - (double)nb.adam_beta1);

@@ -400,7 +400,6 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* desc) {
     // floats cover P for every W <= kMaxRanks
     TRY(dalloc(c, &nb.grad, (size_t)P + kShardPad));
     TRY(dalloc(c, &nb.opt, (size_t)P + kShardPad));
-    nb.book_inc = 1;
     TRY(dalloc(c, &nb.opt_init, 4));
     TRY(dalloc(c, &nb.iter, 1));
     // acting scratch (n <= B)
@@ -1258,33 +1257,47 @@ static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
   return DDQ_OK;
 }
 
-// book >= 0: this backward feeds a step's apply; its slab reduce also does
-// the apply bookkeeping with target period `book` (saves a launch).
-static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, Marks m = {}, int book = -1,
-                           ReplayMeta* bump = nullptr) {
+// The gradient launches of a step as sl.plan has them; fc4_done: the
+// overlapped all-reduce's start (launch_backward).
+// (one stream: forking the weight-gradient kernels onto a side stream cost
+// more in cross-stream graph edges (6-14 us idle each, measured) than the
+// overlap returned, as every kernel here fills the GPU on its own)
+static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, const StepLaunch& sl, Marks m = {},
+                           hipError_t (*fc4_done)(void*) = nullptr, const NetBuffers* prio_next = nullptr,
+                           uint64_t prio_seed = 0) {
   TRY(enqueue_qn_forward(c, nb, m));
   if (nb.small) {
-    HIP_TRY(c, launch_small_fwd_head(nb, c->stream, m.fn, m.arg));
+    HIP_TRY(c, launch_small_fwd_head(nb, sl, c->stream, m.fn, m.arg));
   } else {
     HIP_TRY(c, launch_forward(nb, 2, c->stream, m.fn, m.arg, false));
     m("head");
-    HIP_TRY(c, launch_head(nb, c->stream));
+    HIP_TRY(c, launch_head(nb, sl, c->stream));
   }
-  // one stream: forking the weight-gradient kernels onto a side stream cost
-  // more in cross-stream graph edges (6-14 us idle each, measured) than the
-  // overlap returned, as every kernel here fills the GPU on its own
-  if (nb.small)
-    HIP_TRY(c, launch_small_bwd(nb, c->stream, m.fn, m.arg, book >= 0, book, bump, nullptr, nullptr,
-                                nullptr));
-  else
-    HIP_TRY(c, launch_backward(nb, c->stream, m.fn, m.arg, book >= 0, book, bump));
+  // prioritized replay: right after the launch that wrote Q_sa and target_Q_sa,
+  // one workgroup commits this step's |TD|, moves the counter on and, when a
+  // next step is being prefetched, draws its index set and weights
+  if (sl.plan.prio_commit) {
+    m("prio_commit");
+    HIP_TRY(c, launch_prio_commit_draw(nb, sl.meta, sl.plan.draw == Site::PrioCommit ? prio_next : nullptr,
+                                       prio_seed, c->stream));
+  }
+  hipError_t e = nb.small ? launch_small_bwd(nb, sl, c->stream, m.fn, m.arg, fc4_done, c)
+                          : launch_backward(nb, sl, c->stream, m.fn, m.arg, fc4_done, c);
+  if (e != hipSuccess && !c->comm_err.empty()) {
+    std::string m = c->comm_err;
+    c->comm_err.clear();
+    return fail(c, DDQ_ERCCL, "overlapped all-reduce: %s", m.c_str());
+  }
+  HIP_TRY(c, e);
   return DDQ_OK;
 }
 
 int ddq_forward_backward_async(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(set_dev(c));
-  return enqueue_fwd_bwd(c, c->nb);
+  StepLaunch sl;
+  sl.plan = plan_grad_only();
+  return enqueue_fwd_bwd(c, c->nb, sl);
 }
 
 int ddq_forward_backward(ddq_ctx* c, float* loss) {
@@ -1742,16 +1755,17 @@ static int check_cfg(ddq_ctx* c, const ddq_update_cfg* u) {
 // The apply launch of one update (every caller of launch_apply).  Adam with
 // clipping on: the gradient-norm launch first, over the buffer the apply reads
 // (under all-reduce: the summed gradient).
-static int enqueue_apply(ddq_ctx* c, const NetBuffers& nb, const ddq_update_cfg& u, int period,
-                         bool booked, const Prefetch* pf = nullptr, Marks m = {}) {
-  const bool adam = u.rule == DDQ_RULE_ADAM;
+static UpdateRule rule_of(const ddq_update_cfg& u, int period) {
+  return UpdateRule{u.rule, period, u.lr, u.decay, u.eps, u.momentum, u.weight_decay};
+}
+static int enqueue_apply(ddq_ctx* c, const NetBuffers& nb, const StepLaunch& sl, Marks m = {}) {
+  const bool adam = sl.u.rule == DDQ_RULE_ADAM;
   if (adam && nb.adam_clip > 0.f) {
     m("grad_norm");
     HIP_TRY(c, launch_grad_norm(nb, c->stream));
   }
   m(adam ? "adam_apply" : "apply");
-  HIP_TRY(c, launch_apply(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay, period,
-                          booked, c->stream, pf));
+  HIP_TRY(c, launch_apply(nb, sl, c->stream));
   return DDQ_OK;
 }
 
@@ -1759,7 +1773,10 @@ int ddq_apply_async(ddq_ctx* c, const ddq_update_cfg* u) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(check_cfg(c, u));
   TRY(set_dev(c));
-  TRY(enqueue_apply(c, c->nb, *u, 0, false));
+  StepLaunch sl;
+  sl.plan = plan_apply_only();
+  sl.u = rule_of(*u, 0);
+  TRY(enqueue_apply(c, c->nb, sl));
   c->applied++;
   return DDQ_OK;
 }
@@ -1947,48 +1964,47 @@ static hipError_t fc4_bucket_start(void* arg) {
   return hipEventRecord(c->cev[2], c->cs);
 }
 
-static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, Marks m, int book, ReplayMeta* bump,
-                             bool overlap, const Prefetch* pf = nullptr,
-                             const NetBuffers* prio_next = nullptr, uint64_t prio_seed = 0) {
-  TRY(enqueue_qn_forward(c, nb, m));
-  if (nb.small) {
-    HIP_TRY(c, launch_small_fwd_head(nb, c->stream, m.fn, m.arg, bump, nb.fa.on ? pf : nullptr));
-  } else {
-    HIP_TRY(c, launch_forward(nb, 2, c->stream, m.fn, m.arg, false));
-    m("head");
-    // fused apply: the draw counter advances here (pipelined: with the next
-    // step's draw, kernels.hip head_draw)
-    HIP_TRY(c, launch_head(nb, c->stream, bump, nb.fa.on ? pf : nullptr));
-  }
-  // prioritized replay: right after the launch that wrote Q_sa and target_Q_sa,
-  // one workgroup commits this step's |TD|, advances the draw counter and, when
-  // a next step is being prefetched, draws its index set and weights (the
-  // prefetch blocks below then gather with predrawn = 1)
-  if (nb.prio.leaf && bump) {
-    m("prio_commit");
-    HIP_TRY(c, launch_prio_commit_draw(nb, bump, prio_next, prio_seed, c->stream));
-  }
-  // the draw counter advances once per step: without the fused apply the slab
-  // reduce's bookkeeping would advance it (apply_book's bump), but on a
-  // prioritized step the commit launch above already has (an Adam step)
-  ReplayMeta* bbump = (nb.prio.leaf && !nb.fa.on) ? nullptr : bump;
-  hipError_t e = nb.small ? launch_small_bwd(nb, c->stream, m.fn, m.arg, book >= 0, book, bbump,
-                                             overlap ? fc4_bucket_start : nullptr, c, pf)
-                          : launch_backward(nb, c->stream, m.fn, m.arg, book >= 0, book, bbump,
-                                            overlap ? fc4_bucket_start : nullptr, c, pf);
-  if (e != hipSuccess && !c->comm_err.empty()) {
-    std::string m = c->comm_err;
-    c->comm_err.clear();
-    return fail(c, DDQ_ERCCL, "overlapped all-reduce: %s", m.c_str());
-  }
-  HIP_TRY(c, e);
+// What a step of (ctx, cfg) is, for plan_step.
+static StepFacts step_facts(const ddq_ctx* c, const ddq_step_cfg* cfg) {
+  StepFacts f;
+  const int ex = has_exchange(c, cfg) ? cfg->exchange : DDQ_EXCHANGE_NONE;
+  f.small = c->nb.small;
+  f.b_le_256 = c->nb.B <= 256;
+  f.prio = c->nb.prio.leaf != nullptr;
+  f.adam = cfg->update.rule == DDQ_RULE_ADAM;
+  // (an Adam step's all-reduce is one call on the ctx stream: cfg->overlap is
+  // for the fused fc4 apply, which Adam does not take)
+  f.ex = ex == DDQ_EXCHANGE_ALLREDUCE
+             ? (cfg->overlap && c->comm && !f.adam ? Exchange::AllReduceOverlap : Exchange::AllReduce)
+         : ex == DDQ_EXCHANGE_SHARDED ? Exchange::Sharded
+         : ex == DDQ_EXCHANGE_SERVER  ? Exchange::Server
+         : ex == DDQ_EXCHANGE_ASYNC   ? Exchange::AsyncWorker
+                                      : Exchange::None;
+  f.fused_apply_ok = fused_apply_ok(c->nb.L);
+  f.no_grad_store = (cfg->flags & DDQ_STEP_NO_GRAD_STORE) != 0;
+  // (only the two-launch draw moved the counter on itself: enqueue_draw)
+  f.holds_counter = c->prio_on || c->nb.B <= 256;
+  // (the owners keep the async exchange's iteration)
+  const bool worker = f.ex == Exchange::AsyncWorker;
+  f.book_period = worker ? -1 : book_period(cfg);
+  f.book_step = worker ? 1 : step_inc(c, cfg);
+  return f;
+}
+
+// The plan of a step with these facts and what its launches need of the ctx.
+static int plan_launches(ddq_ctx* c, const ddq_step_cfg* cfg, const StepFacts& f, StepLaunch* sl) {
+  const char* why = "";
+  if (!plan_step(f, &sl->plan, &why)) return fail(c, DDQ_ESTATE, "internal: %s", why);
+  sl->u = rule_of(cfg->update, cfg->target_period);
+  sl->meta = c->r_meta;
+  sl->fc4_wait = sl->plan.ext() ? c->cev[2] : nullptr;
   return DDQ_OK;
 }
 
 // Gradient exchange + apply of one step over RCCL (graph-capturable):
 //  ALLREDUCE  sum all-reduce, replicated apply (overlap: fc4 bucket on the
 //             comm stream under the conv backward, applied by the slab-reduce
-//             launch (nb.fa.ext); the rest -- conv layers, fc4 bias, Q_out --
+//             launch (StepPlan::ext); the rest -- conv layers, fc4 bias, Q_out --
 //             as one grouped call after the slab reduce, then their apply);
 //  SHARDED    reduce-scatter(sum) -> owner apply of its 1/W shard ->
 //             in-place all-gather of theta -> conv layouts / P <- Q refresh;
@@ -1996,16 +2012,15 @@ static int enqueue_fwd_bwd_x(ddq_ctx* c, const NetBuffers& nb, Marks m, int book
 //             one by one in rank order (server.py:196-209 on arrival) ->
 //             all-gather -> refresh.
 static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb,
-                                  Marks m, bool overlap, const Prefetch* pf = nullptr) {
-  const ddq_update_cfg& u = cfg->update;
+                                  const StepLaunch& sl, Marks m, bool overlap) {
   const ParamLayout& L = nb.L;
   const int ex = has_exchange(c, cfg) ? cfg->exchange : DDQ_EXCHANGE_NONE;
   if (ex == DDQ_EXCHANGE_NONE || ex == DDQ_EXCHANGE_ALLREDUCE) {
     if (ex == DDQ_EXCHANGE_ALLREDUCE) {
       m("allreduce");
-      if (overlap && nb.fa.on) {
+      if (sl.plan.ext()) {
         // fc4's weights were summed under the conv backward and applied by
-        // the slab-reduce launch (nb.fa.ext), whose stream waited for that
+        // the slab-reduce launch, whose stream waited for that
         // all-reduce: the rest (4 % of the parameters) right here on the ctx
         // stream -- nothing is left to overlap it with, and a comm-stream
         // round trip costs a graph fork / join (measured 0.968 against 0.995
@@ -2032,7 +2047,7 @@ static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const Net
                                   c->stream));
       }
     }
-    return enqueue_apply(c, nb, u, cfg->target_period, true, pf, m);
+    return enqueue_apply(c, nb, sl, m);
   }
   const int W = c->nranks;
   const size_t len = (size_t)c->shard_len;
@@ -2051,12 +2066,13 @@ static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const Net
     NCCL_TRY(c, ncclGroupEnd());
   }
   m("apply_shard");
-  HIP_TRY(c, launch_apply_shard(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
-                                c->gsl, (int64_t)c->rank * len, (int64_t)len, (int64_t)len,
-                                ex == DDQ_EXCHANGE_SHARDED ? 1 : W, c->stream, nullptr, -1, pf,
-                                nullptr, -1, c->rank,
-                                ex == DDQ_EXCHANGE_SHARDED ? nullptr
-                                                           : nb.grad + (size_t)c->rank * len));
+  ShardOpts o;
+  if (sl.plan.gather == Site::OwnerApply) o.pre = sl.next;
+  o.refresh_own = -1;
+  o.own_w = c->rank;
+  o.own_g = ex == DDQ_EXCHANGE_SHARDED ? nullptr : nb.grad + (size_t)c->rank * len;
+  HIP_TRY(c, launch_apply_shard(nb, sl.u, c->gsl, (int64_t)c->rank * len, (int64_t)len,
+                                (int64_t)len, ex == DDQ_EXCHANGE_SHARDED ? 1 : W, c->stream, o));
   m("all_gather");
   NCCL_TRY(c, ncclAllGather(nb.theta[0] + (size_t)c->rank * len, nb.theta[0], len, ncclFloat,
                             c->comm, c->stream));
@@ -2091,80 +2107,42 @@ static int enqueue_draw(ddq_ctx* c, const NetBuffers& nb, uint64_t seed, hipStre
   return DDQ_OK;
 }
 
-// fwd/bwd -> exchange -> apply on the minibatch held by `nb`; when `pre` is
-// given, the NEXT step's sample + gather into `pre`'s minibatch set run on
-// the side stream under this step's forward (the replay ring is not written
-// inside a step, and the device RNG counter advances in the same order, so
-// the index stream equals the sequential one).
-// Pipelined steps whose next draw + gather ride on the apply launch (no side
-// stream): exchanges that end in the plain apply kernel, B <= 256.
-// (sharded / server: on the owner-apply launch, after the slab reduce's
-// bookkeeping advanced the draw counter)
+// Pipelined steps whose next draw + gather ride on launches of the step (no
+// side stream): every exchange but the async one, B <= 256 (StepPlan::gather).
 static bool fused_prefetch(const ddq_ctx* c, const ddq_step_cfg* cfg) {
-  const int ex = has_exchange(c, cfg) ? cfg->exchange : DDQ_EXCHANGE_NONE;
-  return ex != DDQ_EXCHANGE_ASYNC && c->nb.B <= 256;
+  return !is_async(c, cfg) && c->nb.B <= 256;
 }
 
-static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
-                              const NetBuffers* pre, Marks m, ReplayMeta* bump) {
-  NetBuffers nb = nb_in;
-  nb.book_inc = step_inc(c, cfg);
-  // exchange-free steps: fc4's weight update rides on the slab-reduce launch
-  const int ex = has_exchange(c, cfg) ? cfg->exchange : DDQ_EXCHANGE_NONE;
-  // (an Adam step's all-reduce is one call on the ctx stream: cfg->overlap is
-  // for the fused fc4 apply, which Adam does not take)
-  const bool ar_overlap = ex == DDQ_EXCHANGE_ALLREDUCE && cfg->overlap && c->comm &&
-                          cfg->update.rule != DDQ_RULE_ADAM;
-  // (deepq16: fc4's parameters are final and applied inside the fc4 chain,
-  // K2, before any bucket could be summed: the overlapped all-reduce takes the
-  // plain apply launch there)
-  // (Adam keeps two state words: its update is a launch of its own after the
-  // gradient launches, the sequencing of an exchanged step; fc4's gradient is
-  // then stored whatever DDQ_STEP_NO_GRAD_STORE says)
-  const bool adam = cfg->update.rule == DDQ_RULE_ADAM;
-  if (!adam && (ex == DDQ_EXCHANGE_NONE || (ar_overlap && !nb.small)) && fused_apply_ok(nb.L)) {
-    const ddq_update_cfg& u = cfg->update;
-    nb.fa.on = 1;
-    nb.fa.ext = ar_overlap ? 1 : 0;
-    nb.fa.store_grad = ar_overlap || !(cfg->flags & DDQ_STEP_NO_GRAD_STORE);
-    nb.fc4_wait = ar_overlap ? c->cev[2] : nullptr;
-    nb.fa.rule = u.rule;
-    nb.fa.period = book_period(cfg);
-    nb.fa.lr = u.lr; nb.fa.decay = u.decay; nb.fa.eps = u.eps;
-    nb.fa.momentum = u.momentum; nb.fa.wd = u.weight_decay;
+// fwd/bwd -> exchange -> apply on the minibatch held by `nb`, as the step's
+// plan has it; when `pre` is given, the NEXT step's sample + gather into
+// `pre`'s minibatch set run beside this step (the replay ring is not written
+// inside a step, and the device RNG counter moves on in the same order, so
+// the index stream equals the sequential one).
+// fault: ddq_inject_fault's meeting timeout, for this step's launches only
+static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb,
+                              const NetBuffers* pre, Marks m, bool fault) {
+  StepFacts f = step_facts(c, cfg);
+  f.prefetch = pre != nullptr;
+  f.fault_k2_short = fault;
+  StepLaunch sl;
+  TRY(plan_launches(c, cfg, f, &sl));
+  const bool side = sl.plan.draw == Site::Side, overlap = f.ex == Exchange::AllReduceOverlap;
+  Prefetch pf;
+  if (on_ctx_stream(sl.plan.gather)) {
+    pf = make_prefetch(*pre, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
+                       cfg->seed);
+    pf.predrawn = sl.plan.predrawn();
+    sl.next = &pf;
   }
-  // Not a refusal of the contract but an invariant: while prioritization is on
-  // every exchange is refused (check_step), so ex is NONE; fused_apply_ok holds
-  // for every layout make_layout builds; and every caller of a prioritized step
-  // passes the draw counter (B <= 256, no async exchange).  Were one of these
-  // ever to change, the step would commit with no counter to advance: stop.
-  // An Adam step is the one prioritized step without the fused apply: its commit
-  // launch advances the counter (and draws the next set), the slab reduce's
-  // bookkeeping then does not (enqueue_fwd_bwd_x), and the apply launch's
-  // prefetch blocks gather the set the commit launch drew (predrawn).
-  if (nb.prio.leaf && (!(nb.fa.on || adam) || !bump))
-    return fail(c, DDQ_ESTATE, "internal: a prioritized step without the fused apply or the draw "
-                               "counter");
-  if (pre && fused_prefetch(c, cfg)) {
-    // the step's bookkeeping advances the draw counter (bump) before the apply
-    // launch draws the next minibatch with it
-    Prefetch pf = make_prefetch(*pre, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                c->r_meta, cfg->seed);
-    if (nb.prio.leaf && !nb.fa.on) pf.predrawn = 1;
-    // fused apply: the slab-reduce launch carries the draw + gather too
-    TRY(enqueue_fwd_bwd_x(c, nb, m, book_period(cfg), c->r_meta, ar_overlap,
-                          nb.fa.on ? &pf : nullptr, pre, cfg->seed));
-    return enqueue_exchange_apply(c, cfg, nb, m, ar_overlap, nb.fa.on ? nullptr : &pf);
-  }
-  if (pre) {   // (B > 256: the two-launch draw)
+  if (side) {
     HIP_TRY(c, hipEventRecord(nb.ev[6], c->stream));
     HIP_TRY(c, hipStreamWaitEvent(nb.side, nb.ev[6], 0));
     TRY(enqueue_draw(c, *pre, cfg->seed, nb.side));
     HIP_TRY(c, hipEventRecord(nb.ev[7], nb.side));
   }
-  TRY(enqueue_fwd_bwd_x(c, nb, m, book_period(cfg), bump, ar_overlap, nullptr, nullptr, cfg->seed));
-  TRY(enqueue_exchange_apply(c, cfg, nb, m, ar_overlap));
-  if (pre) HIP_TRY(c, hipStreamWaitEvent(c->stream, nb.ev[7], 0));
+  TRY(enqueue_fwd_bwd(c, nb, sl, m, overlap ? fc4_bucket_start : nullptr, pre, cfg->seed));
+  TRY(enqueue_exchange_apply(c, cfg, nb, sl, m, overlap));
+  if (side) HIP_TRY(c, hipStreamWaitEvent(c->stream, nb.ev[7], 0));
   return DDQ_OK;
 }
 
@@ -2172,9 +2150,9 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
 // launch: loss_t, g_t and the parameters after update t; the kernel itself
 // tests the device iteration against the period, so the launch is the same
 // every step and replays from a captured graph.
-static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb_in,
-                         const NetBuffers* pre, Marks m, ReplayMeta* bump) {
-  TRY(enqueue_train_body(c, cfg, nb_in, pre, m, bump));
+static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& nb,
+                         const NetBuffers* pre, Marks m, bool fault = false) {
+  TRY(enqueue_train_body(c, cfg, nb, pre, m, fault));
   if (c->mon.ring && c->mon_period > 0) {
     m("monitor");
     HIP_TRY(c, launch_monitor(c->mon, c->mon_period, -1, c->stream));
@@ -2182,11 +2160,9 @@ static int enqueue_train(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuffers& 
   return DDQ_OK;
 }
 
-static int enqueue_step(ddq_ctx* c, const ddq_step_cfg* cfg, Marks m = {}) {
+static int enqueue_step(ddq_ctx* c, const ddq_step_cfg* cfg, Marks m = {}, bool fault = false) {
   TRY(enqueue_draw(c, c->nb, cfg->seed, c->stream, m));
-  // (only the two-launch draw advanced the draw counter itself)
-  const bool bump = c->prio_on || c->nb.B <= 256;
-  return enqueue_train(c, cfg, c->nb, nullptr, m, bump ? c->r_meta : nullptr);
+  return enqueue_train(c, cfg, c->nb, nullptr, m, fault);
 }
 
 // minibatch set p: 0 = the ctx's own buffers, 1 = the pipelining twin
@@ -2269,11 +2245,10 @@ static int check_monitor_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
 // drawn: the minibatch was drawn + gathered already (by the owner apply of
 // this worker's own push, async_owner_apply)
 static int async_compute(ddq_ctx* c, const ddq_step_cfg* cfg, bool drawn = false) {
-  NetBuffers nb = c->nb;
-  const bool one = nb.B <= 256;   // one draw + gather launch; the head advances the counter
-  nb.head_bump = one;
-  if (!drawn) TRY(enqueue_draw(c, nb, cfg->seed, c->stream));
-  TRY(enqueue_fwd_bwd_x(c, nb, {}, -1, one ? c->r_meta : nullptr, false));
+  StepLaunch sl;
+  TRY(plan_launches(c, cfg, step_facts(c, cfg), &sl));
+  if (!drawn) TRY(enqueue_draw(c, c->nb, cfg->seed, c->stream));
+  TRY(enqueue_fwd_bwd(c, c->nb, sl));
   HIP_TRY(c, hipEventRecord(c->grad_ev, c->stream));
   c->ready_seen = false;
   c->grad_ev_captured = c->acapture;
@@ -2338,10 +2313,13 @@ static int async_owner_apply(ddq_ctx* c, const ddq_step_cfg* cfg, int64_t it, bo
   if (draw)
     pf = make_prefetch(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
                        cfg->seed);
-  HIP_TRY(c, launch_apply_shard(c->nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
-                                g, off, L, L, 1, c->cs, c->own, c->applied == 0 ? 1 : 0,
-                                draw ? &pf : nullptr, own ? c->nb.theta[0] : nullptr,
-                                own ? (async_p_now(cfg, it) ? 2 : 1) : 0));
+  ShardOpts o;
+  o.theta = c->own;
+  o.first = c->applied == 0 ? 1 : 0;
+  o.pre = draw ? &pf : nullptr;
+  o.mirror = own ? c->nb.theta[0] : nullptr;
+  o.refresh_own = own ? (async_p_now(cfg, it) ? 2 : 1) : 0;
+  HIP_TRY(c, launch_apply_shard(c->nb, rule_of(u, 0), g, off, L, L, 1, c->cs, o));
   if (async_p_now(cfg, it))
     HIP_TRY(c, hipMemcpyAsync(c->pown + off, c->own + off, L * 4, hipMemcpyDeviceToDevice, c->cs));
   return DDQ_OK;
@@ -2700,11 +2678,9 @@ int ddq_step_async(ddq_ctx* c, const ddq_step_cfg* cfg) {
   }
   TRY(check_not_async(c));
   if (c->steps == 0) TRY(initial_target_sync(c, cfg));
-  c->nb.fault_k2_short = c->fault == DDQ_FAULT_MEET_TIMEOUT;   // (this step's launches only)
+  const bool fault = c->fault == DDQ_FAULT_MEET_TIMEOUT;
   c->fault = 0;
-  const int rc = enqueue_step(c, cfg);
-  c->nb.fault_k2_short = 0;
-  TRY(rc);
+  TRY(enqueue_step(c, cfg, {}, fault));
   count_steps(c, cfg, 1);
   c->idx_bound = true;
   return DDQ_OK;
@@ -2773,14 +2749,13 @@ static int ensure_pipe(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (g.holds(cfg)) return DDQ_OK;
   invalidate_graph(c);
   const bool fpf = fused_prefetch(c, cfg);
-  ReplayMeta* bump = fpf ? c->r_meta : nullptr;
   // r steps on alternating sets from set p; pf_last: the last one prefetches too
   auto capture = [&](hipGraphExec_t* out, int p, int r, bool pf_last) {
     return capture_exec(c, out, [&]() -> int {
       for (int k = 0; k < r; ++k) {
         const int q = p ^ (k & 1);
         const NetBuffers cur = mb_view(c, q), nxt = mb_view(c, 1 - q);
-        TRY(enqueue_train(c, cfg, cur, (k + 1 < r || pf_last) ? &nxt : nullptr, {}, bump));
+        TRY(enqueue_train(c, cfg, cur, (k + 1 < r || pf_last) ? &nxt : nullptr, {}));
       }
       return DDQ_OK;
     });
@@ -2992,9 +2967,9 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
   const int ex = cfg->exchange;
   if (ex == DDQ_EXCHANGE_ASYNC) return group_async_round(ctxs, W, cfg);
   for (int r = 0; r < W; ++r) TRY(check_not_async(ctxs[r]));
-  const ddq_update_cfg& u = cfg->update;
   const int64_t P = ctxs[0]->nb.L.total;
   std::vector<hipEvent_t> ev(W);
+  std::vector<StepLaunch> sl(W);
   auto record_all = [&](void) -> int {
     for (int r = 0; r < W; ++r) {
       ddq_ctx* c = ctxs[r];
@@ -3014,11 +2989,11 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
       ddq_ctx* c = ctxs[r];
       TRY(set_dev(c));
       if (c->steps == 0) TRY(initial_target_sync(c, cfg));
-      NetBuffers nb = c->nb;
-      nb.book_inc = step_inc(c, cfg);
-      TRY(enqueue_draw(c, nb, cfg->seed, c->stream));
-      ReplayMeta* bump = nb.B <= 256 ? c->r_meta : nullptr;   // (the one-launch draw)
-      TRY(enqueue_fwd_bwd_x(c, nb, {}, book_period(cfg), bump, false));
+      StepFacts f = step_facts(c, cfg);
+      f.fused_apply_ok = false;   // (the apply is phase 2, after the members' exchange)
+      TRY(plan_launches(c, cfg, f, &sl[r]));
+      TRY(enqueue_draw(c, c->nb, cfg->seed, c->stream));
+      TRY(enqueue_fwd_bwd(c, c->nb, sl[r]));
     }
     TRY(record_all());
     // phase 2: exchange + (owner) apply
@@ -3029,7 +3004,7 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
       const NetBuffers& nb = c->nb;
       const int64_t len = c->shard_len;
       if (ex == DDQ_EXCHANGE_NONE) {
-        TRY(enqueue_apply(c, nb, u, cfg->target_period, true));
+        TRY(enqueue_apply(c, nb, sl[r]));
         continue;
       }
       if (ex == DDQ_EXCHANGE_ALLREDUCE) {   // gather every gradient first (summed below)
@@ -3046,8 +3021,7 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
         HIP_TRY(c, launch_sum_slices(c->gsl, c->gsl, W, len, len, c->stream));
         nsl = 1;
       }
-      HIP_TRY(c, launch_apply_shard(nb, u.rule, u.lr, u.decay, u.eps, u.momentum, u.weight_decay,
-                                    c->gsl, (int64_t)r * len, len, len, nsl, c->stream));
+      HIP_TRY(c, launch_apply_shard(nb, sl[r].u, c->gsl, (int64_t)r * len, len, len, nsl, c->stream));
     }
     if (ex == DDQ_EXCHANGE_ALLREDUCE) {
       TRY(record_all());       // every member holds all W gradients: sum in rank order, apply
@@ -3056,7 +3030,7 @@ int ddq_group_step(ddq_ctx** ctxs, int32_t W, const ddq_step_cfg* cfg) {
         TRY(set_dev(c));
         TRY(wait_all(c));
         HIP_TRY(c, launch_sum_slices(c->nb.grad, c->gstage, W, P, P, c->stream));
-        TRY(enqueue_apply(c, c->nb, u, cfg->target_period, true));
+        TRY(enqueue_apply(c, c->nb, sl[r]));
       }
     }
     if (ex == DDQ_EXCHANGE_SHARDED || ex == DDQ_EXCHANGE_SERVER) {
@@ -3277,14 +3251,13 @@ int ddq_time_layer(ddq_ctx* c, const char* name, int32_t reps, float* usec) {
   else if (!strcmp(name, "conv3_fwd")) l = 3;
   else return fail(c, DDQ_EINVAL, "time_layer: unknown layer %s", name);
   TRY(set_dev(c));
-  NetBuffers nb = c->nb;
-  nb.fwd_only = l;
+  const NetBuffers& nb = c->nb;
   hipEvent_t e0, e1;
   HIP_TRY(c, hipEventCreate(&e0));
   HIP_TRY(c, hipEventCreate(&e1));
-  hipError_t e = launch_forward(nb, 2, c->stream, nullptr, nullptr);   // warm
+  hipError_t e = launch_forward(nb, 2, c->stream, nullptr, nullptr, true, l);   // warm
   if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-  for (int i = 0; i < reps && e == hipSuccess; ++i) e = launch_forward(nb, 2, c->stream, nullptr, nullptr);
+  for (int i = 0; i < reps && e == hipSuccess; ++i) e = launch_forward(nb, 2, c->stream, nullptr, nullptr, true, l);
   if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
   if (e == hipSuccess) e = hipEventSynchronize(e1);
   float ms = 0.f;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "common.h"   // ddq_launch / ExtTiming (kernel timing)
+#include "step_plan.h"
 
 namespace ddq {
 
@@ -45,21 +46,28 @@ struct ReplayMeta {
   float gamma;
 };
 
-// Fused apply: the update rule of the step.  ext = 0 (exchange-free steps):
-// the slab-reduce launch computes fc4's weight gradient tile by tile and
-// updates every parameter where its gradient becomes final.  ext = 1 (RCCL
-// all-reduce with overlap): fc4_bwd computes fc4's weight gradient, the comm
-// stream sums it over the ranks under the conv backward (fc4_wait), the
-// slab-reduce launch applies fc4's weights from it, and launch_apply the rest
-// after their (small) all-reduce.
-struct FusedApplyCfg {
-  int on, ext;
-  int store_grad;             // fc4's weight gradient also to the gradient buffer
+// The update rule's scalars (ddq_update_cfg) and the target period as given.
+struct UpdateRule {
   int rule, period;
   float lr, decay, eps, momentum, wd;
 };
 
 struct Prefetch;
+// What the launches of one step take besides the buffers: the plan
+// (step_plan.h) and what its sites need.  plan.fused(): the slab-reduce launch
+// computes fc4's weight gradient tile by tile and updates every parameter
+// where its gradient becomes final.  plan.ext() (RCCL all-reduce with
+// overlap): fc4_bwd computes fc4's weight gradient, the comm stream sums it
+// over the ranks under the conv backward (fc4_wait), the slab-reduce launch
+// applies fc4's weights from it, and launch_apply the rest after their (small)
+// all-reduce.
+struct StepLaunch {
+  StepPlan plan;
+  UpdateRule u{};
+  ReplayMeta* meta = nullptr;       // the draw counter, for plan.bump / plan.draw
+  const Prefetch* next = nullptr;   // the next step's set, for plan.draw / plan.gather
+  hipEvent_t fc4_wait = nullptr;    // plan.ext(): the slab-reduce launch waits for it
+};
 
 // Prioritized replay (prio.hip, prio.h, ddq_replay_set_priority): a radix-64 sum tree over
 // the ring's slots in device memory.  Leaves are uint32 fixed-point priorities
@@ -127,19 +135,10 @@ struct NetBuffers {
   // apply launch cannot carry them (pipelined stepping, B > 256)
   hipStream_t side;
   hipEvent_t ev[8];
-  hipEvent_t fc4_wait;              // the slab-reduce launch waits for it (fa.ext)
   ParamLayout L;
   float gamma;
-  int fwd_only;                     // launch_forward: 0 = every layer, l + 1 = conv layer l only
-  int fault_k2_short = 0;           // ddq_inject_fault (tests): this step's fc4 chain launch
-                                    // one workgroup short, so its fan-in meeting times out
-  FusedApplyCfg fa;                 // on: head latches the apply flags, the slab reduce
-                                    // applies (FusedApplyCfg)
   int nstep = 1;                    // the ring's n-step length: >= 2 launches the n-step
                                     // instantiations of the kernels that draw or gather
-  int book_inc;                     // param-server iterations per apply (1, or W: server mode)
-  int head_bump;                    // the head kernel advances the draw counter without a
-                                    // fused apply (async gradients: sample_gather draws)
   // selectable objective (ddq_set_objective): target 0 = max_a P, 1 = P at the
   // first maximum of qn_out (Q(s',.) under theta_Q, (B,4), the pass's first
   // launch group); loss 0 = Euclidean, 1 = Huber with band huber_delta
@@ -173,8 +172,8 @@ struct NetBuffers {
   uint64_t* pairc;                  // K1 split form: meeting counters [B][2]
 };
 
-// fused device draw + gather for the step (B <= 256); counter advanced by the
-// step's apply bookkeeping (launch_backward's bump)
+// fused device draw + gather for the step (B <= 256); the step moves the
+// counter on (StepPlan::bump)
 hipError_t launch_sample_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t* act,
                                 const int16_t* rew, const uint8_t* nt, ReplayMeta* meta,
                                 uint64_t seed, hipStream_t s);
@@ -182,41 +181,33 @@ hipError_t launch_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t*
                          const int16_t* rew, const uint8_t* nt, ReplayMeta* meta,
                          hipStream_t s);
 hipError_t launch_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s);
+// only: 0 = every layer, l + 1 = conv layer l alone (ddq_time_layer)
 hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, void (*mark)(void*, const char*), void* mark_arg,
-                          bool out = true);
-// deepq16 (nb.small): K1 (towers + the head's bookkeeping: latch, bump /
-// next draw, as launch_head's) and K2 (fc4 chain) in place of launch_forward
-// + launch_head
+                          bool out = true, int only = 0);
+// deepq16 (nb.small): K1 (towers + the head's bookkeeping, as launch_head's)
+// and K2 (fc4 chain) in place of launch_forward + launch_head
 // Every meeting launch of the small-map step has all of its meeting
 // workgroups resident at once on this device (meet() spins on the others):
 // *ok = 0 and why set otherwise (the ctx then runs the general kernels)
 hipError_t small_coresident(int B, int* ok, char* why, int nwhy);
-hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
-                                 void (*mark)(void*, const char*), void* mark_arg,
-                                 ReplayMeta* bump = nullptr, const struct Prefetch* pf = nullptr);
-// bump (fused apply only): the step's draw-counter advance, done here so the
-// slab-reduce launch can carry the next step's draw + gather
-hipError_t launch_head(const NetBuffers& nb, hipStream_t s, ReplayMeta* bump = nullptr,
-                       const Prefetch* pf = nullptr);
+hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
+                                 void (*mark)(void*, const char*), void* mark_arg);
+hipError_t launch_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s);
 bool fused_apply_ok(const ParamLayout& L);
-// book: the slab reduce also does the apply bookkeeping (target period
-// book_period); fc4_done: called right after the fc4 weight gradient is
-// enqueued (the overlapped all-reduce starts there); pf (fused apply only):
-// the next step's draw + gather as blocks of the slab-reduce launch.
+// fc4_done: called right after the fc4 weight gradient is enqueued (the
+// overlapped all-reduce starts there).
 // deepq16 (nb.small): K3 (data gradients, conv1's weight gradient slabs)
 // and K4 (conv weight gradients + fused apply + bookkeeping + next gather) in
 // place of launch_backward (same arguments)
-hipError_t launch_small_bwd(const NetBuffers& nb, hipStream_t s, void (*mark)(void*, const char*),
-                            void* mark_arg, bool book, int book_period, ReplayMeta* bump,
-                            hipError_t (*fc4_done)(void*), void* fc4_done_arg,
-                            const struct Prefetch* pf);
+hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
+                            void (*mark)(void*, const char*), void* mark_arg,
+                            hipError_t (*fc4_done)(void*), void* fc4_done_arg);
 void small_groups(int B, int* G2, int* G3);
-hipError_t launch_backward(const NetBuffers& nb, hipStream_t s, void (*mark)(void*, const char*),
-                           void* mark_arg, bool book = false, int book_period = 0,
-                           ReplayMeta* bump = nullptr, hipError_t (*fc4_done)(void*) = nullptr,
-                           void* fc4_done_arg = nullptr, const Prefetch* pf = nullptr);
-// period > 0: also copy Q -> P when the next pull sees iteration % period == 0.
-// Next step's draw + gather carried by the apply launch (pipelined stepping)
+hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
+                           void (*mark)(void*, const char*), void* mark_arg,
+                           hipError_t (*fc4_done)(void*) = nullptr, void* fc4_done_arg = nullptr);
+// The next step's draw + gather as extra blocks of the launch StepPlan::gather
+// names (pipelined stepping)
 struct Prefetch {
   const uint8_t* st;
   const uint8_t* act;
@@ -225,7 +216,8 @@ struct Prefetch {
   ReplayMeta* meta;
   uint64_t seed;
   int B, S, gx, ng;                 // ng = 0: no prefetch blocks
-  int predrawn;                     // 1: the head launch drew the set into idx already
+  int predrawn;                     // 1: an earlier launch drew the set into idx already
+                                    // (StepPlan::predrawn)
   int32_t* idx;
   int32_t* idx_log;                 // NetBuffers::idx_log / log_cap of the step
   int64_t log_cap;
@@ -233,9 +225,8 @@ struct Prefetch {
 };
 Prefetch make_prefetch(const NetBuffers& next, const uint8_t* st, const uint8_t* act,
                        const int16_t* rew, const uint8_t* nt, ReplayMeta* meta, uint64_t seed);
-hipError_t launch_apply(const NetBuffers& nb, int rule, float lr, float decay, float eps,
-                        float momentum, float wd, int period, bool booked, hipStream_t s,
-                        const Prefetch* pre = nullptr);
+// sl.u.period > 0: also copy Q -> P when the next pull sees iteration % period == 0.
+hipError_t launch_apply(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s);
 // rule DDQ_RULE_ADAM (4): launch_apply launches adam_apply_kernel (adam.h) in
 // the apply kernel's place, with nb's Adam constants and lr; the fused apply
 // must be off.  With nb.adam_clip > 0 the caller launches launch_grad_norm
@@ -247,24 +238,27 @@ hipError_t launch_relayout(const NetBuffers& nb, int z, hipStream_t s);
 // owner apply of shard [off, off+len) with W gradient slices (stride `slice`)
 // applied in rank order; then, after the theta all-gather, launch_refresh
 // rebuilds the conv kernel layouts and performs a latched P <- Q sync.
-// theta: the parameters updated (default nb.theta[0]; the async exchange's
-// owner copy otherwise).  first >= 0: the rules' first-call flag from the host
-// and the apply's bookkeeping (iteration += 1) done by the launch itself
-// (async owner applies); -1: the flags latched by a prior launch_book.
-// pre: the next step's draw + gather as extra blocks (pipelined steps)
-// refresh_own != 0: the launch also does launch_refresh's work for its own
-// shard (conv kernel layouts of nb.wks[0]; the P <- Q copy into nb.theta[1] /
-// nb.wks[1] when a sync is due: -1 the latched flag decides, 1 no sync, 2
-// sync), from the values it applied; the refresh after the all-gather / pull
-// then skips that shard.  own_g: slice own_w
-// is read from there (the rank's own gradient in place) instead of gsl
-hipError_t launch_apply_shard(const NetBuffers& nb, int rule, float lr, float decay, float eps,
-                              float momentum, float wd, const float* gsl, int64_t off,
-                              int64_t len, int64_t slice, int W, hipStream_t s,
-                              float* theta = nullptr, int first = -1,
-                              const Prefetch* pre = nullptr, float* mirror = nullptr,
-                              int refresh_own = 0, int own_w = -1,
-                              const float* own_g = nullptr);
+struct ShardOpts {
+  float* theta = nullptr;         // the parameters updated: nb.theta[0], or the async
+                                  // exchange's owner copy
+  int first = -1;                 // >= 0: the rules' first-call flag from the host and the
+                                  // apply's bookkeeping (iteration += 1) done by the launch
+                                  // itself (async owner applies); -1: the flags latched by
+                                  // the step's bookkeeping
+  const Prefetch* pre = nullptr;  // the next step's draw + gather as extra blocks
+  float* mirror = nullptr;        // a second copy of the updated shard
+  int refresh_own = 0;            // != 0: the launch also does launch_refresh's work for its
+                                  // own shard (conv kernel layouts of nb.wks[0]; the P <- Q
+                                  // copy into nb.theta[1] / nb.wks[1] when a sync is due: -1
+                                  // the latched flag decides, 1 no sync, 2 sync), from the
+                                  // values it applied; the refresh after the all-gather /
+                                  // pull then skips that shard
+  int own_w = -1;                 // with own_g: slice own_w is read from there (the rank's
+  const float* own_g = nullptr;   // own gradient in place) instead of gsl
+};
+hipError_t launch_apply_shard(const NetBuffers& nb, const UpdateRule& u, const float* gsl,
+                              int64_t off, int64_t len, int64_t slice, int W, hipStream_t s,
+                              const ShardOpts& o = {});
 // force_sync >= 0: P <- Q decided by the host instead of the latched flag.
 // [skip_lo, skip_hi): a range already refreshed (an owner's refresh_own
 // apply); nothing is launched when it covers every parameter

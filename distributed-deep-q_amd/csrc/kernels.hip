@@ -778,7 +778,7 @@ struct HeadArgs {
   const __bf16* wks;
   int64_t wks_plane, wks2_off, wkst_off, wks3_off, wkst3_off;
   // pipelined fused steps: one extra block draws the NEXT step's sorted index
-  // set into didx and advances the draw counter (instead of every prefetch
+  // set into didx and moves the draw counter on (instead of every prefetch
   // block of the slab-reduce launch drawing it again, and block 0 bumping)
   ReplayMeta* dmeta;
   int32_t* didx;
@@ -1233,18 +1233,37 @@ __device__ __forceinline__ void head_sums(int hb, int B, const float* __restrict
   }
 }
 
-static HeadArgs head_args(const NetBuffers& nb, ReplayMeta* bump) {
+// The head launch's bookkeeping (K1's book block on the small path), as the
+// plan has it: the early latch of the apply flags, the counter's advance and,
+// with it, the next step's draw.
+static hipError_t head_book(const NetBuffers& nb, const StepLaunch& sl, sm16::BookArgs* k) {
+  const StepPlan& p = sl.plan;
+  const bool bump = p.bump == Site::Head, draw = p.draw == Site::Head;
+  if ((bump && !sl.meta) || (draw && !(bump && sl.next && nb.B <= 256)))
+    return hipErrorInvalidValue;
+  *k = sm16::BookArgs{};
+  k->latch = p.latch == Site::Head ? nb.opt_init : nullptr;
+  k->iter = nb.iter; k->period = p.fused() ? p.book_period : 0; k->inc = p.book_step; k->B = nb.B;
+  if (draw) {
+    k->dmeta = sl.meta;
+    k->didx = sl.next->idx; k->dseed = sl.next->seed;
+    k->dlog = sl.next->idx_log; k->dlog_cap = sl.next->log_cap;
+  } else if (bump) {
+    k->bump = sl.meta;
+  }
+  return hipSuccess;
+}
+
+static HeadArgs head_args(const NetBuffers& nb, const sm16::BookArgs& k) {
   const ParamLayout& L = nb.L;
   return HeadArgs{nb.fc4_part, nb.fc4_splits, nb.B, nb.gamma, nb.theta[0], nb.theta[1], L.b[3],
                   L.w[4], L.b[4], nb.action, nb.reward, nb.nonterm, nb.h4[0], nb.h4[1], nb.q_out,
                   nb.p_out, nb.q_sa, nb.p_sa, nb.target, nb.dqbuf, nb.lpart, nb.dh4,
-                  nb.fa.on ? nb.opt_init : nullptr, nb.iter, nb.fa.period, nb.book_inc,
-                  // (prioritized steps: prio_commit_draw advances the counter and draws)
-                  ((nb.fa.on || nb.head_bump) && !nb.prio.leaf) ? bump : nullptr, nb.wks[0],
+                  k.latch, k.iter, k.period, k.inc, k.bump, nb.wks[0],
                   L.wks_total,
                   L.wks_off[1], L.wkst_off,
                   L.wks_off[2], L.wkst3_off,
-                  nullptr, nullptr, 0, nullptr, 0,
+                  k.dmeta, k.didx, k.dseed, k.dlog, k.dlog_cap,
                   nb.obj_target, nb.obj_loss, nb.huber_delta, nb.isw != nullptr, nb.qn_out};
 }
 
@@ -1262,16 +1281,12 @@ static Fc4DgradArgs fc4_dgrad_args(const NetBuffers& nb, bool& narrow, int& ndx,
   return f;
 }
 
-hipError_t launch_head(const NetBuffers& nb, hipStream_t s, ReplayMeta* bump, const Prefetch* pf) {
-  HeadArgs H = head_args(nb, bump);
+hipError_t launch_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s) {
+  sm16::BookArgs k;
+  CHECK_LAUNCH(head_book(nb, sl, &k));
+  const HeadArgs H = head_args(nb, k);
   if (H.obj_target && !H.qn) return hipErrorInvalidValue;
-  int extra = 0;
-  if (pf && pf->ng > 0 && H.bump && nb.B <= 256) {   // the next step's draw moves here
-    H.dmeta = H.bump;
-    H.bump = nullptr;
-    H.didx = pf->idx; H.dseed = pf->seed; H.dlog = pf->idx_log; H.dlog_cap = pf->log_cap;
-    extra = 1;
-  }
+  const int extra = H.dmeta ? 1 : 0;   // the next step's draw: a block of its own
   const bool obj = H.obj_target || H.obj_loss || H.weighted;
   ddq_launch(nb.nstep > 1 ? (obj ? fc4_head_obj_kernel<true> : fc4_head_kernel<true>)
                           : (obj ? fc4_head_obj_kernel<false> : fc4_head_kernel<false>),
@@ -1573,7 +1588,7 @@ template <bool NS>
 __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
     const float* __restrict__ part, float* __restrict__ grad, WredDims d0, WredDims d1,
     WredDims d2, int nub, int64_t* iter, int32_t* opt_init, int book_period,
-    ReplayMeta* bump, int book_inc, HeadSums hs, ApplyTail fat, ApplyArgs faa, Prefetch pf,
+    ReplayMeta* bump, int book_step, HeadSums hs, ApplyTail fat, ApplyArgs faa, Prefetch pf,
     const float* __restrict__ fc4_x, int fc4_k) {
   __shared__ float red[4][4][64];
   int bid = blockIdx.x;
@@ -1590,7 +1605,7 @@ __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
   const bool rest = fat.rest != 0;
   if (bid < kFc4 / 64) {
     if (opt_init && bid == 0 && threadIdx.x == 0)
-      apply_book(iter, opt_init, book_period, bump, book_inc);
+      apply_book(iter, opt_init, book_period, bump, book_step);
     head_sums(bid, hs.B, hs.dqbuf, hs.lpart, hs.h4q, hs.dh4, hs.loss, hs.gw5, hs.gb5, hs.gb4,
               rest, fat, faa);
     return;
@@ -1753,17 +1768,26 @@ __global__ __launch_bounds__(256) void sum_slices_kernel(float* __restrict__ out
   out[j] = acc;
 }
 
-static ApplyArgs apply_args(const NetBuffers& nb, int rule, float lr, float decay, float eps,
-                            float momentum, float wd, int period) {
+static ApplyArgs apply_args(const NetBuffers& nb, const UpdateRule& u) {
   ApplyArgs a;
   a.n = nb.L.total;
   a.lo = 0; a.hi = a.n; a.skip_lo = a.n; a.skip_len = 0;
-  a.rule = rule; a.period = period;
-  a.lr = lr; a.decay = decay; a.eps = eps; a.momentum = momentum; a.wd = wd;
-  a.one_minus_decay = (float)(1.0 - (double)decay);   // numpy: (1 - rmsprop_decay) in double
+  a.rule = u.rule; a.period = u.period;
+  a.lr = u.lr; a.decay = u.decay; a.eps = u.eps; a.momentum = u.momentum; a.wd = u.wd;
+  a.one_minus_decay = (float)(1.0 - (double)u.decay);   // numpy: (1 - rmsprop_decay) in double
   for (int l = 0; l < 5; ++l) { a.bias_lo[l] = nb.L.b[l]; a.bias_hi[l] = nb.L.b[l] + nb.L.bn[l]; }
   conv_dims(nb.L, a.conv);
   return a;
+}
+
+// the fused apply's rule inside the gradient launches (nothing when it is off)
+static ApplyArgs fused_args(const NetBuffers& nb, const StepLaunch& sl) {
+  UpdateRule u{};
+  if (sl.plan.fused()) {
+    u = sl.u;
+    u.period = sl.plan.book_period;
+  }
+  return apply_args(nb, u);
 }
 
 static ApplyTail apply_tail(const NetBuffers& nb) {
@@ -1775,37 +1799,37 @@ static ApplyTail apply_tail(const NetBuffers& nb) {
   return t;
 }
 
-// The fused fc4-weight apply (NetBuffers::fa): fc4's weight gradient is final
+// The fused fc4-weight apply (StepPlan::fused): fc4's weight gradient is final
 // after the fc4 backward, so its update runs as extra blocks of the slab-
 // reduce launch and the apply launch keeps the rest of the parameters.
 bool fused_apply_ok(const ParamLayout& L) {
   return L.w[3] % 4 == 0 && L.b[3] % 4 == 0 && L.b[3] > L.w[3];
 }
 
-hipError_t launch_apply_shard(const NetBuffers& nb, int rule, float lr, float decay, float eps,
-                              float momentum, float wd, const float* gsl, int64_t off,
-                              int64_t len, int64_t slice, int W, hipStream_t s, float* theta,
-                              int first, const Prefetch* pre, float* mirror, int refresh_own,
-                              int own_w, const float* own_g) {
-  const ApplyArgs a = apply_args(nb, rule, lr, decay, eps, momentum, wd, 0);
+hipError_t launch_apply_shard(const NetBuffers& nb, const UpdateRule& u, const float* gsl,
+                              int64_t off, int64_t len, int64_t slice, int W, hipStream_t s,
+                              const ShardOpts& o) {
+  UpdateRule r = u;
+  r.period = 0;
+  const ApplyArgs a = apply_args(nb, r);
   Prefetch pf{};
-  if (pre) pf = *pre;
+  if (o.pre) pf = *o.pre;
   // (shard starts are multiples of 64: a float4 never straddles two shards)
   const RefreshOut ro{nb.theta[1], nb.wks[0], nb.wks[1], nb.L.wks_total,
-                      refresh_own < 0 ? 1 : refresh_own == 0 ? 0 : refresh_own == 1 ? 2 : 3};
+                      o.refresh_own < 0 ? 1 : o.refresh_own == 0 ? 0 : o.refresh_own == 1 ? 2 : 3};
   const int64_t blocks = (len / 4 + 255) / 256;
   auto kern = nb.nstep > 1 ? apply_shard_kernel<true> : apply_shard_kernel<false>;
   if (blocks + pf.ng > 0)
     ddq_launch(kern, dim3((uint32_t)(blocks + pf.ng)), dim3(256), 0, s,
-                       theta ? theta : nb.theta[0], gsl, nb.opt, nb.opt_init, off, len, slice, W,
-                       a, first, nb.iter, pf, mirror, ro, own_g ? own_w : -1, own_g);
+                       o.theta ? o.theta : nb.theta[0], gsl, nb.opt, nb.opt_init, off, len, slice,
+                       W, a, o.first, nb.iter, pf, o.mirror, ro, o.own_g ? o.own_w : -1, o.own_g);
   return hipGetLastError();
 }
 
 
 hipError_t launch_refresh(const NetBuffers& nb, hipStream_t s, int force_sync, int64_t skip_lo,
                           int64_t skip_hi) {
-  const ApplyArgs a = apply_args(nb, 0, 0.f, 0.f, 0.f, 0.f, 0.f, 0);
+  const ApplyArgs a = apply_args(nb, UpdateRule{});
   if (skip_lo <= 0 && skip_hi >= a.n) return hipSuccess;
   ddq_launch(refresh_kernel, dim3((uint32_t)((a.n / 4 + 255) / 256)), dim3(256), 0, s,
                      nb.theta[0], nb.opt_init, nb.theta[1], nb.wks[0], nb.wks[1],
@@ -1842,22 +1866,32 @@ Prefetch make_prefetch(const NetBuffers& next, const uint8_t* st, const uint8_t*
 // the Adam rule's apply launch (adam.h, included at the end of this file: its
 // kernels are emitted after every other kernel of the code object, which keep
 // the offsets they have without it)
-hipError_t launch_adam_apply(const NetBuffers& nb, const ApplyArgs& a, const Prefetch& pf,
-                             hipStream_t s);
+hipError_t launch_adam_apply(const NetBuffers& nb, const StepPlan& plan, const ApplyArgs& a,
+                             const Prefetch& pf, hipStream_t s);
 
-hipError_t launch_apply(const NetBuffers& nb, int rule, float lr, float decay, float eps,
-                        float momentum, float wd, int period, bool booked, hipStream_t s,
-                        const Prefetch* pre) {
+// the next step's set as extra blocks of `site`'s launch, if the plan gathers there
+static hipError_t gather_blocks(const StepLaunch& sl, Site site, Prefetch* pf) {
+  if (sl.plan.gather != site) return hipSuccess;
+  if (!sl.next) return hipErrorInvalidValue;
+  *pf = *sl.next;
+  return hipSuccess;
+}
+
+hipError_t launch_apply(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s) {
+  const StepPlan& p = sl.plan;
+  if (p.apply != ApplyRange::AllInApply && !p.fused()) return hipErrorInvalidValue;
   Prefetch pf{};
-  if (pre) pf = *pre;
-  ApplyArgs a = apply_args(nb, rule, lr, decay, eps, momentum, wd, period);
-  if (!booked) ddq_launch(apply_book_kernel, dim3(1), dim3(1), 0, s, nb.iter, nb.opt_init, period);
-  if (rule == kRuleAdam) return launch_adam_apply(nb, a, pf, s);
+  CHECK_LAUNCH(gather_blocks(sl, Site::Apply, &pf));
+  ApplyArgs a = apply_args(nb, sl.u);
+  if (p.book == Site::Apply)
+    ddq_launch(apply_book_kernel, dim3(1), dim3(1), 0, s, nb.iter, nb.opt_init, sl.u.period);
+  if (sl.u.rule == kRuleAdam) return launch_adam_apply(nb, p, a, pf, s);
   // fused steps: the slab-reduce launch already updated every parameter --
   // or, with its fc4 gradient summed over the ranks under the conv backward
-  // (fa.ext), fc4's weights: the rest (summed after the reduce) here
-  if (nb.fa.on && nb.fa.ext) { a.skip_lo = nb.L.w[3]; a.skip_len = nb.L.wn[3]; }
-  const int blocks = (nb.fa.on && !nb.fa.ext) ? 0 : (int)(((a.n - a.skip_len) / 4 + 255) / 256);
+  // (ext), fc4's weights: the rest (summed after the reduce) here
+  if (p.ext()) { a.skip_lo = nb.L.w[3]; a.skip_len = nb.L.wn[3]; }
+  const int blocks = p.apply == ApplyRange::AllInSlabReduce
+                         ? 0 : (int)(((a.n - a.skip_len) / 4 + 255) / 256);
   if (blocks + pf.ng == 0) return hipSuccess;
   auto kern = nb.nstep > 1 ? apply_kernel<true> : apply_kernel<false>;
   ddq_launch(kern, dim3(blocks + pf.ng), dim3(256), 0, s, apply_tail(nb), a, pf);
@@ -2045,18 +2079,18 @@ static sm16::TowerArgs tower_args(const NetBuffers& nb, int nz, const sm16::Book
 }
 
 hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
-                          void (*mark)(void*, const char*), void* marg, bool out) {
+                          void (*mark)(void*, const char*), void* marg, bool out, int only) {
   const ParamLayout& L = nb.L;
   const int B = nb.B, S = nb.S;
   auto M = [&](const char* n) { if (mark) mark(marg, n); };
   const float* in[2] = {nb.state, nb.next_state};
   // deepq16: conv1 -> pool3 of each (image, tower) in one workgroup (small.h)
-  const bool tower = !nb.fwd_only && nb.small;
+  const bool tower = !only && nb.small;
   if (tower) {
     M("tower_fwd");
     CHECK_LAUNCH(sm16::launch_tower_fwd16(tower_args(nb, nz, nullptr), s, nb.nstep > 1));
   }
-  if (!tower && (!nb.fwd_only || nb.fwd_only == 1)) {
+  if (!tower && (!only || only == 1)) {
     // conv1 (train_val.prototxt:39-78): bf16 matrix cores, fp32-exact
     // (split.h): frames are exact in bf16, so 3 MFMAs per 32x32x16 block; the
     // pooled output goes out fp32 NHWC (conv2 splits it while staging and
@@ -2075,7 +2109,7 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
     M("conv1_fwd");
     CHECK_LAUNCH(pick_tile(kConv1Fwd, S, S).launch(c1, nz, s, L.wks_total));
   }
-  if (!tower && (!nb.fwd_only || nb.fwd_only == 2)) {
+  if (!tower && (!only || only == 2)) {
     // conv2 (train_val.prototxt:79-118): split bf16, 16x16 tiles, 16 waves of
     // one 32x32 block each (kConv2Fwd: edge-fitting tiles on other maps)
     const int H = S / 2;
@@ -2095,7 +2129,7 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
     M("conv2_fwd");
     CHECK_LAUNCH(pick_tile(kConv2Fwd, H, H).launch(a2, nz, s));
   }
-  if (!tower && (!nb.fwd_only || nb.fwd_only == 3)) {
+  if (!tower && (!only || only == 3)) {
     // conv3 (train_val.prototxt:119-158): split bf16, 8x8 tiles (kConv3Fwd), two k groups
     // of 4 waves; pool3 (= fc4's input) fp32 in Caffe order, routing bytes
     // NHWC (the backward expands dpool3 through them)
@@ -2115,7 +2149,7 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
     M("conv3_fwd");
     CHECK_LAUNCH(pick_tile(kConv3Fwd, H, H).launch(a3, nz, s));
   }
-  if (nb.fwd_only) return hipSuccess;   // ddq_time_layer: one conv layer
+  if (only) return hipSuccess;   // ddq_time_layer: one conv layer
   // fc4 (train_val.prototxt:159-185): split bf16 MFMA register-direct, split-K
   // partials (reduced by the head kernel, or by fc4_reduce_out below)
   const int s4 = S / 8;
@@ -2134,23 +2168,13 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
   return hipSuccess;
 }
 
-hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
-                                 void (*mark)(void*, const char*), void* marg, ReplayMeta* bump,
-                                 const Prefetch* pf) {
+hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
+                                 void (*mark)(void*, const char*), void* marg) {
   const ParamLayout& L = nb.L;
   auto M = [&](const char* n) { if (mark) mark(marg, n); };
   // the head's bookkeeping (launch_head / head_args), by K1's extra workgroup
-  sm16::BookArgs bk{};
-  bk.latch = nb.fa.on ? nb.opt_init : nullptr;
-  bk.iter = nb.iter; bk.period = nb.fa.period; bk.inc = nb.book_inc; bk.B = nb.B;
-  // (prioritized steps: prio_commit_draw advances the counter and draws)
-  ReplayMeta* hb = ((nb.fa.on || nb.head_bump) && !nb.prio.leaf) ? bump : nullptr;
-  if (pf && pf->ng > 0 && hb && nb.B <= 256) {
-    bk.dmeta = hb;
-    bk.didx = pf->idx; bk.dseed = pf->seed; bk.dlog = pf->idx_log; bk.dlog_cap = pf->log_cap;
-  } else {
-    bk.bump = hb;
-  }
+  sm16::BookArgs bk;
+  CHECK_LAUNCH(head_book(nb, sl, &bk));
   M("tower_fwd");
   CHECK_LAUNCH(sm16::launch_tower_fwd16(tower_args(nb, 2, &bk), s, nb.nstep > 1));
   sm16::ChainArgs c{};
@@ -2168,10 +2192,9 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   c.qn = nb.qn_out;
   c.weighted = nb.isw != nullptr;
   if (c.obj_target && !c.qn) return hipErrorInvalidValue;
-  c.apply = nb.fa.on && !nb.fa.ext;
-  c.store_grad = nb.fa.store_grad;
-  c.aa = apply_args(nb, nb.fa.rule, nb.fa.lr, nb.fa.decay, nb.fa.eps, nb.fa.momentum, nb.fa.wd,
-                    nb.fa.period);
+  c.apply = sl.plan.apply == ApplyRange::AllInSlabReduce;
+  c.store_grad = sl.plan.store_grad;
+  c.aa = fused_args(nb, sl);
   c.at = apply_tail(nb);
   c.G = nb.small_G; c.upart = nb.upart; c.w4part = nb.w4part;
   if (c.G > 8 || (c.G > 1 && (!c.upart || !c.w4part))) return hipErrorInvalidValue;
@@ -2184,7 +2207,7 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, hipStream_t s,
   CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr[(obj ? 2 : 0) + (one ? 0 : 1)],
                               sm16::kChainSmem));
   M("fc4_chain");
-  ddq_launch(kern, dim3((one ? 2 : 1) * sm16::kFcBlk * c.G - (nb.fault_k2_short ? 1 : 0)), dim3(512),
+  ddq_launch(kern, dim3((one ? 2 : 1) * sm16::kFcBlk * c.G - (sl.plan.k2_short ? 1 : 0)), dim3(512),
              sm16::kChainSmem, s, c);
   CHECK_LAUNCH(hipGetLastError());
   return hipSuccess;
@@ -2255,11 +2278,13 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
   return hipSuccess;
 }
 
-hipError_t launch_small_bwd(const NetBuffers& nb, hipStream_t s,
-                            void (*mark)(void*, const char*), void* marg, bool book,
-                            int book_period, ReplayMeta* bump, hipError_t (*fc4_done)(void*),
-                            void* fc4_done_arg, const Prefetch* pre) {
+hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
+                            void (*mark)(void*, const char*), void* marg,
+                            hipError_t (*fc4_done)(void*), void* fc4_done_arg) {
   const ParamLayout& L = nb.L;
+  const StepPlan& p = sl.plan;
+  const bool book = p.book == Site::SlabReduce;
+  if (p.bump == Site::SlabReduce && !(book && sl.meta)) return hipErrorInvalidValue;
   const int B = nb.B;
   auto M = [&](const char* n) { if (mark) mark(marg, n); };
   // fc4's weight gradient is final since K2 (B <= 32; else after K4's chunk
@@ -2304,23 +2329,19 @@ hipError_t launch_small_bwd(const NetBuffers& nb, hipStream_t s,
     w.grad = nb.grad;
     for (int l = 0; l < 3; ++l) { w.w_off[l] = L.w[l]; w.b_off[l] = L.b[l]; }
     conv_dims(L, w.cd);
-    w.apply = nb.fa.on && !nb.fa.ext;
-    w.aa = apply_args(nb, nb.fa.rule, nb.fa.lr, nb.fa.decay, nb.fa.eps, nb.fa.momentum, nb.fa.wd,
-                      nb.fa.period);
+    w.apply = p.apply == ApplyRange::AllInSlabReduce;
+    w.aa = fused_args(nb, sl);
     w.at = apply_tail(nb);
-    w.book = book; w.book_period = book_period; w.book_inc = nb.book_inc;
+    w.book = book; w.book_period = p.book_period; w.book_step = p.book_step;
     w.iter = nb.iter;
-    w.bump = book && !nb.fa.on ? bump : nullptr;
+    w.bump = p.bump == Site::SlabReduce ? sl.meta : nullptr;
     w.w4_off = L.w[3];
     w.G = nb.small_G; w.upart = nb.upart; w.w4part = nb.w4part;
     w.b4_off = L.b[3]; w.w5_off = L.w[4]; w.b5_off = L.b[4]; w.loss = nb.loss;
     w.nw4 = (w.apply || w.G > 1) ? 32 : 0;
     w.nus = w.G > 1 ? 1 : 0;
     if (L.w[3] % 4) return hipErrorInvalidValue;   // (float4 rows; 94496 for this net)
-    if (pre && nb.fa.on) {
-      w.pf = *pre;
-      w.pf.predrawn = bump != nullptr && B <= 256;   // K1 drew it (its book block)
-    }
+    CHECK_LAUNCH(gather_blocks(sl, Site::SlabReduce, &w.pf));   // (K1's book block drew it)
     // LDS: a round buffer per tile layer, two where a group has more than one
     // round; at least the wave sums + a one-group tile's sums
     const int r2 = (w.ipg2 + sm16::Wg2::NI - 1) / sm16::Wg2::NI;
@@ -2344,11 +2365,14 @@ hipError_t launch_small_bwd(const NetBuffers& nb, hipStream_t s,
   return hipSuccess;
 }
 
-hipError_t launch_backward(const NetBuffers& nb, hipStream_t s, void (*mark)(void*, const char*),
-                           void* marg, bool book, int book_period, ReplayMeta* bump,
-                           hipError_t (*fc4_done)(void*), void* fc4_done_arg,
-                           const Prefetch* pre) {
+hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
+                           void (*mark)(void*, const char*), void* marg,
+                           hipError_t (*fc4_done)(void*), void* fc4_done_arg) {
   const ParamLayout& L = nb.L;
+  const StepPlan& p = sl.plan;
+  const bool book = p.book == Site::SlabReduce;
+  if (p.bump == Site::SlabReduce && !(book && sl.meta)) return hipErrorInvalidValue;
+  if (p.ext() && !sl.fc4_wait) return hipErrorInvalidValue;
   const int B = nb.B, S = nb.S;
   const int s4 = S / 8;
   auto M = [&](const char* n) { if (mark) mark(marg, n); };
@@ -2357,7 +2381,7 @@ hipError_t launch_backward(const NetBuffers& nb, hipStream_t s, void (*mark)(voi
     bool narrow;
     int ndx, nd;
     Fc4DgradArgs f = fc4_dgrad_args(nb, narrow, ndx, nd);
-    const int nw = (nb.fa.on && !nb.fa.ext) ? 0 : fc4_wgrad_blocks<8>(f.K);
+    const int nw = p.apply == ApplyRange::AllInSlabReduce ? 0 : fc4_wgrad_blocks<8>(f.K);
     M("fc4_bwd");
     ddq_launch((narrow ? fc4_bwd_kernel<true, 16> : fc4_bwd_kernel<true, 32>),
                        dim3(nd + nw), dim3(512), 0, s, f, nb.pool3[0], nb.grad + L.w[3], nd, ndx);
@@ -2433,37 +2457,33 @@ hipError_t launch_backward(const NetBuffers& nb, hipStream_t s, void (*mark)(voi
     blk += cout[l] * (nb.wnp[l] / 64) * G / 4;   // units per layer: a multiple of 32
   }
   {  // slab reduce -> grads (Caffe layout) [+ the fused apply + next draw]
-    if (nb.fc4_wait) CHECK_LAUNCH(hipStreamWaitEvent(s, nb.fc4_wait, 0));
+    if (p.ext()) CHECK_LAUNCH(hipStreamWaitEvent(s, sl.fc4_wait, 0));
     M("wgrad_reduce");
     HeadSums hs{0, B, nb.dqbuf, nb.lpart, nb.h4[0], nb.dh4, nb.loss, nb.grad + L.w[4],
                 nb.grad + L.b[4], nb.grad + L.b[3]};
     const int nub = blk;
     ApplyTail fat = apply_tail(nb);
-    ApplyArgs faa = apply_args(nb, nb.fa.rule, nb.fa.lr, nb.fa.decay, nb.fa.eps, nb.fa.momentum,
-                               nb.fa.wd, nb.fa.period);
+    ApplyArgs faa = fused_args(nb, sl);
     int nfa = 0;
     fat.nfa = 0;
-    if (nb.fa.on) {   // fc4 weights [w4, b4): its gradient is final since fc4_bwd
+    if (p.fused()) {   // fc4 weights [w4, b4): its gradient is final since fc4_bwd
       faa.lo = L.w[3];
       faa.hi = L.b[3];
       nfa = fc4_wgrad_blocks<kFc4ApplyR>(64 * s4 * s4);
       fat.nfa = nfa;
-      fat.ext = nb.fa.ext;
-      fat.store_grad = nb.fa.store_grad;
+      fat.ext = p.ext();
+      fat.store_grad = p.store_grad;
       // and everything else where its gradient is reduced -- unless the rest
       // must be summed over the ranks first (ext: apply launch after that)
-      fat.rest = !nb.fa.ext;
+      fat.rest = !p.ext();
     }
     Prefetch pf{};
-    if (pre && nb.fa.on) {
-      pf = *pre;
-      pf.predrawn = bump != nullptr && nb.B <= 256;   // launch_head drew it (head_draw)
-    }
+    CHECK_LAUNCH(gather_blocks(sl, Site::SlabReduce, &pf));   // (launch_head drew it: head_draw)
     auto kern = nb.nstep > 1 ? wgrad_reduce_kernel<true> : wgrad_reduce_kernel<false>;
     ddq_launch(kern, dim3(pf.ng + nub + kFc4 / 64 + nfa), dim3(256), 0, s,
                        nb.wpart, nb.grad, d[0], d[1], d[2], nub, nb.iter,
-                       book ? nb.opt_init : nullptr, book_period,
-                       book && !nb.fa.on ? bump : nullptr, nb.book_inc, hs, fat, faa, pf,
+                       book ? nb.opt_init : nullptr, p.book_period,
+                       p.bump == Site::SlabReduce ? sl.meta : nullptr, p.book_step, hs, fat, faa, pf,
                        nb.pool3[0], 64 * s4 * s4);
     CHECK_LAUNCH(hipGetLastError());
   }

@@ -1344,7 +1344,7 @@ struct WgArgs {
   ApplyArgs aa;
   ApplyTail at;
   // bookkeeping (the slab reduce's): apply_book when book
-  int book, book_period, book_inc;
+  int book, book_period, book_step;
   int64_t* iter;
   ReplayMeta* bump;
   Prefetch pf;
@@ -1837,7 +1837,7 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgArgs a) {
   DDQ_STAMP(40);
   // conv1: the B per-image slabs summed in image order, element by element
   if (bid == 0 && threadIdx.x == 0 && a.book && !pois)   // (no update: no iteration)
-    apply_book(a.iter, const_cast<int32_t*>(a.at.opt_init), a.book_period, a.bump, a.book_inc);
+    apply_book(a.iter, const_cast<int32_t*>(a.at.opt_init), a.book_period, a.bump, a.book_step);
   const int np = a.w1_np;
   for (int e = bid * 256 + threadIdx.x; e < 32 * 197; e += kW1Blocks * 256) {
     const int co = e / 197, n = e - co * 197;

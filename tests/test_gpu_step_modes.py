@@ -31,7 +31,7 @@ def ref():
     return ref_numpy
 
 
-def two_nets(ddq, ref):
+def two_nets(ddq, ref, S=S, B=B):
     rng = np.random.default_rng(21)
     nets = [ddq.DeepQNet(batch=B, frame=S) for _ in range(2)]
     theta = ref.flatten(ref.init_params(S, seed=6))
@@ -103,3 +103,36 @@ def test_objective_change_between_graph_steps_matches_eager_steps(ddq, ref):
     a.step_graph(cfg, 9)
     eager(b, cfg, 9)
     assert_same_state(a, b, 0, 11)
+
+
+# Regimes of the step plan (csrc/step_plan.h, DESIGN.md "The step plan") that no
+# other GPU suite runs.  (S, B, exchange, overlap): the general kernels with the
+# one-launch draw under the overlapped all-reduce of a 1-rank communicator --
+# fc4 applied by the slab-reduce launch after its bucket's all-reduce, the rest
+# by the apply launch, the next draw in the head launch (the other suites run
+# the overlap on the small path, or past 256 images with the side-stream draw).
+PLAN_REGIMES = [(24, 8, "allreduce", True)]
+
+
+@pytest.mark.parametrize("S,B,exchange,overlap", PLAN_REGIMES)
+def test_exchanged_regime_through_the_modes_matches_eager_steps(ddq, ref, S, B, exchange, overlap):
+    """Net A: the exchange over its 1-rank communicator, through every mode.  Net
+    B: no exchange, eager steps alone (a sum over one rank is the identity)."""
+    a, b = two_nets(ddq, ref, S, B)
+    a.comm_init(ddq.DeepQNet.comm_unique_id(), 1, 0)
+    for n in (a, b):
+        n.index_log_enable(64)
+    # (lr: rmsprop at 1e-4 leaves float32 range within four steps at S = 24, with
+    # or without the exchange; tests/test_gpu_large_batch.py steps that frame at 1e-6)
+    cfg_a = a.step_cfg("rmsprop", lr=1e-6, target_period=3, exchange=exchange, overlap=overlap,
+                       seed=5)
+    cfg_b = b.step_cfg("rmsprop", lr=1e-6, target_period=3, seed=5)
+    eager(a, cfg_a, 2)
+    a.step_graph(cfg_a, 9)        # one 8-step exec plus a single
+    a.step_pipelined(cfg_a, 11)   # an 8-step exec plus a 3-step tail
+    eager(a, cfg_a, 1)
+    eager(b, cfg_b, 23)
+    assert_same_state(a, b, 0, 23)
+    assert a.get_flat(0).tobytes() != a.get_flat(1).tobytes()   # steps 22, 23 after the sync at 21
+    for n in (a, b):
+        n.close()
