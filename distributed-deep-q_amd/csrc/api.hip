@@ -109,12 +109,9 @@ struct ddq_ctx {
   NetBuffers nb{};
   std::vector<void*> allocs;
   std::string err;
-  // replay ring
-  uint8_t* r_state = nullptr;
-  uint8_t* r_action = nullptr;
-  int16_t* r_reward = nullptr;
-  uint8_t* r_nonterm = nullptr;
-  ReplayMeta* r_meta = nullptr;    // device
+  // replay ring: the view every launch takes (state == nullptr: not created;
+  // meta: device; prio follows d_prio, nullptr while prioritization is off)
+  ReplayRing ring{};
   uint32_t* r_bitmap = nullptr;    // large-batch sampler scratch (lazy)
   int32_t* r_blk = nullptr;
   uint64_t batch_ctr = 0;          // large-batch draws so far (RNG stream position)
@@ -122,14 +119,14 @@ struct ddq_ctx {
   int32_t lanes = 1;               // laned ring (ddq_replay_set_lanes): head / valid per lane
   int64_t lane_len = 0;            // capacity / lanes
   int32_t nstep = 1;               // n-step returns (ddq_replay_set_nstep)
-  // prioritized replay (ddq_replay_set_priority): nb.prio / nb.isw are bound while on
+  // prioritized replay (ddq_replay_set_priority): nb.prio and the sets' isw are bound while on
   bool prio_on = false;
   ddq_priority_cfg prio_cfg{0, 0.f, 0.f, 0.f};
   PrioTree* d_prio = nullptr;      // device copy of nb.prio: the ring writers' argument
   int32_t* pset_idx = nullptr;     // ddq_replay_set_priorities staging (grown on demand)
   uint32_t* pset_q = nullptr;
   int32_t pset_cap = 0;
-  bool idx_bound = false;          // nb.idx holds the bound minibatch's slots
+  bool idx_bound = false;          // nb.mb.idx holds the bound minibatch's slots
   bool adam_on = false;            // ddq_set_adam was called: nb.opt2 / gn_part / gnorm exist
   // acting scratch
   uint8_t* act_u8 = nullptr;
@@ -187,10 +184,9 @@ struct ddq_ctx {
   int fault = 0;
   std::string small_off;           // why the small-map step is off at S = 16 (empty: on)
   StepGraphs graphs;
-  // pipelined stepping: a second minibatch set
-  float *mb2_state = nullptr, *mb2_next = nullptr, *mb2_action = nullptr;
-  float *mb2_reward = nullptr, *mb2_nonterm = nullptr;
-  int32_t* mb2_idx = nullptr;
+  // minibatch sets: [0] the ctx's own (nb.mb is its copy), [1] the twin of
+  // pipelined stepping (ensure_pipe allocates it)
+  Minibatch mb[2] = {};
   int64_t steps = 0;
   int64_t applied = 0;               // host mirror of the device iteration counter
   // profiling marks: a kernel's own dispatch start / stop events
@@ -262,6 +258,29 @@ static void dfree(ddq_ctx* c, T*& p) {
     if (r_ != DDQ_OK) return r_; \
   } while (0)
 
+// One minibatch set's buffers, all or none.  The reward buffer holds 2 * B
+// floats: the B rewards, then the B importance-sampling weights of prioritized
+// replay (mb_bind_weights).
+static int mb_alloc(ddq_ctx* c, Minibatch* out) {
+  const size_t B = c->nb.B, frames = B * c->nb.S * c->nb.S * 4;
+  Minibatch m{};
+  TRY(dalloc(c, &m.state, frames));
+  TRY(dalloc(c, &m.next_state, frames));
+  TRY(dalloc(c, &m.action, B * 4));
+  TRY(dalloc(c, &m.reward, 2 * B));
+  TRY(dalloc(c, &m.nonterm, B));
+  TRY(dalloc(c, &m.idx, B));
+  *out = m;
+  return DDQ_OK;
+}
+
+// The weights of every allocated set: the second half of its reward buffer
+// while prioritization is on, none otherwise.  nb.mb follows set 0.
+static void mb_bind_weights(ddq_ctx* c, bool on) {
+  for (Minibatch& m : c->mb) m.isw = on && m.reward ? m.reward + c->nb.B : nullptr;
+  c->nb.mb = c->mb[0];
+}
+
 // Blocking copy ordered on the ctx stream.
 static hipError_t scopy(ddq_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
@@ -323,13 +342,8 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* desc) {
     nb.L = make_layout(S);
     const int64_t P = nb.L.total;
     const int S2 = S / 2, S3 = S / 4, S4 = S / 8;
-    TRY(dalloc(c, &nb.state, (size_t)B * S * S * 4));
-    TRY(dalloc(c, &nb.next_state, (size_t)B * S * S * 4));
-    TRY(dalloc(c, &nb.action, (size_t)B * 4));
-    // (B rewards, then the B importance-sampling weights of prioritized replay)
-    TRY(dalloc(c, &nb.reward, (size_t)2 * B));
-    TRY(dalloc(c, &nb.nonterm, (size_t)B));
-    TRY(dalloc(c, &nb.idx, (size_t)B));
+    TRY(mb_alloc(c, &c->mb[0]));
+    nb.mb = c->mb[0];
     for (int z = 0; z < 2; ++z) {
       TRY(dalloc(c, &nb.pool3[z], (size_t)B * S4 * S4 * 64));
       TRY(dalloc(c, &nb.h4[z], (size_t)B * 512));
@@ -412,7 +426,7 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* desc) {
     TRY(dalloc(c, &c->act_part, (size_t)nb.fc4_splits * 2 * B * 512));
     TRY(dalloc(c, &c->act_q, (size_t)B * 4));
     TRY(dalloc(c, &c->act_out, (size_t)B));
-    TRY(dalloc(c, &c->r_meta, 1));
+    TRY(dalloc(c, &c->ring.meta, 1));
     return DDQ_OK;
   }();
   if (rc != DDQ_OK) {
@@ -614,7 +628,8 @@ static void prio_release(ddq_ctx* c) {
   for (auto& p : t.sum) dfree(c, p);
   dfree(c, t.st);
   t = PrioTree{};
-  c->nb.isw = nullptr;
+  mb_bind_weights(c, false);
+  c->ring.prio = nullptr;
   c->prio_on = false;
   c->prio_cfg.enabled = 0;
 }
@@ -625,7 +640,7 @@ static int prio_rebuild(ddq_ctx* c) {
   if (!c->prio_on) return DDQ_OK;
   const uint32_t one = kPrioOne;
   HIP_TRY(c, hipMemcpyAsync(&c->nb.prio.st->pmax, &one, 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, launch_prio_rebuild(c->nb.prio, c->r_meta, c->stream));
+  HIP_TRY(c, launch_prio_rebuild(c->nb.prio, c->ring.meta, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->idx_bound = false;
   return DDQ_OK;
@@ -637,7 +652,7 @@ static int prio_enable_fill(ddq_ctx* c, const float abe[3]) {
   const PrioTree& t = c->nb.prio;
   HIP_TRY(c, hipMemcpyAsync(t.st, abe, 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(c->d_prio, &t, sizeof(t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, launch_fill_ones(c->nb.isw, c->nb.B, c->stream));
+  HIP_TRY(c, launch_fill_ones(c->nb.mb.isw, c->nb.B, c->stream));
   return prio_rebuild(c);
 }
 
@@ -652,10 +667,10 @@ static int prio_refuse(ddq_ctx* c, const char* what) {
 // ---------------- replay ----------------
 static int push_meta(ddq_ctx* c, bool prio_add = false, int64_t h = 0) {
   int64_t hv[2] = {c->head, c->valid};
-  HIP_TRY(c, hipMemcpyAsync(c->r_meta, hv, sizeof(hv), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->ring.meta, hv, sizeof(hv), hipMemcpyHostToDevice, c->stream));
   // prioritized replay: the writer rule on the slot just added, after the new
   // head / valid (stream order)
-  if (prio_add) HIP_TRY(c, launch_prio_add(c->nb.prio, c->r_meta, 0, h, c->stream));
+  if (prio_add) HIP_TRY(c, launch_prio_add(c->nb.prio, c->ring.meta, 0, h, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;
 }
@@ -664,13 +679,13 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (capacity < 2 || capacity > (int64_t)INT32_MAX)
     return fail(c, DDQ_EINVAL, "capacity must be in [2, 2^31) (got %lld)", (long long)capacity);
-  if (c->r_state) return fail(c, DDQ_ESTATE, "replay already created");
+  if (c->ring.state) return fail(c, DDQ_ESTATE, "replay already created");
   TRY(set_dev(c));
   const size_t slot = (size_t)4 * c->nb.S * c->nb.S;
-  TRY(dalloc(c, &c->r_state, slot * capacity));
-  TRY(dalloc(c, &c->r_action, (size_t)capacity));
-  TRY(dalloc(c, &c->r_reward, (size_t)capacity));
-  TRY(dalloc(c, &c->r_nonterm, (size_t)capacity));
+  TRY(dalloc(c, &c->ring.state, slot * capacity));
+  TRY(dalloc(c, &c->ring.action, (size_t)capacity));
+  TRY(dalloc(c, &c->ring.reward, (size_t)capacity));
+  TRY(dalloc(c, &c->ring.nonterm, (size_t)capacity));
   c->capacity = capacity;
   c->head = c->valid = 0;
   c->lanes = 1;
@@ -684,14 +699,14 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   m.lane_len = capacity;
   m.nstep = 1;
   m.gamma = c->nb.gamma;
-  HIP_TRY(c, scopy(c, c->r_meta, &m, sizeof(m), hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.meta, &m, sizeof(m), hipMemcpyHostToDevice));
   invalidate_graph(c);
   return DDQ_OK;
 }
 
 int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* state) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (c->lanes > 1) return fail(c, DDQ_ESTATE, "ddq_replay_add on a laned ring (%d lanes)", c->lanes);
   if (action < 0 || action > 255) return fail(c, DDQ_EINVAL, "action must fit uint8");
   if (reward < -32768 || reward > 32767) return fail(c, DDQ_EINVAL, "reward must fit int16");
@@ -700,11 +715,11 @@ int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* st
   const int64_t h = c->head;
   uint8_t a = (uint8_t)action, nt = state ? 1 : 0;
   int16_t r = (int16_t)reward;
-  HIP_TRY(c, hipMemcpyAsync(c->r_action + h, &a, 1, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->r_reward + h, &r, 2, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->r_nonterm + h, &nt, 1, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->ring.action + h, &a, 1, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->ring.reward + h, &r, 2, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->ring.nonterm + h, &nt, 1, hipMemcpyHostToDevice, c->stream));
   if (state)
-    HIP_TRY(c, hipMemcpyAsync(c->r_state + h * slot, state, slot, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->ring.state + h * slot, state, slot, hipMemcpyHostToDevice, c->stream));
   c->head = (c->head + 1) % c->capacity;
   c->valid = std::min(c->capacity, c->valid + 1);
   return push_meta(c, c->prio_on, h);
@@ -742,7 +757,7 @@ static bool too_few_slots(const ddq_ctx* c, int64_t batch) {
 
 int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (c->valid != 0) return fail(c, DDQ_ESTATE, "set_lanes needs an empty ring (valid = %lld)",
                                  (long long)c->valid);
   if (lanes < 1 || c->capacity % lanes != 0 || c->capacity / lanes < 2)
@@ -758,7 +773,7 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
   c->head = 0;
   c->p_env.n = 0;                    // a pool or an actor belongs to the lanes it was
   c->a_env.n = 0;                    // created on
-  char* m = reinterpret_cast<char*>(c->r_meta);
+  char* m = reinterpret_cast<char*>(c->ring.meta);
   HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lanes), &c->lanes, 4, hipMemcpyHostToDevice));
   HIP_TRY(c, scopy(c, m + offsetof(ReplayMeta, lane_len), &c->lane_len, 8, hipMemcpyHostToDevice));
   TRY(push_meta(c));
@@ -767,7 +782,7 @@ int ddq_replay_set_lanes(ddq_ctx* c, int32_t lanes) {
 
 int ddq_replay_lanes(const ddq_ctx* c, int32_t* lanes, int64_t* lane_len) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
   if (lanes) *lanes = c->lanes;
   if (lane_len) *lane_len = c->lane_len;
   return DDQ_OK;
@@ -777,7 +792,7 @@ static_assert(kNstepMax == DDQ_NSTEP_MAX, "the window loops unroll to DDQ_NSTEP_
 
 int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (c->async_on)
     return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: set the n-step "
                                "length before ddq_async_begin");
@@ -789,14 +804,14 @@ int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
   invalidate_graph(c);   // a pipelined chain holds a minibatch gathered under the old n
   c->nstep = n;
   c->nb.nstep = n;   // n >= 2: the n-step instantiations of the drawing / gathering kernels
-  HIP_TRY(c, scopy(c, reinterpret_cast<char*>(c->r_meta) + offsetof(ReplayMeta, nstep), &c->nstep,
+  HIP_TRY(c, scopy(c, reinterpret_cast<char*>(c->ring.meta) + offsetof(ReplayMeta, nstep), &c->nstep,
                    4, hipMemcpyHostToDevice));
   return prio_rebuild(c);
 }
 
 int ddq_replay_nstep(const ddq_ctx* c, int32_t* n) {
   if (!c || !n) return fail(nullptr, DDQ_EINVAL, "null argument");
-  if (!c->r_state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
   *n = c->nstep;
   return DDQ_OK;
 }
@@ -807,7 +822,7 @@ static bool unit_interval(float x) { return std::isfinite(x) && x >= 0.f && x <=
 int ddq_replay_set_priority(ddq_ctx* c, const ddq_priority_cfg* p) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!p) return fail(c, DDQ_EINVAL, "null priority cfg");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   TRY(set_dev(c));
   if (!p->enabled) {
     if (!c->prio_on) return DDQ_OK;
@@ -854,7 +869,8 @@ int ddq_replay_set_priority(ddq_ctx* c, const ddq_priority_cfg* p) {
   // enable reuses them, ddq_destroy frees them with every other allocation)
   if (rc == DDQ_OK && !c->d_prio) rc = dalloc(c, &c->d_prio, 1);
   c->nb.prio = t;
-  c->nb.isw = c->nb.reward + c->nb.B;   // the second half of the reward buffer (mb_view: set 1's)
+  mb_bind_weights(c, true);
+  c->ring.prio = c->d_prio;
   c->prio_on = true;
   if (rc == DDQ_OK) rc = prio_enable_fill(c, abe);
   if (rc != DDQ_OK) { prio_release(c); return rc; }   // all or nothing: no half-bound tree
@@ -929,7 +945,7 @@ int ddq_replay_update_priorities_async(ddq_ctx* c) {
     return fail(c, DDQ_ESTATE, "no device-side index set is bound (the minibatch was not drawn from "
                                "the ring)");
   TRY(set_dev(c));
-  HIP_TRY(c, launch_prio_commit(c->nb, c->r_meta, c->stream));
+  HIP_TRY(c, launch_prio_commit(c->nb, c->ring.meta, c->stream));
   return DDQ_OK;
 }
 
@@ -937,17 +953,17 @@ int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
                       const int16_t* reward, const uint8_t* nonterm, int64_t n, int64_t head,
                       int64_t valid) {
   if (!c || !state || !action || !reward || !nonterm) return fail(c, DDQ_EINVAL, "null argument");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (n != c->capacity) return fail(c, DDQ_EINVAL, "import size %lld != capacity %lld",
                                     (long long)n, (long long)c->capacity);
   if (head < 0 || head >= c->lane_len || valid < 0 || valid > c->lane_len)
     return fail(c, DDQ_EINVAL, "head/valid out of range");
   TRY(set_dev(c));
   const size_t slot = (size_t)4 * c->nb.S * c->nb.S;
-  HIP_TRY(c, scopy(c, c->r_state, state, slot * n, hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->r_action, action, n, hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->r_reward, reward, 2 * n, hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->r_nonterm, nonterm, n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.state, state, slot * n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.action, action, n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.reward, reward, 2 * n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.nonterm, nonterm, n, hipMemcpyHostToDevice));
   c->head = head;
   c->valid = valid;
   TRY(push_meta(c));
@@ -957,25 +973,25 @@ int ddq_replay_import(ddq_ctx* c, const uint8_t* state, const uint8_t* action,
 int ddq_replay_export(ddq_ctx* c, uint8_t* state, uint8_t* action, int16_t* reward,
                       uint8_t* nonterm, int64_t n) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (n != c->capacity) return fail(c, DDQ_EINVAL, "export size mismatch");
   TRY(set_dev(c));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const size_t slot = (size_t)4 * c->nb.S * c->nb.S;
-  if (state) HIP_TRY(c, scopy(c, state, c->r_state, slot * n, hipMemcpyDeviceToHost));
-  if (action) HIP_TRY(c, scopy(c, action, c->r_action, n, hipMemcpyDeviceToHost));
-  if (reward) HIP_TRY(c, scopy(c, reward, c->r_reward, 2 * n, hipMemcpyDeviceToHost));
-  if (nonterm) HIP_TRY(c, scopy(c, nonterm, c->r_nonterm, n, hipMemcpyDeviceToHost));
+  if (state) HIP_TRY(c, scopy(c, state, c->ring.state, slot * n, hipMemcpyDeviceToHost));
+  if (action) HIP_TRY(c, scopy(c, action, c->ring.action, n, hipMemcpyDeviceToHost));
+  if (reward) HIP_TRY(c, scopy(c, reward, c->ring.reward, 2 * n, hipMemcpyDeviceToHost));
+  if (nonterm) HIP_TRY(c, scopy(c, nonterm, c->ring.nonterm, n, hipMemcpyDeviceToHost));
   return DDQ_OK;
 }
 
 static int check_err_flag(ddq_ctx* c) {
   ReplayMeta m;
-  HIP_TRY(c, hipMemcpyAsync(&m, c->r_meta, sizeof(m), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&m, c->ring.meta, sizeof(m), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (m.err) {
     int32_t z = 0;
-    HIP_TRY(c, scopy(c, reinterpret_cast<char*>(c->r_meta) + offsetof(ReplayMeta, err), &z, 4,
+    HIP_TRY(c, scopy(c, reinterpret_cast<char*>(c->ring.meta) + offsetof(ReplayMeta, err), &z, 4,
                          hipMemcpyHostToDevice));
     if (m.err == 2) return fail(c, DDQ_ERANGE, "batch sampler could not find distinct indices");
     return fail(c, DDQ_ERANGE, "stored action index out of range for %d actions", 4);
@@ -985,7 +1001,7 @@ static int check_err_flag(ddq_ctx* c) {
 
 int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   if (!c || !idx) return fail(c, DDQ_EINVAL, "null argument");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (too_few_slots(c, batch))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 batch, (long long)(c->lanes * c->valid));
@@ -1000,28 +1016,26 @@ int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
     if (i && idx[i] <= idx[i - 1]) return fail(c, DDQ_EINVAL, "indices must be sorted and distinct");
   }
   TRY(set_dev(c));
-  HIP_TRY(c, hipMemcpyAsync(c->nb.idx, idx, batch * 4, hipMemcpyHostToDevice, c->stream));
-  if (c->nb.isw) HIP_TRY(c, launch_fill_ones(c->nb.isw, batch, c->stream));   // host-given set
-  HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                           c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->nb.mb.idx, idx, batch * 4, hipMemcpyHostToDevice, c->stream));
+  if (c->nb.mb.isw) HIP_TRY(c, launch_fill_ones(c->nb.mb.isw, batch, c->stream));   // host-given set
+  HIP_TRY(c, launch_gather(c->nb, c->ring, c->stream));
   c->idx_bound = true;
   return check_err_flag(c);
 }
 
 int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (too_few_slots(c, c->nb.B))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 c->nb.B, (long long)(c->lanes * c->valid));
   TRY(set_dev(c));
   if (c->prio_on) {   // the prioritized draw (one workgroup), then its counter's advance
-    HIP_TRY(c, launch_prio_sample(c->nb, c->r_meta, seed, c->stream, true));
+    HIP_TRY(c, launch_prio_sample(c->nb, c->ring.meta, seed, c->stream, true));
   } else {
-    HIP_TRY(c, launch_sample(c->nb, c->r_meta, seed, c->stream));
+    HIP_TRY(c, launch_sample(c->nb, c->ring.meta, seed, c->stream));
   }
-  HIP_TRY(c, launch_gather(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                           c->stream));
+  HIP_TRY(c, launch_gather(c->nb, c->ring, c->stream));
   c->idx_bound = true;
   return DDQ_OK;
 }
@@ -1030,7 +1044,7 @@ int ddq_replay_fill_tiled(ddq_ctx* c, const uint8_t* state, const uint8_t* actio
                           const int16_t* reward, const uint8_t* nonterm, int64_t pool,
                           int64_t head, int64_t valid) {
   if (!c || !state || !action || !reward || !nonterm) return fail(c, DDQ_EINVAL, "null argument");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (c->lanes > 1)
     return fail(c, DDQ_ESTATE, "ddq_replay_fill_tiled on a laned ring (%d lanes)", c->lanes);
   const int64_t n = c->capacity;
@@ -1039,29 +1053,29 @@ int ddq_replay_fill_tiled(ddq_ctx* c, const uint8_t* state, const uint8_t* actio
     return fail(c, DDQ_EINVAL, "head/valid out of range");
   TRY(set_dev(c));
   const size_t slot = (size_t)4 * c->nb.S * c->nb.S;
-  HIP_TRY(c, scopy(c, c->r_state, state, slot * pool, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.state, state, slot * pool, hipMemcpyHostToDevice));
   if (pool < n)
-    HIP_TRY(c, launch_tile(c->r_state + slot * pool, c->r_state, slot * pool,
+    HIP_TRY(c, launch_tile(c->ring.state + slot * pool, c->ring.state, slot * pool,
                            slot * (n - pool), c->stream));
   std::vector<uint8_t> a(n), t(n);
   std::vector<int16_t> r(n);
   for (int64_t i = 0; i < n; ++i) {
     a[i] = action[i % pool]; r[i] = reward[i % pool]; t[i] = nonterm[i % pool];
   }
-  HIP_TRY(c, scopy(c, c->r_action, a.data(), n, hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->r_reward, r.data(), 2 * n, hipMemcpyHostToDevice));
-  HIP_TRY(c, scopy(c, c->r_nonterm, t.data(), n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.action, a.data(), n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.reward, r.data(), 2 * n, hipMemcpyHostToDevice));
+  HIP_TRY(c, scopy(c, c->ring.nonterm, t.data(), n, hipMemcpyHostToDevice));
   c->head = head;
   c->valid = valid;
   TRY(push_meta(c));
   return prio_rebuild(c);
 }
 
-static int check_batch_out(ddq_ctx* c, int32_t n, float* s0, float* a, float* r, float* s1,
-                           float* nt) {
+static int check_batch_out(ddq_ctx* c, int32_t n, const Minibatch& out) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!s0 || !a || !r || !s1 || !nt) return fail(c, DDQ_EINVAL, "null output buffer");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!out.state || !out.action || !out.reward || !out.next_state || !out.nonterm)
+    return fail(c, DDQ_EINVAL, "null output buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (c->lanes > 1)
     return fail(c, DDQ_ESTATE, "the large-batch sampler does not read a laned ring (%d lanes)",
                 c->lanes);
@@ -1077,7 +1091,8 @@ static int check_batch_out(ddq_ctx* c, int32_t n, float* s0, float* a, float* r,
 int ddq_replay_sample_batch_async(ddq_ctx* c, int32_t n, uint64_t seed, int32_t* idx,
                                   float* state, float* action, float* reward, float* next_state,
                                   float* nonterm) {
-  TRY(check_batch_out(c, n, state, action, reward, next_state, nonterm));
+  const Minibatch out{state, next_state, action, reward, nonterm};
+  TRY(check_batch_out(c, n, out));
   if (!idx) return fail(c, DDQ_EINVAL, "null idx");
   if (2 * (int64_t)n > c->valid)
     return fail(c, DDQ_EINVAL, "batch sampler needs n <= valid/2 (n=%d, valid=%lld)", n,
@@ -1088,23 +1103,20 @@ int ddq_replay_sample_batch_async(ddq_ctx* c, int32_t n, uint64_t seed, int32_t*
     TRY(dalloc(c, &c->r_bitmap, (size_t)nblk * 1024));
     TRY(dalloc(c, &c->r_blk, (size_t)nblk));
   }
-  HIP_TRY(c, launch_sample_batch(c->r_meta, c->valid, n, seed, c->batch_ctr++, c->r_bitmap,
+  HIP_TRY(c, launch_sample_batch(c->ring.meta, c->valid, n, seed, c->batch_ctr++, c->r_bitmap,
                                  c->r_blk, idx, c->stream, c->nstep));
-  HIP_TRY(c, launch_gather_nchw(c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                                idx, n, c->nb.S, state, next_state, action, reward, nonterm,
-                                c->stream, c->nstep));
+  HIP_TRY(c, launch_gather_nchw(c->ring, idx, n, c->nb.S, out, c->stream, c->nstep));
   return DDQ_OK;
 }
 
 int ddq_replay_gather_batch_async(ddq_ctx* c, const int32_t* idx, int32_t n, float* state,
                                   float* action, float* reward, float* next_state,
                                   float* nonterm) {
-  TRY(check_batch_out(c, n, state, action, reward, next_state, nonterm));
+  const Minibatch out{state, next_state, action, reward, nonterm};
+  TRY(check_batch_out(c, n, out));
   if (!idx) return fail(c, DDQ_EINVAL, "null idx");
   TRY(set_dev(c));
-  HIP_TRY(c, launch_gather_nchw(c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                                idx, n, c->nb.S, state, next_state, action, reward, nonterm,
-                                c->stream, c->nstep));
+  HIP_TRY(c, launch_gather_nchw(c->ring, idx, n, c->nb.S, out, c->stream, c->nstep));
   return DDQ_OK;
 }
 
@@ -1116,7 +1128,7 @@ int ddq_index_log_enable(ddq_ctx* c, int64_t draws) {
   // the ring restarts at the current draw: earlier draws (or entries of a
   // ring of another capacity) are never reported as logged
   ReplayMeta m;
-  HIP_TRY(c, scopy(c, &m, c->r_meta, sizeof(m), hipMemcpyDeviceToHost));
+  HIP_TRY(c, scopy(c, &m, c->ring.meta, sizeof(m), hipMemcpyDeviceToHost));
   c->log_first = (int64_t)m.counter;
   if (draws == 0) {
     c->nb.idx_log = nullptr;
@@ -1136,10 +1148,10 @@ int ddq_index_log_enable(ddq_ctx* c, int64_t draws) {
 
 int ddq_replay_draws(ddq_ctx* c, int64_t* draws) {
   if (!c || !draws) return fail(c, DDQ_EINVAL, "null argument");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   TRY(set_dev(c));
   ReplayMeta m;
-  HIP_TRY(c, hipMemcpyAsync(&m, c->r_meta, sizeof(m), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&m, c->ring.meta, sizeof(m), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *draws = (int64_t)m.counter;
   return DDQ_OK;
@@ -1165,7 +1177,7 @@ int ddq_index_log_read(ddq_ctx* c, int64_t first, int64_t n, int32_t* out) {
 
 int ddq_replay_status(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   TRY(set_dev(c));
   return check_err_flag(c);
 }
@@ -1173,7 +1185,7 @@ int ddq_replay_status(ddq_ctx* c) {
 int ddq_read_indices(ddq_ctx* c, int32_t* idx, int32_t batch) {
   if (!c || !idx || batch != c->nb.B) return fail(c, DDQ_EINVAL, "bad argument");
   TRY(set_dev(c));
-  HIP_TRY(c, hipMemcpyAsync(idx, c->nb.idx, batch * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(idx, c->nb.mb.idx, batch * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;
 }
@@ -1188,16 +1200,16 @@ int ddq_read_minibatch(ddq_ctx* c, float* state, float* action, float* reward, f
   for (int which = 0; which < 2; ++which) {
     float* dst = which ? next_state : state;
     if (!dst) continue;
-    HIP_TRY(c, scopy(c, tmp.data(), which ? c->nb.next_state : c->nb.state, tmp.size() * 4,
+    HIP_TRY(c, scopy(c, tmp.data(), which ? c->nb.mb.next_state : c->nb.mb.state, tmp.size() * 4,
                          hipMemcpyDeviceToHost));
     for (int b = 0; b < B; ++b)
       for (int ch = 0; ch < 4; ++ch)
         for (int p = 0; p < SS; ++p)
           dst[((size_t)b * 4 + ch) * SS + p] = tmp[((size_t)b * SS + p) * 4 + ch];
   }
-  if (action) HIP_TRY(c, scopy(c, action, c->nb.action, B * 16, hipMemcpyDeviceToHost));
-  if (reward) HIP_TRY(c, scopy(c, reward, c->nb.reward, B * 4, hipMemcpyDeviceToHost));
-  if (nonterm) HIP_TRY(c, scopy(c, nonterm, c->nb.nonterm, B * 4, hipMemcpyDeviceToHost));
+  if (action) HIP_TRY(c, scopy(c, action, c->nb.mb.action, B * 16, hipMemcpyDeviceToHost));
+  if (reward) HIP_TRY(c, scopy(c, reward, c->nb.mb.reward, B * 4, hipMemcpyDeviceToHost));
+  if (nonterm) HIP_TRY(c, scopy(c, nonterm, c->nb.mb.nonterm, B * 4, hipMemcpyDeviceToHost));
   return DDQ_OK;
 }
 
@@ -1215,14 +1227,14 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
       for (int ch = 0; ch < 4; ++ch)
         for (int p = 0; p < SS; ++p)
           tmp[((size_t)b * SS + p) * 4 + ch] = src[((size_t)b * 4 + ch) * SS + p];
-    HIP_TRY(c, scopy(c, which ? c->nb.next_state : c->nb.state, tmp.data(), tmp.size() * 4,
+    HIP_TRY(c, scopy(c, which ? c->nb.mb.next_state : c->nb.mb.state, tmp.data(), tmp.size() * 4,
                          hipMemcpyHostToDevice));
   }
-  if (action) HIP_TRY(c, scopy(c, c->nb.action, action, B * 16, hipMemcpyHostToDevice));
-  if (reward) HIP_TRY(c, scopy(c, c->nb.reward, reward, B * 4, hipMemcpyHostToDevice));
-  if (nonterm) HIP_TRY(c, scopy(c, c->nb.nonterm, nonterm, B * 4, hipMemcpyHostToDevice));
-  if (c->nb.isw) {   // a minibatch set directly has no draw: weights 1
-    HIP_TRY(c, launch_fill_ones(c->nb.isw, B, c->stream));
+  if (action) HIP_TRY(c, scopy(c, c->nb.mb.action, action, B * 16, hipMemcpyHostToDevice));
+  if (reward) HIP_TRY(c, scopy(c, c->nb.mb.reward, reward, B * 4, hipMemcpyHostToDevice));
+  if (nonterm) HIP_TRY(c, scopy(c, c->nb.mb.nonterm, nonterm, B * 4, hipMemcpyHostToDevice));
+  if (c->nb.mb.isw) {   // a minibatch set directly has no draw: weights 1
+    HIP_TRY(c, launch_fill_ones(c->nb.mb.isw, B, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   c->idx_bound = false;
@@ -1230,19 +1242,9 @@ int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, con
 }
 
 // ---------------- compute ----------------
-// The profile marks of a step (ddq_profile_step): m(name) names the kernel
-// launched next; without fn (every other caller) it does nothing.
-struct Marks {
-  void (*fn)(void*, const char*) = nullptr;
-  void* arg = nullptr;
-  void operator()(const char* name) const {
-    if (fn) fn(arg, name);
-  }
-};
-
 // Double target (ddq_set_objective): Q(s',.) under theta_Q for the minibatch view
 // the pass trains on, the pass's first launch group -- ddq_forward_q's kernels
-// at n = B over nb.next_state in the acting scratch (the actor, pool and
+// at n = B over nb.mb.next_state in the acting scratch (the actor, pool and
 // evaluator are serial on the same stream), into the ctx's Qn_out buffer.  It
 // depends on theta_Q and the bound view only: stream order after the previous
 // step's apply is enough.  Profile names: "qn_<kernel>".
@@ -1252,24 +1254,25 @@ static void qn_mark(void* a, const char* name) {
 }
 static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
   if (nb.obj_target != DDQ_TARGET_DOUBLE) return DDQ_OK;
-  HIP_TRY(c, launch_act(nb, nb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
-                        nullptr, c->act_p1s, c->act_p2s, c->stream, m.fn ? qn_mark : nullptr, &m));
+  const Marks qn = m.fn ? Marks{qn_mark, &m} : Marks{};
+  HIP_TRY(c, launch_act(nb, nb.mb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
+                        nullptr, c->act_p1s, c->act_p2s, c->stream, qn));
   return DDQ_OK;
 }
 
 // The gradient launches of a step as sl.plan has them; fc4_done: the
-// overlapped all-reduce's start (launch_backward).
+// overlapped all-reduce's start, its argument the ctx (launch_backward).
 // (one stream: forking the weight-gradient kernels onto a side stream cost
 // more in cross-stream graph edges (6-14 us idle each, measured) than the
 // overlap returned, as every kernel here fills the GPU on its own)
 static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, const StepLaunch& sl, Marks m = {},
-                           hipError_t (*fc4_done)(void*) = nullptr, const NetBuffers* prio_next = nullptr,
+                           Fc4Done fc4_done = {}, const NetBuffers* prio_next = nullptr,
                            uint64_t prio_seed = 0) {
   TRY(enqueue_qn_forward(c, nb, m));
   if (nb.small) {
-    HIP_TRY(c, launch_small_fwd_head(nb, sl, c->stream, m.fn, m.arg));
+    HIP_TRY(c, launch_small_fwd_head(nb, sl, c->stream, m));
   } else {
-    HIP_TRY(c, launch_forward(nb, 2, c->stream, m.fn, m.arg, false));
+    HIP_TRY(c, launch_forward(nb, 2, c->stream, m, false));
     m("head");
     HIP_TRY(c, launch_head(nb, sl, c->stream));
   }
@@ -1281,8 +1284,8 @@ static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, const StepLaunch& s
     HIP_TRY(c, launch_prio_commit_draw(nb, sl.meta, sl.plan.draw == Site::PrioCommit ? prio_next : nullptr,
                                        prio_seed, c->stream));
   }
-  hipError_t e = nb.small ? launch_small_bwd(nb, sl, c->stream, m.fn, m.arg, fc4_done, c)
-                          : launch_backward(nb, sl, c->stream, m.fn, m.arg, fc4_done, c);
+  hipError_t e = nb.small ? launch_small_bwd(nb, sl, c->stream, m, fc4_done)
+                          : launch_backward(nb, sl, c->stream, m, fc4_done);
   if (e != hipSuccess && !c->comm_err.empty()) {
     std::string m = c->comm_err;
     c->comm_err.clear();
@@ -1329,7 +1332,7 @@ int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
     if (!nb.qn_out) TRY(dalloc(c, &nb.qn_out, (size_t)nb.B * 4));
     // one run of the extra forward now: its kernels' function attributes are set
     // outside any capture (the result is overwritten by the first pass)
-    HIP_TRY(c, launch_act(nb, nb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
+    HIP_TRY(c, launch_act(nb, nb.mb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
                           nullptr, c->act_p1s, c->act_p2s, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
@@ -1348,7 +1351,7 @@ int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
 int ddq_forward_q(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(set_dev(c));
-  HIP_TRY(c, launch_act(c->nb, c->nb.state, c->nb.B, c->act_p3, c->act_h4, c->act_part,
+  HIP_TRY(c, launch_act(c->nb, c->nb.mb.state, c->nb.B, c->act_p3, c->act_h4, c->act_part,
                         c->nb.q_out, nullptr, c->act_p1s, c->act_p2s, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;
@@ -1362,7 +1365,7 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_sa", c->nb.q_sa, B},         {"P_sa", c->nb.p_sa, B},
       {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1},
       {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B},
-      {"is_weight", c->nb.isw, B},       {"grad_norm", c->nb.gnorm, 1}};
+      {"is_weight", c->nb.mb.isw, B},       {"grad_norm", c->nb.gnorm, 1}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
@@ -1370,7 +1373,7 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
         return fail(c, DDQ_ESTATE, "blob grad_norm exists while Adam's gradient clipping is on");
       if (!strcmp(name, "Qn_out") && c->nb.obj_target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
-      if (!strcmp(name, "is_weight") && !c->nb.isw)
+      if (!strcmp(name, "is_weight") && !c->nb.mb.isw)
         return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       TRY(set_dev(c));
       return copy_out(c, dst, e.p, n, 0);
@@ -1503,17 +1506,12 @@ static EnvIO env_io(const ddq_ctx* c, const EnvBufs<Game>& b) {
   return EnvIO{b.maps, b.in, c->nb.S, b.n};
 }
 
-static EnvRing env_ring(const ddq_ctx* c) {
-  return EnvRing{c->r_state,   c->r_action, c->r_reward,
-                 c->r_nonterm, c->r_meta,   c->prio_on ? c->d_prio : nullptr};
-}
-
-static ActorRole actor_role(const ddq_ctx* c) { return ActorRole{c->a_env.games, env_ring(c)}; }
+static ActorRole actor_role(const ddq_ctx* c) { return ActorRole{c->a_env.games, c->ring}; }
 static EvalRole eval_role(const ddq_ctx* c) {
   return EvalRole{c->e_env.games, c->e_log, c->e_max_moves, c->e_max_ep};
 }
 static PoolRole pool_role(const ddq_ctx* c) {
-  return PoolRole{c->p_env.games, env_ring(c), c->lane_len, c->p_h0, c->p_v0};
+  return PoolRole{c->p_env.games, c->ring, c->lane_len, c->p_h0, c->p_v0};
 }
 
 // (Re)create an environment: its buffers allocated once with room for `room`
@@ -1567,7 +1565,7 @@ int ddq_actor_create(ddq_ctx* c, const int8_t* init_board, const int32_t* row_ma
   std::vector<uint8_t> maps;
   TRY(env_pack_maps(c, row_map, col_map, &maps));
   TRY(env_check_boards(c, init_board, 1, true));
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (c->lanes > 1)
     return fail(c, DDQ_ESTATE, "ddq_actor_create on a laned ring (%d lanes): use ddq_actors_create",
                 c->lanes);
@@ -1688,7 +1686,7 @@ int ddq_actors_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards,
   std::vector<uint8_t> maps;
   TRY(env_pack_maps(c, row_map, col_map, &maps));
   TRY(env_check_boards(c, init_boards, ngames, false));
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
   if (ngames != c->lanes)
     return fail(c, DDQ_EINVAL, "ngames %d != the ring's %d lanes (ddq_replay_set_lanes)", ngames,
                 c->lanes);
@@ -1996,7 +1994,7 @@ static int plan_launches(ddq_ctx* c, const ddq_step_cfg* cfg, const StepFacts& f
   const char* why = "";
   if (!plan_step(f, &sl->plan, &why)) return fail(c, DDQ_ESTATE, "internal: %s", why);
   sl->u = rule_of(cfg->update, cfg->target_period);
-  sl->meta = c->r_meta;
+  sl->meta = c->ring.meta;
   sl->fc4_wait = sl->plan.ext() ? c->cev[2] : nullptr;
   return DDQ_OK;
 }
@@ -2089,20 +2087,17 @@ static int enqueue_draw(ddq_ctx* c, const NetBuffers& nb, uint64_t seed, hipStre
                         Marks m = {}) {
   if (c->prio_on) {   // one workgroup descends the sum tree, then the plain gather
     m("prio_sample");
-    HIP_TRY(c, launch_prio_sample(nb, c->r_meta, seed, stream));
+    HIP_TRY(c, launch_prio_sample(nb, c->ring.meta, seed, stream));
     m("gather");
-    HIP_TRY(c, launch_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             stream));
+    HIP_TRY(c, launch_gather(nb, c->ring, stream));
   } else if (nb.B <= 256) {   // one kernel: every gather workgroup draws the same index set
     m("sample_gather");
-    HIP_TRY(c, launch_sample_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm,
-                                    c->r_meta, seed, stream));
+    HIP_TRY(c, launch_sample_gather(nb, c->ring, seed, stream));
   } else {
     m("sample");
-    HIP_TRY(c, launch_sample(nb, c->r_meta, seed, stream));
+    HIP_TRY(c, launch_sample(nb, c->ring.meta, seed, stream));
     m("gather");
-    HIP_TRY(c, launch_gather(nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                             stream));
+    HIP_TRY(c, launch_gather(nb, c->ring, stream));
   }
   return DDQ_OK;
 }
@@ -2129,8 +2124,7 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
   const bool side = sl.plan.draw == Site::Side, overlap = f.ex == Exchange::AllReduceOverlap;
   Prefetch pf;
   if (on_ctx_stream(sl.plan.gather)) {
-    pf = make_prefetch(*pre, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                       cfg->seed);
+    pf = make_prefetch(*pre, c->ring, cfg->seed);
     pf.predrawn = sl.plan.predrawn();
     sl.next = &pf;
   }
@@ -2140,7 +2134,8 @@ static int enqueue_train_body(ddq_ctx* c, const ddq_step_cfg* cfg, const NetBuff
     TRY(enqueue_draw(c, *pre, cfg->seed, nb.side));
     HIP_TRY(c, hipEventRecord(nb.ev[7], nb.side));
   }
-  TRY(enqueue_fwd_bwd(c, nb, sl, m, overlap ? fc4_bucket_start : nullptr, pre, cfg->seed));
+  const Fc4Done fc4_done = overlap ? Fc4Done{fc4_bucket_start, c} : Fc4Done{};
+  TRY(enqueue_fwd_bwd(c, nb, sl, m, fc4_done, pre, cfg->seed));
   TRY(enqueue_exchange_apply(c, cfg, nb, sl, m, overlap));
   if (side) HIP_TRY(c, hipStreamWaitEvent(c->stream, nb.ev[7], 0));
   return DDQ_OK;
@@ -2165,14 +2160,10 @@ static int enqueue_step(ddq_ctx* c, const ddq_step_cfg* cfg, Marks m = {}, bool 
   return enqueue_train(c, cfg, c->nb, nullptr, m, fault);
 }
 
-// minibatch set p: 0 = the ctx's own buffers, 1 = the pipelining twin
+// the ctx's buffers with minibatch set p (0 = its own, 1 = the pipelining twin)
 static NetBuffers mb_view(const ddq_ctx* c, int p) {
   NetBuffers v = c->nb;
-  if (p == 1) {
-    v.state = c->mb2_state; v.next_state = c->mb2_next; v.action = c->mb2_action;
-    v.reward = c->mb2_reward; v.nonterm = c->mb2_nonterm; v.idx = c->mb2_idx;
-    if (c->prio_on) v.isw = c->mb2_reward + c->nb.B;
-  }
+  v.mb = c->mb[p];
   return v;
 }
 
@@ -2192,7 +2183,7 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (!cfg) return fail(c, DDQ_EINVAL, "null step cfg");
   TRY(check_cfg(c, &cfg->update));
-  if (!c->r_state) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer");
   if (too_few_slots(c, c->nb.B))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 c->nb.B, (long long)(c->lanes * c->valid));
@@ -2310,9 +2301,7 @@ static int async_owner_apply(ddq_ctx* c, const ddq_step_cfg* cfg, int64_t it, bo
   // (the apply kernel indexes the gradient slice from the shard's start)
   const float* g = own ? c->nb.grad + off : c->gsl;
   Prefetch pf{};
-  if (draw)
-    pf = make_prefetch(c->nb, c->r_state, c->r_action, c->r_reward, c->r_nonterm, c->r_meta,
-                       cfg->seed);
+  if (draw) pf = make_prefetch(c->nb, c->ring, cfg->seed);
   ShardOpts o;
   o.theta = c->own;
   o.first = c->applied == 0 ? 1 : 0;
@@ -2736,14 +2725,9 @@ static int ensure_pipe(ddq_ctx* c, const ddq_step_cfg* cfg) {
     return fail(c, DDQ_EINVAL, "the async exchange runs round-robin rounds (ddq_step_async, "
                                "ddq_step_graph_async) or ticks (ddq_async_tick)");
   TRY(check_not_async(c));
-  if (!c->mb2_state) {
-    const int B = c->nb.B, S = c->nb.S;
-    TRY(dalloc(c, &c->mb2_state, (size_t)B * S * S * 4));
-    TRY(dalloc(c, &c->mb2_next, (size_t)B * S * S * 4));
-    TRY(dalloc(c, &c->mb2_action, (size_t)B * 4));
-    TRY(dalloc(c, &c->mb2_reward, (size_t)2 * B));   // (rewards, then weights, as nb.reward)
-    TRY(dalloc(c, &c->mb2_nonterm, (size_t)B));
-    TRY(dalloc(c, &c->mb2_idx, (size_t)B));
+  if (!c->mb[1].state) {
+    TRY(mb_alloc(c, &c->mb[1]));
+    mb_bind_weights(c, c->prio_on);
   }
   auto& g = c->graphs.pipe;
   if (g.holds(cfg)) return DDQ_OK;
@@ -3255,9 +3239,9 @@ int ddq_time_layer(ddq_ctx* c, const char* name, int32_t reps, float* usec) {
   hipEvent_t e0, e1;
   HIP_TRY(c, hipEventCreate(&e0));
   HIP_TRY(c, hipEventCreate(&e1));
-  hipError_t e = launch_forward(nb, 2, c->stream, nullptr, nullptr, true, l);   // warm
+  hipError_t e = launch_forward(nb, 2, c->stream, {}, true, l);   // warm
   if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-  for (int i = 0; i < reps && e == hipSuccess; ++i) e = launch_forward(nb, 2, c->stream, nullptr, nullptr, true, l);
+  for (int i = 0; i < reps && e == hipSuccess; ++i) e = launch_forward(nb, 2, c->stream, {}, true, l);
   if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
   if (e == hipSuccess) e = hipEventSynchronize(e1);
   float ms = 0.f;

@@ -120,7 +120,8 @@ __device__ __forceinline__ void actor_store_nhwc(float* __restrict__ in, int p,
 // -1 after a terminal step: the slot's frames stay stale).
 
 // the transition's scalars into ring slot `slot`
-__device__ __forceinline__ void ring_put(const EnvRing& ring, int64_t slot, int act, int reward) {
+__device__ __forceinline__ void ring_put(const ReplayRing& ring, int64_t slot, int act,
+                                         int reward) {
   ring.action[slot] = (uint8_t)act;
   ring.reward[slot] = (int16_t)reward;
   ring.nonterm[slot] = reward < 0 ? 0 : 1;

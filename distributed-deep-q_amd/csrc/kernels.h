@@ -93,11 +93,50 @@ struct PrioTree {
   PrioState* st;
 };
 
-struct NetBuffers {
-  int B, S;
-  // minibatch (NHWC frames; action one-hot (B,4); reward / non_terminal (B))
+// The replay ring in device memory: every launch that reads or adds to it
+// takes this view.  A member of ActorRole / PoolRole (kernel arguments): the
+// layout is fixed.
+struct ReplayRing {
+  uint8_t* state;
+  uint8_t* action;
+  int16_t* reward;
+  uint8_t* nonterm;
+  ReplayMeta* meta;
+  const PrioTree* prio;             // device copy of the tree; nullptr: prioritization off
+};
+
+// One minibatch set: NHWC frames, action one-hot (B,4), reward / non_terminal
+// (B), the ring slots they were gathered from.  isw: the importance-sampling
+// weights (B) of prioritized replay, bound only while it is on and then always
+// reward + B, the second half of the reward buffer (the head then runs its
+// objective instantiation, reads them there and scales dQ and the loss terms
+// by them).
+struct Minibatch {
   float *state, *next_state, *action, *reward, *nonterm;
   int32_t* idx;
+  float* isw;
+};
+
+// The profile marks of a step (ddq_profile_step): m(name) names the kernel
+// launched next; without fn (every other caller) it does nothing.
+struct Marks {
+  void (*fn)(void*, const char*) = nullptr;
+  void* arg = nullptr;
+  void operator()(const char* name) const {
+    if (fn) fn(arg, name);
+  }
+};
+// Called right after the fc4 weight gradient is enqueued (the overlapped
+// all-reduce starts there); without fn it does nothing.
+struct Fc4Done {
+  hipError_t (*fn)(void*) = nullptr;
+  void* arg = nullptr;
+  hipError_t operator()() const { return fn ? fn(arg) : hipSuccess; }
+};
+
+struct NetBuffers {
+  int B, S;
+  Minibatch mb;                     // the set the launches train on and draw into
   // activations per tower z (0 = Q on state, 1 = P on next_state): pool1 /
   // pool2 in one buffer each, sized for their split form (3 bf16 planes,
   // NHWC) -- the S = 16 small-map step keeps the Q tower's split there (its K4
@@ -145,12 +184,7 @@ struct NetBuffers {
   int obj_target = 0, obj_loss = 0;
   float huber_delta = 0.f;
   float* qn_out = nullptr;
-  // prioritized replay: the minibatch's importance-sampling weights (B), bound
-  // only while prioritization is on and then always reward + B, the second half
-  // of the reward buffer (the head then runs its objective instantiation, reads
-  // them there and scales dQ and the loss terms by them); prio: the tree
-  float* isw = nullptr;
-  PrioTree prio{};
+  PrioTree prio{};                  // prioritized replay: the tree (leaf == nullptr: off)
   // Adam (ddq_set_adam, adam.h): opt holds the first moment, opt2 the second;
   // gn_part: the gradient-norm launch's partials; gnorm: the last pre-clip norm
   float* opt2 = nullptr;
@@ -174,15 +208,12 @@ struct NetBuffers {
 
 // fused device draw + gather for the step (B <= 256); the step moves the
 // counter on (StepPlan::bump)
-hipError_t launch_sample_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t* act,
-                                const int16_t* rew, const uint8_t* nt, ReplayMeta* meta,
-                                uint64_t seed, hipStream_t s);
-hipError_t launch_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t* act,
-                         const int16_t* rew, const uint8_t* nt, ReplayMeta* meta,
-                         hipStream_t s);
+hipError_t launch_sample_gather(const NetBuffers& nb, const ReplayRing& ring, uint64_t seed,
+                                hipStream_t s);
+hipError_t launch_gather(const NetBuffers& nb, const ReplayRing& ring, hipStream_t s);
 hipError_t launch_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s);
 // only: 0 = every layer, l + 1 = conv layer l alone (ddq_time_layer)
-hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, void (*mark)(void*, const char*), void* mark_arg,
+hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, Marks M = {},
                           bool out = true, int only = 0);
 // deepq16 (nb.small): K1 (towers + the head's bookkeeping, as launch_head's)
 // and K2 (fc4 chain) in place of launch_forward + launch_head
@@ -191,21 +222,17 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, void (*ma
 // *ok = 0 and why set otherwise (the ctx then runs the general kernels)
 hipError_t small_coresident(int B, int* ok, char* why, int nwhy);
 hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
-                                 void (*mark)(void*, const char*), void* mark_arg);
+                                 Marks M = {});
 hipError_t launch_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s);
 bool fused_apply_ok(const ParamLayout& L);
-// fc4_done: called right after the fc4 weight gradient is enqueued (the
-// overlapped all-reduce starts there).
 // deepq16 (nb.small): K3 (data gradients, conv1's weight gradient slabs)
 // and K4 (conv weight gradients + fused apply + bookkeeping + next gather) in
 // place of launch_backward (same arguments)
 hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
-                            void (*mark)(void*, const char*), void* mark_arg,
-                            hipError_t (*fc4_done)(void*), void* fc4_done_arg);
+                            Marks M = {}, Fc4Done fc4_done = {});
 void small_groups(int B, int* G2, int* G3);
 hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
-                           void (*mark)(void*, const char*), void* mark_arg,
-                           hipError_t (*fc4_done)(void*) = nullptr, void* fc4_done_arg = nullptr);
+                           Marks M = {}, Fc4Done fc4_done = {});
 // The next step's draw + gather as extra blocks of the launch StepPlan::gather
 // names (pipelined stepping)
 struct Prefetch {
@@ -223,8 +250,8 @@ struct Prefetch {
   int64_t log_cap;
   float *sQ, *sP, *action, *reward, *nonterm;
 };
-Prefetch make_prefetch(const NetBuffers& next, const uint8_t* st, const uint8_t* act,
-                       const int16_t* rew, const uint8_t* nt, ReplayMeta* meta, uint64_t seed);
+// next: the buffers of the step that trains on the prefetched set (next.mb)
+Prefetch make_prefetch(const NetBuffers& next, const ReplayRing& ring, uint64_t seed);
 // sl.u.period > 0: also copy Q -> P when the next pull sees iteration % period == 0.
 hipError_t launch_apply(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s);
 // rule DDQ_RULE_ADAM (4): launch_apply launches adam_apply_kernel (adam.h) in
@@ -269,11 +296,10 @@ hipError_t launch_book(const NetBuffers& nb, int period, hipStream_t s);
 hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, int64_t slice,
                              hipStream_t s);
 // Q-tower forward of n states (NHWC f32 in `in`) into scratch, argmax into out.
-// mark: the launches' profile names (ddq_profile_step).
+// M: the launches' profile names (ddq_profile_step).
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s,
-                      void (*mark)(void*, const char*) = nullptr, void* mark_arg = nullptr);
+                      __bf16* pool2s, hipStream_t s, Marks M = {});
 // Device-resident Snake environment (env.h): one kernel body, three roles.
 // ActorState: one acting game.  boards: the 4-frame history of 10x10 board
 // codes [x*10+y] (SnakeGame.encode_state), oldest first, then init_board;
@@ -301,15 +327,6 @@ struct EnvIO {
   float* in;                        // [ngames] states as f32 NHWC (S,S,4): the forward's input
   int S, ngames;
 };
-// the replay ring an acting role adds into
-struct EnvRing {
-  uint8_t* state;
-  uint8_t* action;
-  int16_t* reward;
-  uint8_t* nonterm;
-  ReplayMeta* meta;
-  const PrioTree* prio;             // device copy of the tree; nullptr: prioritization off
-};
 // A role is the launch argument that says what its games differ in: the state
 // type, whether the coin is drawn even at thresh == 0, whether a ring slot is
 // rendered, and (env.h) env_idle / env_commit.
@@ -319,7 +336,7 @@ struct ActorRole {
   using Game = ActorState;
   static constexpr bool kCoinAlways = true, kRing = true;
   ActorState* games;
-  EnvRing ring;
+  ReplayRing ring;                  // the ring the role adds into
 };
 // Actor pool (ddq_actors_*): ngames == lanes games, game g adding into lane g of
 // a laned ring at slot g lane_len + (h0 + steps_g) mod lane_len; h0 / v0: the
@@ -329,7 +346,7 @@ struct PoolRole {
   using Game = ActorState;
   static constexpr bool kCoinAlways = true, kRing = true;
   ActorState* games;
-  EnvRing ring;
+  ReplayRing ring;                  // the ring the role adds into
   int64_t lane_len, h0, v0;
 };
 // Policy evaluation (ddq_eval_*): the episode record when the game is over or
@@ -396,10 +413,9 @@ hipError_t launch_monitor(const MonitorEnv& e, int32_t period, int64_t tag, hipS
 hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t seed,
                                uint64_t ctr, uint32_t* bm, int32_t* blk, int32_t* idx,
                                hipStream_t s, int nstep);
-hipError_t launch_gather_nchw(const uint8_t* st, const uint8_t* act, const int16_t* rew,
-                              const uint8_t* nt, ReplayMeta* meta, const int32_t* idx, int n,
-                              int S, float* s0, float* s1, float* action, float* reward,
-                              float* nonterm, hipStream_t s, int nstep);
+// out: the n transitions' buffers (its idx / isw are not read)
+hipError_t launch_gather_nchw(const ReplayRing& ring, const int32_t* idx, int n, int S,
+                              const Minibatch& out, hipStream_t s, int nstep);
 hipError_t launch_tile(uint8_t* dst, const uint8_t* src, uint64_t pool_bytes, uint64_t total,
                        hipStream_t s);
 hipError_t launch_u8_to_nhwc(const uint8_t* src, int n, int S, float* dst, hipStream_t s);
@@ -408,14 +424,14 @@ hipError_t launch_u8_to_nhwc(const uint8_t* src, int n, int S, float* dst, hipSt
 // allocation, graph-capture safe.
 // every filled, allowed slot <- st->pmax, the rest 0, then the sums bottom-up
 hipError_t launch_prio_rebuild(const PrioTree& t, const ReplayMeta* meta, hipStream_t s);
-// one workgroup: the draw counter's stratified sample into nb.idx / nb.isw (and
+// one workgroup: the draw counter's stratified sample into nb.mb.idx / nb.mb.isw (and
 // the index log); advance: the counter moves on afterwards (a step's own
 // launch_prio_commit_draw does that otherwise)
 hipError_t launch_prio_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s,
                               bool advance = false);
 // one workgroup, after the launch that wrote nb.q_sa / nb.target: commit |TD| of
-// nb.idx.  bump: the draw counter advances by one; next != nullptr: then draw
-// the advanced counter's sample into next->idx / next->isw and log it
+// nb.mb.idx.  bump: the draw counter advances by one; next != nullptr: then draw
+// the advanced counter's sample into next->mb.idx / next->mb.isw and log it
 hipError_t launch_prio_commit_draw(const NetBuffers& nb, ReplayMeta* bump, const NetBuffers* next,
                                    uint64_t seed, hipStream_t s);
 // the commit alone (ddq_replay_update_priorities_async)

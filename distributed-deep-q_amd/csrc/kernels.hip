@@ -369,31 +369,30 @@ hipError_t launch_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, 
   int threads = 64;                 // one wave for B <= 64: cheap barriers
   while (threads < nb.B) threads <<= 1;
   auto kern = nb.nstep > 1 ? sample_kernel<true> : sample_kernel<false>;
-  ddq_launch(kern, dim3(1), dim3(threads), 0, s, meta, nb.B, seed, nb.idx,
+  ddq_launch(kern, dim3(1), dim3(threads), 0, s, meta, nb.B, seed, nb.mb.idx,
                      nb.idx_log, nb.log_cap);
   return hipGetLastError();
 }
 
-hipError_t launch_sample_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t* act,
-                                const int16_t* rew, const uint8_t* nt, ReplayMeta* meta,
-                                uint64_t seed, hipStream_t s) {
+hipError_t launch_sample_gather(const NetBuffers& nb, const ReplayRing& r, uint64_t seed,
+                                hipStream_t s) {
   const int SS = nb.S * nb.S;
+  const Minibatch& m = nb.mb;
   dim3 grid((SS / 4 + 255) / 256, nb.B, 2);
   auto kern = nb.nstep > 1 ? sample_gather_kernel<true> : sample_gather_kernel<false>;
-  ddq_launch(kern, grid, dim3(256), 0, s, st, act, rew, nt, meta, nb.B,
-                     seed, nb.idx, nb.S, nb.state, nb.next_state, nb.action, nb.reward,
-                     nb.nonterm, nb.idx_log, nb.log_cap);
+  ddq_launch(kern, grid, dim3(256), 0, s, r.state, r.action, r.reward, r.nonterm, r.meta, nb.B,
+             seed, m.idx, nb.S, m.state, m.next_state, m.action, m.reward, m.nonterm, nb.idx_log,
+             nb.log_cap);
   return hipGetLastError();
 }
 
-hipError_t launch_gather(const NetBuffers& nb, const uint8_t* st, const uint8_t* act,
-                         const int16_t* rew, const uint8_t* nt, ReplayMeta* meta,
-                         hipStream_t s) {
+hipError_t launch_gather(const NetBuffers& nb, const ReplayRing& r, hipStream_t s) {
   const int SS = nb.S * nb.S;
+  const Minibatch& m = nb.mb;
   dim3 grid((SS / 4 + 255) / 256, nb.B, 2);
   auto kern = nb.nstep > 1 ? gather_kernel<true> : gather_kernel<false>;
-  ddq_launch(kern, grid, dim3(256), 0, s, st, act, rew, nt, meta, nb.idx, nb.S,
-                     nb.state, nb.next_state, nb.action, nb.reward, nb.nonterm);
+  ddq_launch(kern, grid, dim3(256), 0, s, r.state, r.action, r.reward, r.nonterm, r.meta, m.idx,
+             nb.S, m.state, m.next_state, m.action, m.reward, m.nonterm);
   return hipGetLastError();
 }
 
@@ -581,16 +580,15 @@ hipError_t launch_sample_batch(ReplayMeta* meta, int64_t valid, int n, uint64_t 
   return hipGetLastError();
 }
 
-hipError_t launch_gather_nchw(const uint8_t* st, const uint8_t* act, const int16_t* rew,
-                              const uint8_t* nt, ReplayMeta* meta, const int32_t* idx, int n,
-                              int S, float* s0, float* s1, float* action, float* reward,
-                              float* nonterm, hipStream_t s, int nstep) {
+hipError_t launch_gather_nchw(const ReplayRing& r, const int32_t* idx, int n, int S,
+                              const Minibatch& out, hipStream_t s, int nstep) {
   const uint32_t wps = (uint32_t)(S * S);          // 4-byte words per slot
   const uint32_t per = 256u * kGatherWpt;
   const uint32_t cpr = (wps + per - 1) / per;       // n * cpr < 2^31 (n <= 2^31 / S^2 checked)
   auto kern = nstep > 1 ? gather_nchw_kernel<true> : gather_nchw_kernel<false>;
-  ddq_launch(kern, dim3((uint32_t)n * cpr, 2), dim3(256), 0, s, st, act, rew, nt,
-             meta, idx, n, wps, FastDiv(cpr), s0, s1, action, reward, nonterm);
+  ddq_launch(kern, dim3((uint32_t)n * cpr, 2), dim3(256), 0, s, r.state, r.action, r.reward,
+             r.nonterm, r.meta, idx, n, wps, FastDiv(cpr), out.state, out.next_state, out.action,
+             out.reward, out.nonterm);
   return hipGetLastError();
 }
 
@@ -789,7 +787,7 @@ struct HeadArgs {
   int obj_target, obj_loss;
   float huber_delta;
   // prioritized replay: the minibatch's importance-sampling weights follow its
-  // rewards, reward[B..2B) (NetBuffers::isw; read by the objective instantiation
+  // rewards, reward[B..2B) (Minibatch::isw; read by the objective instantiation
   // only).  The flag sits in the hole before qn: no offset of the struct moves
   int weighted;
   const float* qn;
@@ -1257,14 +1255,14 @@ static hipError_t head_book(const NetBuffers& nb, const StepLaunch& sl, sm16::Bo
 static HeadArgs head_args(const NetBuffers& nb, const sm16::BookArgs& k) {
   const ParamLayout& L = nb.L;
   return HeadArgs{nb.fc4_part, nb.fc4_splits, nb.B, nb.gamma, nb.theta[0], nb.theta[1], L.b[3],
-                  L.w[4], L.b[4], nb.action, nb.reward, nb.nonterm, nb.h4[0], nb.h4[1], nb.q_out,
+                  L.w[4], L.b[4], nb.mb.action, nb.mb.reward, nb.mb.nonterm, nb.h4[0], nb.h4[1], nb.q_out,
                   nb.p_out, nb.q_sa, nb.p_sa, nb.target, nb.dqbuf, nb.lpart, nb.dh4,
                   k.latch, k.iter, k.period, k.inc, k.bump, nb.wks[0],
                   L.wks_total,
                   L.wks_off[1], L.wkst_off,
                   L.wks_off[2], L.wkst3_off,
                   k.dmeta, k.didx, k.dseed, k.dlog, k.dlog_cap,
-                  nb.obj_target, nb.obj_loss, nb.huber_delta, nb.isw != nullptr, nb.qn_out};
+                  nb.obj_target, nb.obj_loss, nb.huber_delta, nb.mb.isw != nullptr, nb.qn_out};
 }
 
 static Fc4DgradArgs fc4_dgrad_args(const NetBuffers& nb, bool& narrow, int& ndx, int& nd) {
@@ -1849,17 +1847,18 @@ hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, in
   return hipGetLastError();
 }
 
-Prefetch make_prefetch(const NetBuffers& next, const uint8_t* st, const uint8_t* act,
-                       const int16_t* rew, const uint8_t* nt, ReplayMeta* meta, uint64_t seed) {
+Prefetch make_prefetch(const NetBuffers& next, const ReplayRing& r, uint64_t seed) {
+  const Minibatch& m = next.mb;
   Prefetch pf;
-  pf.st = st; pf.act = act; pf.rew = rew; pf.nt = nt; pf.meta = meta; pf.seed = seed;
+  pf.st = r.state; pf.act = r.action; pf.rew = r.reward; pf.nt = r.nonterm; pf.meta = r.meta;
+  pf.seed = seed;
   pf.B = next.B; pf.S = next.S;
   pf.predrawn = 0;
   pf.gx = (next.S * next.S / 4 + 255) / 256;
   pf.ng = pf.gx * next.B * 2;
-  pf.idx = next.idx; pf.sQ = next.state; pf.sP = next.next_state;
+  pf.idx = m.idx; pf.sQ = m.state; pf.sP = m.next_state;
   pf.idx_log = next.idx_log; pf.log_cap = next.log_cap;
-  pf.action = next.action; pf.reward = next.reward; pf.nonterm = next.nonterm;
+  pf.action = m.action; pf.reward = m.reward; pf.nonterm = m.nonterm;
   return pf;
 }
 
@@ -2057,7 +2056,7 @@ static sm16::TowerArgs tower_args(const NetBuffers& nb, int nz, const sm16::Book
   const ParamLayout& L = nb.L;
   sm16::TowerArgs t{};
   t.B = nb.B; t.nz = nz;
-  t.in[0] = nb.state; t.in[1] = nb.next_state;
+  t.in[0] = nb.mb.state; t.in[1] = nb.mb.next_state;
   for (int z = 0; z < 2; ++z) {
     t.wks[z] = nb.wks[z];
     t.bias1[z] = nb.theta[z] + L.b[0];
@@ -2078,12 +2077,11 @@ static sm16::TowerArgs tower_args(const NetBuffers& nb, int nz, const sm16::Book
   return t;
 }
 
-hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
-                          void (*mark)(void*, const char*), void* marg, bool out, int only) {
+hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, Marks M, bool out,
+                          int only) {
   const ParamLayout& L = nb.L;
   const int B = nb.B, S = nb.S;
-  auto M = [&](const char* n) { if (mark) mark(marg, n); };
-  const float* in[2] = {nb.state, nb.next_state};
+  const float* in[2] = {nb.mb.state, nb.mb.next_state};
   // deepq16: conv1 -> pool3 of each (image, tower) in one workgroup (small.h)
   const bool tower = !only && nb.small;
   if (tower) {
@@ -2169,9 +2167,8 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s,
 }
 
 hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
-                                 void (*mark)(void*, const char*), void* marg) {
+                                 Marks M) {
   const ParamLayout& L = nb.L;
-  auto M = [&](const char* n) { if (mark) mark(marg, n); };
   // the head's bookkeeping (launch_head / head_args), by K1's extra workgroup
   sm16::BookArgs bk;
   CHECK_LAUNCH(head_book(nb, sl, &bk));
@@ -2183,14 +2180,14 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hip
   c.th[0] = nb.theta[0]; c.th[1] = nb.theta[1];
   c.w4_off = L.w[3]; c.b4_off = L.b[3]; c.w5_off = L.w[4]; c.b5_off = L.b[4];
   if (L.w[3] % 4) return hipErrorInvalidValue;   // (dW4 rows stored as float4)
-  c.action = nb.action; c.reward = nb.reward; c.nonterm = nb.nonterm; c.gamma = nb.gamma;
+  c.action = nb.mb.action; c.reward = nb.mb.reward; c.nonterm = nb.mb.nonterm; c.gamma = nb.gamma;
   c.qpart = nb.qpart; c.dpart = nb.dpart; c.sync = nb.csync;
   c.q_out = nb.q_out; c.p_out = nb.p_out; c.q_sa = nb.q_sa; c.p_sa = nb.p_sa;
   c.target = nb.target; c.loss = nb.loss; c.grad = nb.grad;
   c.dq_out = nb.dqbuf;
   c.obj_target = nb.obj_target; c.obj_loss = nb.obj_loss; c.huber_delta = nb.huber_delta;
   c.qn = nb.qn_out;
-  c.weighted = nb.isw != nullptr;
+  c.weighted = nb.mb.isw != nullptr;
   if (c.obj_target && !c.qn) return hipErrorInvalidValue;
   c.apply = sl.plan.apply == ApplyRange::AllInSlabReduce;
   c.store_grad = sl.plan.store_grad;
@@ -2278,24 +2275,22 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
   return hipSuccess;
 }
 
-hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
-                            void (*mark)(void*, const char*), void* marg,
-                            hipError_t (*fc4_done)(void*), void* fc4_done_arg) {
+hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s, Marks M,
+                            Fc4Done fc4_done) {
   const ParamLayout& L = nb.L;
   const StepPlan& p = sl.plan;
   const bool book = p.book == Site::SlabReduce;
   if (p.bump == Site::SlabReduce && !(book && sl.meta)) return hipErrorInvalidValue;
   const int B = nb.B;
-  auto M = [&](const char* n) { if (mark) mark(marg, n); };
   // fc4's weight gradient is final since K2 (B <= 32; else after K4's chunk
   // sums): the overlapped all-reduce starts
-  if (fc4_done && nb.small_G == 1) CHECK_LAUNCH(fc4_done(fc4_done_arg));
+  if (nb.small_G == 1) CHECK_LAUNCH(fc4_done());
   {
     sm16::BwdArgs a{};
     a.B = B; a.dpart = nb.dpart;
     a.mask1 = nb.mask1; a.mask2 = nb.mask2; a.mask3 = nb.mask3;
     a.wks = nb.wks[0]; a.wks_plane = L.wks_total; a.wkst_off = L.wkst_off; a.wkst3_off = L.wkst3_off;
-    a.frames = nb.state;
+    a.frames = nb.mb.state;
     a.dconv3x = nb.dconv3s; a.dconv2x = nb.dconv2x;
     a.w1part = nb.wpart + nb.wpart_off[0]; a.w1_np = nb.wnp[0];
     M("tower_bwd");
@@ -2361,13 +2356,12 @@ hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStrea
                lds, s, w);
     CHECK_LAUNCH(hipGetLastError());
   }
-  if (fc4_done && nb.small_G > 1) CHECK_LAUNCH(fc4_done(fc4_done_arg));   // (chunk sums done)
+  if (nb.small_G > 1) CHECK_LAUNCH(fc4_done());   // (chunk sums done)
   return hipSuccess;
 }
 
-hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s,
-                           void (*mark)(void*, const char*), void* marg,
-                           hipError_t (*fc4_done)(void*), void* fc4_done_arg) {
+hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s, Marks M,
+                           Fc4Done fc4_done) {
   const ParamLayout& L = nb.L;
   const StepPlan& p = sl.plan;
   const bool book = p.book == Site::SlabReduce;
@@ -2375,7 +2369,6 @@ hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream
   if (p.ext() && !sl.fc4_wait) return hipErrorInvalidValue;
   const int B = nb.B, S = nb.S;
   const int s4 = S / 8;
-  auto M = [&](const char* n) { if (mark) mark(marg, n); };
   {  // fc4 (train_val.prototxt:159-185): data gradient -> pooled dpool3, and
      // the weight gradient unless the fused apply computes it itself
     bool narrow;
@@ -2389,7 +2382,7 @@ hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream
   }
   // the fc4 weight gradient (the bulk of the flat gradient) is final here:
   // the caller may start reducing it over the ranks under the conv backward
-  if (fc4_done) CHECK_LAUNCH(fc4_done(fc4_done_arg));
+  CHECK_LAUNCH(fc4_done());
   {  // conv3 data gradient -> split pooled dpool2 (split bf16 on conv3's
      // transposed + flipped split weights, rebuilt by the head kernel; the fp32
      // dpool3 expanded through pool3's routing and split while staged; 4x8 (kConv3Dgrad)
@@ -2439,7 +2432,7 @@ hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream
     a.in[0] = nb.dconv2s; a.in_elems = (int64_t)B * (H / 2) * (H / 2) * 64;
     a.wk[0] = nb.wks[0] + L.wkst_off; a.wk_elems = L.wks_total;
     a.in_route = nb.mask2;
-    a.w1_route = nb.mask1; a.w1_in = nb.state;
+    a.w1_route = nb.mask1; a.w1_in = nb.mb.state;
     a.w1_part = nb.wpart + nb.wpart_off[0]; a.w1_np = nb.wnp[0];
     M("conv2_dgrad");
     CHECK_LAUNCH(pick_tile(kConv2Dgrad, H, H).launch(a, 1, s));
@@ -2505,12 +2498,11 @@ __global__ void argmax_kernel(int n, const float* __restrict__ qout, int32_t* __
 
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s, void (*mark)(void*, const char*),
-                      void* marg) {
+                      __bf16* pool2s, hipStream_t s, Marks M) {
   NetBuffers a = nb;
   a.B = n;
-  a.state = const_cast<float*>(in);
-  a.next_state = const_cast<float*>(in);
+  a.mb.state = const_cast<float*>(in);
+  a.mb.next_state = const_cast<float*>(in);
   a.pool3[0] = pool3; a.h4[0] = h4;
   a.pool3[1] = pool3; a.h4[1] = h4;
   // (no weight gradient: no split side outputs; the scratch holds fp32)
@@ -2520,9 +2512,9 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
   a.mask1 = a.mask2 = a.mask3 = nullptr;
   a.fc4_part = part;
   a.q_out = qout; a.p_out = qout;
-  CHECK_LAUNCH(launch_forward(a, 1, s, mark, marg));
+  CHECK_LAUNCH(launch_forward(a, 1, s, M));
   if (actions) {
-    if (mark) mark(marg, "argmax");
+    M("argmax");
     ddq_launch(argmax_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, qout, actions);
     CHECK_LAUNCH(hipGetLastError());
   }

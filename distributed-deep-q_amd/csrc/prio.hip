@@ -198,21 +198,21 @@ __global__ __launch_bounds__(256) void prio_commit_draw_kernel(
 
 hipError_t launch_prio_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s,
                               bool advance) {
-  if (!nb.prio.leaf || !nb.isw || nb.B > 256) return hipErrorInvalidValue;
+  if (!nb.prio.leaf || !nb.mb.isw || nb.B > 256) return hipErrorInvalidValue;
   ddq_launch(prio_commit_draw_kernel<false>, dim3(1), dim3(256), 0, s, nb.prio, nb.B,
              (const int32_t*)nullptr, (const float*)nullptr, (const float*)nullptr, meta,
              advance ? 2 : 0, 1, seed,
-             nb.idx, nb.isw, nb.idx_log, nb.log_cap);
+             nb.mb.idx, nb.mb.isw, nb.idx_log, nb.log_cap);
   return hipGetLastError();
 }
 
 hipError_t launch_prio_commit_draw(const NetBuffers& nb, ReplayMeta* bump, const NetBuffers* next,
                                    uint64_t seed, hipStream_t s) {
-  if (!nb.prio.leaf || nb.B > 256 || !bump || (next && !next->isw)) return hipErrorInvalidValue;
+  if (!nb.prio.leaf || nb.B > 256 || !bump || (next && !next->mb.isw)) return hipErrorInvalidValue;
   ddq_launch(prio_commit_draw_kernel<true>, dim3(1), dim3(256), 0, s, nb.prio, nb.B,
-             (const int32_t*)nb.idx, (const float*)nb.q_sa, (const float*)nb.target, bump,
-             1, next ? 1 : 0, seed, next ? next->idx : (int32_t*)nullptr,
-             next ? next->isw : (float*)nullptr, nb.idx_log, nb.log_cap);
+             (const int32_t*)nb.mb.idx, (const float*)nb.q_sa, (const float*)nb.target, bump,
+             1, next ? 1 : 0, seed, next ? next->mb.idx : (int32_t*)nullptr,
+             next ? next->mb.isw : (float*)nullptr, nb.idx_log, nb.log_cap);
   return hipGetLastError();
 }
 
@@ -220,7 +220,7 @@ hipError_t launch_prio_commit_draw(const NetBuffers& nb, ReplayMeta* bump, const
 hipError_t launch_prio_commit(const NetBuffers& nb, ReplayMeta* meta, hipStream_t s) {
   if (!nb.prio.leaf || nb.B > 256) return hipErrorInvalidValue;
   ddq_launch(prio_commit_draw_kernel<true>, dim3(1), dim3(256), 0, s, nb.prio, nb.B,
-             (const int32_t*)nb.idx, (const float*)nb.q_sa, (const float*)nb.target, meta, 0, 0,
+             (const int32_t*)nb.mb.idx, (const float*)nb.q_sa, (const float*)nb.target, meta, 0, 0,
              (uint64_t)0, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, (int64_t)0);
   return hipGetLastError();
 }

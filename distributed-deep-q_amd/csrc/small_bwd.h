@@ -61,7 +61,7 @@ struct ChainArgs {
   const float *action, *reward, *nonterm;
   float gamma;
   // prioritized replay: the minibatch's importance-sampling weights follow its
-  // rewards, reward[B..2B) (NetBuffers::isw; read by the objective instantiation
+  // rewards, reward[B..2B) (Minibatch::isw; read by the objective instantiation
   // only).  The flag sits in the hole before qpart: no offset of the struct moves
   int weighted;
   float* qpart;                    // [32][2][B][4]
