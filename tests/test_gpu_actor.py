@@ -6,7 +6,9 @@
   loop's ``select_action`` on the other.  Both run the same forward kernels at
   n = 1, so the Q values, hence every decision, are expected to be equal; no
   tolerance.  S = 16 (small-map ctx) and S = 24 (general kernels), B = 4,
-  capacity 37, 200 steps at epsilon(0), epsilon(60000) and the knee ramp.
+  capacity 37, 200 steps at epsilon(0), epsilon(60000) and the knee ramp;
+  S = 40 and S = 64 once each at epsilon(60000).  That forward itself is held
+  to the float64 oracle by tests/test_gpu_acting.py.
 * The sampler sees the device adds without a synchronise; the host mirror of
   head / valid follows them.
 * ``act_and_step``: acting interleaved with graph training steps.
@@ -20,7 +22,10 @@ pytestmark = pytest.mark.gpu
 
 B, STEPS = 4, 200
 CASES = [(16, "eps1", "coiled"), (16, "eps01", "start"), (16, "ramp", "apple_ahead"),
-         (24, "eps1", "apple_ahead"), (24, "eps01", "coiled"), (24, "ramp", "start")]
+         (24, "eps1", "apple_ahead"), (24, "eps01", "coiled"), (24, "ramp", "start"),
+         # past S = 24 (general kernels; tests/test_gpu_acting.py holds their Q
+         # values to the oracle): a frame with partial edge tiles, the bench's own
+         (40, "eps01", "start"), (64, "eps01", "coiled")]
 
 
 @pytest.fixture(scope="module")

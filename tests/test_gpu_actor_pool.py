@@ -5,7 +5,8 @@ ddq_replay_set_lanes) on the GPU.  Everything is bit equality.
   holding identical parameters (the pool on one, the host loop's batched
   ``select_action`` on the other; both run the same forward kernels at
   n = ngames): S = 16 (small-map ctx) and S = 24 (general kernels), B = 4,
-  N = 3 and N = B = 4, lane length 7, 40 moves as one call of 3 and one of 37.
+  N = 3 and N = B = 4, lane length 7, 40 moves as one call of 3 and one of 37;
+  S = 64 once at N = 3.
   A pool of one game on a plain ring is the single actor.
 * The draw, exactly: tests/_pool_host.py restates ``draw_sorted`` for B <= 64.
   It is checked first against the index log of a plain ring (code this feature
@@ -30,7 +31,8 @@ pytestmark = pytest.mark.gpu
 
 B, L, MOVES = 4, 7, 40
 # (S, N, regime, seed): seeds chosen with the host loop alone (check_covered)
-POOL_CASES = [(16, 3, "eps1", 2), (16, 4, "eps01", 1), (24, 3, "ramp", 2), (24, 4, "eps1", 2)]
+POOL_CASES = [(16, 3, "eps1", 2), (16, 4, "eps01", 1), (24, 3, "ramp", 2), (24, 4, "eps1", 2),
+              (64, 3, "eps01", 2)]
 # (N, L, h, v)
 LANED = [(3, 8, 0, 8), (3, 8, 0, 5), (3, 8, 3, 8), (3, 8, 5, 5)]
 DRAWS = 32

@@ -5,7 +5,8 @@
   batched ``select_action`` on the other.  Both run the same forward kernels
   at the same n, so the Q values, hence every decision, are expected to be
   equal; no tolerance.  S = 16 (small-map ctx) and S = 24 (general kernels),
-  B = 8, N = 6 games on six different start boards; epsilon 0.25 and 0,
+  B = 8, N = 6 games on six different start boards; epsilon 0.25 and 0
+  (S = 40 and S = 64: epsilon 0),
   ``max_episodes`` = 2 (idle games), chunked runs; N = B and N = 1 once each.
 * Non-interference on a ctx that also holds a ring and a device actor.
 * ``DevicePolicyEvaluator.evaluate`` against the host ``streams="per_game"``
@@ -21,6 +22,9 @@ pytestmark = pytest.mark.gpu
 
 B, N = 8, 6
 CASES = [(S, eps) for S in (16, 24) for eps in (eh.EPS, 0.0)]
+# past S = 24, greedy: a frame with partial edge tiles and the bench's own (their
+# Q values are held to the oracle by tests/test_gpu_acting.py)
+CASES += [(40, 0.0), (64, 0.0)]
 
 
 @pytest.fixture(scope="module")
