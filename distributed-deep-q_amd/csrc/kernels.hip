@@ -2243,7 +2243,7 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
     int threads, lds, meeting;   // meeting: workgroups that wait on each other
   };
   const Launch ls[] = {
-      // K1 split form (2 workgroups per (image, tower), B <= 64): pairs meet
+      // K1 split form (2 workgroups per (image, tower), 2 B nz <= 256): pairs meet
       {"tower_fwd16s", reinterpret_cast<const void*>(sm16::tower_fwd16s_kernel<5, 4>),
        sm16::kThreads, sm16::kFwdSmemS, 4 * B <= 256 ? 4 * B : 0},
       // K2: every fc4 workgroup meets (one tower a workgroup at B <= 32)

@@ -119,6 +119,30 @@ __device__ __forceinline__ void lds_split3(__bf16* p, int plane, float v) {
   p[2 * plane] = l;
 }
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// The split product a x b of one k step (split.h): operand planes 0 / 1 / 2 =
+// high / mid / low; the five cross terms into cor, smallest first, the
+// leading term into acc.  Six MFMAs, 16x16x32 or 32x32x16 by the accumulator.
+__device__ __forceinline__ void split_mfma(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4& acc,
+                                           f32x4& cor) {
+  cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], cor, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
+}
+__device__ __forceinline__ void split_mfma(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& acc,
+                                           f32x16& cor) {
+  cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], cor, 0, 0, 0);
+  cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], cor, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+}
+
 // conv2 weight taps: 3 planes x 64 co x 32 ci = 768 16-byte vectors, thread f
 // and f + 512 (f < 256).  Rows n and n + 4 share an 8-lane ds_write group
 // (SplitWStage::row): conflict-free stores of the 40-bf16 rows.
@@ -182,7 +206,7 @@ __device__ void tower_transpose(const TowerArgs& a, int x, char* smem);
 // (old / n + 1) n, which its last arriver reaches with its own add (no
 // reset / generation round trips on the release path).  Bounded: a spin past
 // ~0.1 s records a timeout in the sticky word and goes on (no hang); callers
-// read the word afterwards (meet_failed) and then write no parameter.
+// read the word afterwards (meet_word) and then write no parameter.
 __device__ __forceinline__ void meet(uint64_t* ctr, uint32_t n, int32_t* timeout) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -403,12 +427,7 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16_kernel(const TowerArgs a
       }
       if (t + 1 < 25) ops(t + 1, (t + 1) & 1);
       const int c = t & 1;
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][2], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][1], bv[c][1], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], bv[c][2], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][1], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], bv[c][1], cor, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], bv[c][0], acc, 0, 0, 0);
+      split_mfma(av[c], bv[c], acc, cor);
       __builtin_amdgcn_sched_barrier(0);
       if (t + 2 < 25) w2[(t + 2) % K2].store(ring2 + ((t + 2) % 3) * W2_SLOT, tid);
       __syncthreads();
@@ -448,7 +467,6 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16_kernel(const TowerArgs a
 
   // ---- conv3: 9 taps on 16x16x32 ----
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, cor = {0.f, 0.f, 0.f, 0.f};
     const int r = lane & 15, kq = lane >> 4;
     const int win = r >> 2, y = 2 * (win >> 1) + ((r >> 1) & 1), x = 2 * (win & 1) + (r & 1);
@@ -470,12 +488,7 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16_kernel(const TowerArgs a
       if (t + K3 < 9) w3[(t + K3) % K3].load(wk3, wpl, t + K3, tid);
       if (t + 1 < 9) ops(t + 1, (t + 1) & 1);
       const int c = t & 1;
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][2], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][1], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][2], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][1], cor, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][0], acc, 0, 0, 0);
+      split_mfma(av[c], bv[c], acc, cor);
       __builtin_amdgcn_sched_barrier(0);
       if (t + 2 < 9) w3[(t + 2) % K3].store(ring3 + ((t + 2) % 3) * W3_SLOT, tid);
       __syncthreads();
@@ -552,22 +565,8 @@ static_assert(3 * Q1_PL * 2 == 41472, "pool1 image");
 constexpr int WH2P_SLOT = 2 * WH2_SLOT;                                // a pair of taps
 static_assert(OFF_R + 3 * WH2P_SLOT * 2 <= kFwdSmemS && kFwdSmemS <= 160 * 1024, "split LDS");
 
-// conv2 half taps: 3 planes x 32 co x 32 ci = 384 vectors (threads < 384)
-struct WH2Tap {
-  u32x4 r;
-  __device__ __forceinline__ void load(const __bf16* __restrict__ wk, int64_t plane, int tap,
-                                       int half, int tid) {
-    const int f = tid < 384 ? tid : 383;
-    const int p = f >> 7, q = f & 127, n = q >> 2, c8 = q & 3;
-    r = *reinterpret_cast<const u32x4*>(wk + p * plane + ((32 * half + n) * 25 + tap) * 32 + 8 * c8);
-  }
-  __device__ __forceinline__ void store(__bf16* slot, int tid) const {
-    if (tid >= 384) return;
-    const int p = tid >> 7, q = tid & 127, n = q >> 2, c8 = q & 3;
-    *reinterpret_cast<u32x4*>(slot + p * WH2_PL + n * WH2_CW + 8 * c8) = r;
-  }
-};
-// conv2 half tap pairs (taps 2s, 2s + 1; tap 25 does not exist: repeats 24)
+// conv2 half tap pairs (taps 2s, 2s + 1; tap 25 does not exist: repeats 24):
+// 2 x 3 planes x 32 co x 32 ci = 2 x 384 vectors (threads < 384)
 struct WH2Pair {
   u32x4 r[2];
   __device__ __forceinline__ void load(const __bf16* __restrict__ wk, int64_t plane, int s,
@@ -751,7 +750,6 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16s_kernel(const TowerArgs 
   // ---- conv2, channels [32 half, +32): 25 taps on 16x16x32 ----
   WH3Pair w3[K3];
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, cor = {0.f, 0.f, 0.f, 0.f};
     const int m = 16 * mb2 + r16;                   // pixel (window-major: 4 windows a block)
     const int win = m >> 2, y = 2 * (win >> 2) + ((m >> 1) & 1), x = 2 * (win & 3) + (m & 1);
@@ -786,12 +784,7 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16s_kernel(const TowerArgs 
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         if (2 * st + u >= 25) continue;
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][2], bv[c][u][0], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][1], bv[c][u][1], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][0], bv[c][u][2], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][1], bv[c][u][0], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][0], bv[c][u][1], cor, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][0], bv[c][u][0], acc, 0, 0, 0);
+        split_mfma(av[c][u], bv[c][u], acc, cor);
       }
       __builtin_amdgcn_sched_barrier(0);
       if (st + 2 < NS) w2[(st + 2) % K2].store(ring2 + ((st + 2) % 3) * WH2P_SLOT, tid);
@@ -838,7 +831,6 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16s_kernel(const TowerArgs 
 
   // ---- conv3, channels [32 half, +32): tap pairs s = 0..4, tap 2s + tg3 ----
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, cor = {0.f, 0.f, 0.f, 0.f};
     const int win = r16 >> 2, y = 2 * (win >> 1) + ((r16 >> 1) & 1), x = 2 * (win & 1) + (r16 & 1);
     const int abase = y * P2_RS + x * P2_CS + 32 * kk3 + 8 * kq;
@@ -860,14 +852,8 @@ __global__ __launch_bounds__(kThreads) void tower_fwd16s_kernel(const TowerArgs 
       if (s + K3 < 5) w3[(s + K3) % K3].load(wk3, wpl, s + K3, half, tid);
       if (s + 1 < 5) ops(s + 1, (s + 1) & 1);
       const int c = s & 1;
-      if (2 * s + tg3 < 9) {                         // (wave-uniform: tap 9 does not exist)
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][2], bv[c][0], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][1], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][2], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][0], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][1], cor, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][0], acc, 0, 0, 0);
-      }
+      if (2 * s + tg3 < 9)                           // (wave-uniform: tap 9 does not exist)
+        split_mfma(av[c], bv[c], acc, cor);
       __builtin_amdgcn_sched_barrier(0);
       if (s + 2 < 5) w3[(s + 2) % K3].store(ring3 + ((s + 2) % 3) * WH3_SLOT, tid);
       __syncthreads();

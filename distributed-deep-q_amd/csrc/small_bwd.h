@@ -591,6 +591,18 @@ struct WDTap {
   }
 };
 
+// Both forms of K3: thread tid < 484 stores its pixel (hy, hx) of the frames'
+// 22 x 22 halo, loaded in the prologue (fp32 -> bf16 exact), pixel stride 4.
+// The caller computes (hy, hx) with the prologue's expression so that the two
+// stay one value; computed in here they are not merged and cost a multiply.
+__device__ __forceinline__ void bwd_halo_store(__bf16* halo, const float4& hv, int tid, int hy,
+                                               int hx) {
+  if (tid < 484) {
+    __bf16 q4[4] = {(__bf16)hv.x, (__bf16)hv.y, (__bf16)hv.z, (__bf16)hv.w};
+    *reinterpret_cast<uint2*>(halo + hy * X1_IROW + 4 * hx) = *reinterpret_cast<uint2*>(q4);
+  }
+}
+
 template <int K3, int KD>
 __global__ __launch_bounds__(kThreads) void tower_bwd16_kernel(const BwdArgs a) {
   static_assert(K3 >= 3 && KD >= 3, "ring: tap t + 2 is stored from registers at tap t");
@@ -678,7 +690,6 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16_kernel(const BwdArgs a) 
   const int wn3 = wid & 3, wk3g = wid >> 2;
   const int r16 = lane & 15, kq = lane >> 4;
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, cor = {0.f, 0.f, 0.f, 0.f};
     const int win = r16 >> 2, y = 2 * (win >> 1) + ((r16 >> 1) & 1), x = 2 * (win & 1) + (r16 & 1);
     const int abase = y * P2_RS + x * P2_CS + 32 * wk3g + 8 * kq;
@@ -703,12 +714,7 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16_kernel(const BwdArgs a) 
       }
       if (t + 1 < 9) ops(t + 1, (t + 1) & 1);
       const int c = t & 1;
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][2], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][1], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][2], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][1], cor, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][0], acc, 0, 0, 0);
+      split_mfma(av[c], bv[c], acc, cor);
       __builtin_amdgcn_sched_barrier(0);
       if (t + 2 < 9) w3[(t + 2) % K3].store(ring3 + ((t + 2) % 3) * W3_SLOT, tid);
       __syncthreads();
@@ -775,12 +781,7 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16_kernel(const BwdArgs a) 
       if (t + KD < 25) wd[(t + KD) % KD].load(wt2, wpl, t + KD, tid);
       if (t + 1 < 25) ops(t + 1, (t + 1) & 1);
       const int c = t & 1;
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][2], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][1], bv[c][1], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], bv[c][2], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][1], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], bv[c][1], cor, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], bv[c][0], acc, 0, 0, 0);
+      split_mfma(av[c], bv[c], acc, cor);
       __builtin_amdgcn_sched_barrier(0);
       if (t + 2 < 25) wd[(t + 2) % KD].store(ring2 + ((t + 2) % 3) * WD_SLOT, tid);
       __syncthreads();
@@ -803,13 +804,7 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16_kernel(const BwdArgs a) 
     }
     __syncthreads();
     for (int f = tid; f < (3 * X1_PL) / 8; f += kThreads) reinterpret_cast<u32x4*>(X)[f] = u32x4{0u, 0u, 0u, 0u};
-    {   // the frames' halo (fp32 -> bf16 exact), pixel stride 4 bf16
-      if (tid < 484) {
-        const int hy = tid / 22, hx = tid - 22 * (tid / 22);
-        __bf16 q4[4] = {(__bf16)hv.x, (__bf16)hv.y, (__bf16)hv.z, (__bf16)hv.w};
-        *reinterpret_cast<uint2*>(halo + hy * X1_IROW + 4 * hx) = *reinterpret_cast<uint2*>(q4);
-      }
-    }
+    bwd_halo_store(halo, hv, tid, tid / 22, tid - 22 * (tid / 22));
     __syncthreads();
     if (wkg == 0) {
       // lane: dpool1 at rows 8g + 4h + i of m block wm (window-major pixels of
@@ -919,7 +914,8 @@ constexpr int WDHP_SLOT = 2 * WDH_SLOT;                                // a pair
 constexpr int BS_RED2 = B_RING2;                                      // (over the dead ring)
 static_assert(12 * DS_CS <= D2_RS && B_RING2 + 3 * WDHP_SLOT * 2 <= B_HALO, "K3 split LDS");
 
-// conv2 data-gradient half tap pairs (taps 2s, 2s + 1; 25 repeats 24)
+// conv2 data-gradient half tap pairs (taps 2s, 2s + 1; 25 repeats 24):
+// 2 x 3 planes x 16 ci x 64 co = 2 x 384 vectors
 struct WDHPair {
   u32x4 r[2];
   __device__ __forceinline__ void load(const __bf16* __restrict__ wk, int64_t plane, int s,
@@ -938,21 +934,6 @@ struct WDHPair {
 #pragma unroll
     for (int u = 0; u < 2; ++u)
       *reinterpret_cast<u32x4*>(slot + u * WDH_SLOT + p * WDH_PL + n * WDH_CW + 8 * c8) = r[u];
-  }
-};
-// conv2 data-gradient half taps: 3 planes x 16 ci x 64 co = 384 vectors
-struct WDHTap {
-  u32x4 r;
-  __device__ __forceinline__ void load(const __bf16* __restrict__ wk, int64_t plane, int tap,
-                                       int half, int tid) {
-    const int f = tid < 384 ? tid : 383;
-    const int p = f >> 7, q = f & 127, n = q >> 3, c8 = q & 7;
-    r = *reinterpret_cast<const u32x4*>(wk + p * plane + ((16 * half + n) * 25 + tap) * 64 + 8 * c8);
-  }
-  __device__ __forceinline__ void store(__bf16* slot, int tid) const {
-    if (tid >= 384) return;
-    const int p = tid >> 7, q = tid & 127, n = q >> 3, c8 = q & 7;
-    *reinterpret_cast<u32x4*>(slot + p * WDH_PL + n * WDH_CW + 8 * c8) = r;
   }
 };
 
@@ -1042,7 +1023,6 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16s_kernel(const BwdArgs a)
   const int wn3 = wid & 3, wk3g = wid >> 2;
   const int r16 = lane & 15, kq = lane >> 4;
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, cor = {0.f, 0.f, 0.f, 0.f};
     const int win = r16 >> 2, y = 2 * (win >> 1) + ((r16 >> 1) & 1), x = 2 * (win & 1) + (r16 & 1);
     const int abase = y * P2_RS + x * P2_CS + 32 * wk3g + 8 * kq;
@@ -1067,12 +1047,7 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16s_kernel(const BwdArgs a)
       }
       if (t + 1 < 9) ops(t + 1, (t + 1) & 1);
       const int c = t & 1;
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][2], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][1], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][2], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][1], bv[c][0], cor, 0, 0, 0);
-      cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][1], cor, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][0], bv[c][0], acc, 0, 0, 0);
+      split_mfma(av[c], bv[c], acc, cor);
       __builtin_amdgcn_sched_barrier(0);
       if (t + 2 < 9) w3[(t + 2) % K3].store(ring3 + ((t + 2) % 3) * W3_SLOT, tid);
       __syncthreads();
@@ -1114,7 +1089,6 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16s_kernel(const BwdArgs a)
   // ---- conv2 data gradient, channels [16 half, +16): 25 taps on 16x16x32;
   // waves (m block of 16 pixels, k step of 32 co) = 4 x 2 ----
   {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int mb = wid & 3, kk = wid >> 2;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, cor = {0.f, 0.f, 0.f, 0.f};
     const int m = 16 * mb + r16;
@@ -1146,12 +1120,7 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16s_kernel(const BwdArgs a)
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         if (2 * st + u >= 25) continue;
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][2], bv[c][u][0], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][1], bv[c][u][1], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][0], bv[c][u][2], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][1], bv[c][u][0], cor, 0, 0, 0);
-        cor = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][0], bv[c][u][1], cor, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[c][u][0], bv[c][u][0], acc, 0, 0, 0);
+        split_mfma(av[c][u], bv[c][u], acc, cor);
       }
       __builtin_amdgcn_sched_barrier(0);
       if (st + 2 < NS) wd[(st + 2) % KD].store(ring2 + ((st + 2) % 3) * WDHP_SLOT, tid);
@@ -1172,11 +1141,7 @@ __global__ __launch_bounds__(kThreads) void tower_bwd16s_kernel(const BwdArgs a)
     }
     __syncthreads();
     for (int f = tid; f < (3 * X1_PL) / 8; f += kThreads) reinterpret_cast<u32x4*>(X)[f] = u32x4{0u, 0u, 0u, 0u};
-    if (tid < 484) {   // the frames' halo (fp32 -> bf16 exact), pixel stride 4 bf16
-      const int hy = tid / 22, hx = tid - 22 * (tid / 22);
-      __bf16 q4[4] = {(__bf16)hv.x, (__bf16)hv.y, (__bf16)hv.z, (__bf16)hv.w};
-      *reinterpret_cast<uint2*>(halo + hy * X1_IROW + 4 * hx) = *reinterpret_cast<uint2*>(q4);
-    }
+    bwd_halo_store(halo, hv, tid, tid / 22, tid - 22 * (tid / 22));
     __syncthreads();
     if (kk == 0) {
       // lane: dpool1 at pixels 16 mb + 4 kq + i (window 4 mb + kq of the 8 x 8

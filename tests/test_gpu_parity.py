@@ -200,6 +200,14 @@ FULL_PASS_CASES = [
     # with partial edge tiles, the bench's own state
     (24, 257, "snake", "x3"), (40, 320, "uniform", "x3"), (64, 288, "bench", "bench"),
 ]
+# either side of the small-map step's form switches: K1 splits at
+# 2 B nz <= 256 (B <= 64), K3 at 2 B <= 256 (B <= 128).  (A list of their own,
+# at the end: test_parity_harness numbers its seeded cases by position.)
+FORM_SWITCH_CASES = [
+    (16, 64, "snake", "x3"), (16, 65, "uniform", "x3"), (16, 128, "snake", "x3"),
+    (16, 129, "uniform", "x3"),
+]
+FULL_PASS_CASES += FORM_SWITCH_CASES
 
 
 @pytest.mark.parametrize("S,B,frames,init", FULL_PASS_CASES)
