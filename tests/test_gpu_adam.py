@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import _adam_ref as ar
+import _coherence as co
 import _nstep_ref as nr
 from _parity import close
 
@@ -98,7 +99,9 @@ def check_update(net, before, k, lr, what):
 def test_apply_parity(ddq, S):
     net = ddq.DeepQNet(batch=B, frame=S)
     theta = theta0(S)
+    theta_p = co.theta0(S, seed=43)
     net.set_flat(0, theta)
+    net.set_flat(1, theta_p)
     net.reset_optimizer()
     assert code_of(lambda: net.apply("adam", lr=1e-3)) == ESTATE
     net.set_adam()
@@ -114,22 +117,19 @@ def test_apply_parity(ddq, S):
         assert net.optimizer_state().tobytes() == net.adam_state()[0].tobytes()
         assert net.get_grads_flat().tobytes() == g.tobytes()
     assert code_of(lambda: net.blob("grad_norm")) == ESTATE
-    # the conv weights' split layouts were refreshed: the forward on this net is
-    # the forward of a fresh net given the same theta
-    x = rng.integers(0, 256, (B, 4, S, S)).astype(np.float32)
-    fresh = ddq.DeepQNet(batch=B, frame=S)
-    fresh.set_flat(0, net.get_flat(0))
-    out = []
-    for n in (net, fresh):
-        n.write_minibatch(state=x, next_state=x)
-        n.forward_q()
-        out.append(n.blob("Q_out"))
-    assert np.isfinite(out[0]).all() and out[0].tobytes() == out[1].tobytes()
+    # the conv weights' split layouts were refreshed, and P's (another
+    # initialisation, set before the applies) left alone: both towers' forward,
+    # the backward and the actions on this net are those of a fresh net given the
+    # same parameters, byte for byte (tests/_coherence.py)
+    assert net.get_flat(1).tobytes() == theta_p.tobytes()
+    mb, states = co.probe_inputs(B, S)
+    got, want = co.probe(ddq, net, mb, states)
+    co.assert_coherent(got, want, "S%d after four Adam applies" % S)
     # reset: m, v, t back to zero
     net.reset_optimizer()
     m, v, t = net.adam_state()
     assert t == 0 and not m.any() and not v.any()
-    done(net, fresh)
+    done(net)
 
 
 @pytest.mark.parametrize("S", [16, 32])
