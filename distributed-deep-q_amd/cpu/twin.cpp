@@ -81,6 +81,7 @@ struct ddq_ctx {
   std::vector<float> theta[2], grad, opt;
   int first = 1;                 // the next apply is the first since a reset
   int64_t iter = 0;
+  float target_tau = 1.f;        // ddq_set_target_tau (ddq_soft_sync_target blends with it)
   // Adam (ddq_set_adam): opt holds m, opt2 v; gnorm: the last pre-clip norm
   bool adam_on = false;
   ddq_adam_cfg adam{0.f, 0.f, 0.f, 0.f};
@@ -773,6 +774,38 @@ int ddq_set_grads(ddq_ctx* c, const float* src, int64_t n, int32_t on_dev) {
 int ddq_sync_target(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   c->theta[1] = c->theta[0];
+  return DDQ_OK;
+}
+
+// ---- soft target updates ----
+int ddq_set_target_tau(ddq_ctx* c, float tau) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!(tau > 0.f && tau <= 1.f))
+    return fail(c, DDQ_EINVAL, "target tau must be in (0, 1] (got %g)", (double)tau);
+  c->target_tau = tau;
+  return DDQ_OK;
+}
+
+int ddq_get_target_tau(const ddq_ctx* c, float* tau) {
+  if (!c || !tau) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *tau = c->target_tau;
+  return DDQ_OK;
+}
+
+// P' = P + tau (Q - P): the device's target_blend, three fp32 operations each
+// rounded on its own (this file is built with -ffp-contract=off, as the
+// update rules need)
+int ddq_soft_sync_target(ddq_ctx* c) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->target_tau >= 1.f) return ddq_sync_target(c);
+  const float tau = c->target_tau;
+  const float* q = c->theta[0].data();
+  float* p = c->theta[1].data();
+  for (int64_t i = 0; i < c->L.total; ++i) {
+    const float d = q[i] - p[i];
+    const float s = tau * d;
+    p[i] = p[i] + s;
+  }
   return DDQ_OK;
 }
 

@@ -99,6 +99,8 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(ApplyTail t, ApplyArgs 
       v4 = *reinterpret_cast<const float4*>(ad.v + i);
     }
   }
+  // (soft sync: the old P, with the four streams)
+  const float4 p4 = refresh_old_p(a, live && sync, i, t.thetaP);
   if (threadIdx.x == 0) {
     const double tt = (double)*ad.iter;
     s_k[0] = (float)(1.0 - pow((double)ad.beta1, tt));
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(ApplyTail t, ApplyArgs 
   wt_store4(wt_rsrc(t.opt, nb), ib, make_float4(m[0], m[1], m[2], m[3]));
   wt_store4(wt_rsrc(ad.v, nb), ib, make_float4(v[0], v[1], v[2], v[3]));
   // the P copy on a sync step, and the conv layouts of Q (and of P then)
-  refresh_elems(a, sync, i, th, t.thetaP, t.wks, t.wksP, t.wks_plane);
+  refresh_elems(a, sync, i, th, p4, t.thetaP, t.wks, t.wksP, t.wks_plane);
 }
 
 hipError_t launch_grad_norm(const NetBuffers& nb, hipStream_t s) {

@@ -621,6 +621,37 @@ int ddq_sync_target(ddq_ctx* c) {
   return DDQ_OK;
 }
 
+// ---------------- soft target updates ----------------
+int ddq_set_target_tau(ddq_ctx* c, float tau) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!(tau > 0.f && tau <= 1.f))
+    return fail(c, DDQ_EINVAL, "target tau must be in (0, 1] (got %g)", (double)tau);
+  if (c->async_on && tau < 1.f)
+    return fail(c, DDQ_EINVAL, "soft target updates (tau %g < 1) with the async exchange: its P "
+                               "travels by pulls, not by the steps' syncs", (double)tau);
+  invalidate_graph(c);   // captured steps hold tau as a launch argument
+  c->nb.target_tau = tau;
+  return DDQ_OK;
+}
+
+int ddq_get_target_tau(const ddq_ctx* c, float* tau) {
+  if (!c || !tau) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *tau = c->nb.target_tau;
+  return DDQ_OK;
+}
+
+// One launch: the refresh with its sync forced blends every parameter of P
+// towards Q (target_blend) and rewrites the conv weights' split copies from
+// the blended values.
+int ddq_soft_sync_target(ddq_ctx* c) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->nb.target_tau >= 1.f) return ddq_sync_target(c);
+  TRY(set_dev(c));
+  HIP_TRY(c, launch_refresh(c->nb, c->stream, 1));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return DDQ_OK;
+}
+
 // ---------------- prioritized replay: tree set-up ----------------
 static void prio_release(ddq_ctx* c) {
   PrioTree& t = c->nb.prio;
@@ -2199,6 +2230,10 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
     return fail(c, DDQ_EINVAL, "DDQ_RULE_ADAM runs without an exchange or under "
                                "DDQ_EXCHANGE_ALLREDUCE only (exchange %d shards one state buffer)",
                 cfg->exchange);
+  if (c->nb.target_tau < 1.f && is_async(c, cfg))
+    return fail(c, DDQ_EINVAL, "soft target updates (tau %g < 1) with DDQ_EXCHANGE_ASYNC: its P "
+                               "travels by pulls, not by the steps' syncs",
+                (double)c->nb.target_tau);
   return DDQ_OK;
 }
 
@@ -2426,6 +2461,10 @@ int ddq_async_begin(ddq_ctx* c, const ddq_step_cfg* cfg) {
   if (cfg->exchange != DDQ_EXCHANGE_ASYNC) return fail(c, DDQ_EINVAL, "cfg exchange is not async");
   if (cfg->update.rule == DDQ_RULE_ADAM)
     return fail(c, DDQ_EINVAL, "the async exchange does not take DDQ_RULE_ADAM");
+  if (c->nb.target_tau < 1.f)
+    return fail(c, DDQ_EINVAL, "soft target updates (tau %g < 1) with DDQ_EXCHANGE_ASYNC: its P "
+                               "travels by pulls, not by the steps' syncs",
+                (double)c->nb.target_tau);
   if (c->mon.ring && c->mon_period > 0)
     return fail(c, DDQ_ESTATE, "the async exchange takes no monitor records: disable the monitor or "
                                "enable it with period 0");

@@ -191,6 +191,9 @@ struct NetBuffers {
   double* gn_part = nullptr;
   float* gnorm = nullptr;
   float adam_beta1 = 0.f, adam_beta2 = 0.f, adam_eps = 0.f, adam_clip = 0.f;
+  // soft target updates (ddq_set_target_tau): < 1, every due P <- Q sync of a
+  // step writes P + tau (Q - P) instead (ApplyArgs::tau, target_blend)
+  float target_tau = 1.f;
   // deepq16 step (small.h, small_bwd.h): fc4 chain partials and its fan-in words
   int small;                        // S == 16, B <= 256: the four-launch step
   int small_G = 1;                  // its fc4 chain's image chunks (B > 32: ceil(B / 32))

@@ -1061,6 +1061,7 @@ struct ApplyArgs {
   int64_t lo, hi, skip_lo, skip_len;   // elements [lo, hi) minus [skip_lo, skip_lo + skip_len)
   int rule, period;
   float lr, decay, one_minus_decay, eps, momentum, wd;
+  float tau;                           // < 1: a due target sync blends (target_blend) instead of copying
   int64_t bias_lo[5], bias_hi[5];   // [lo,hi) element ranges of biases (momentum multipliers)
   ConvDims conv[3];
 };
@@ -1108,6 +1109,18 @@ __device__ __forceinline__ float apply_rule(const ApplyArgs& a, bool first, bool
   }
 }
 
+// Soft target update (ddq_set_target_tau): what a due sync writes to P when
+// tau < 1, P' = P + tau (Q' - P) with Q' the value the site just computed for
+// theta_Q.  Three fp32 operations, each rounded on its own (no FMA
+// contraction): every update site and the CPU twin produce the same bits.
+// tau = 1 never comes here: the sites copy Q' as before.
+__device__ __forceinline__ float target_blend(float p, float q, float tau) {
+#pragma clang fp contract(off)
+  const float d = q - p;
+  const float s = tau * d;
+  return p + s;
+}
+
 // Update operands of the apply (the apply launch, or the fused fc4-weight
 // apply blocks of the slab-reduce launch).
 struct ApplyTail {
@@ -1129,14 +1142,14 @@ struct ApplyTail {
 };
 
 __device__ __forceinline__ void apply_at(const ApplyTail& t, const ApplyArgs& a, bool first,
-                                         bool sync, int64_t i, float g, float th, float st,
-                                         bool is_bias, bool conv = false,
+                                         bool sync, bool soft, int64_t i, float g, float th,
+                                         float st, float po, bool is_bias, bool conv = false,
                                          const ConvDims& cd = ConvDims{}, int e = 0);
 __device__ __forceinline__ void head_sums(int hb, int B, const float* __restrict__ dqbuf,
                           const float* __restrict__ lpart, const float* __restrict__ h4q,
                           const float* __restrict__ dh4, float* loss_o, float* __restrict__ gw5,
                           float* __restrict__ gb5, float* __restrict__ gb4,
-                          bool ap, const ApplyTail& at, const ApplyArgs& aa) {
+                          bool ap, bool soft_on, const ApplyTail& at, const ApplyArgs& aa) {
   __shared__ float red[4 * 64 * 5];
   const int t = threadIdx.x, lane = t & 63, g = t >> 6;
   // fused steps: these sums are final here, so their elements are updated
@@ -1145,19 +1158,25 @@ __device__ __forceinline__ void head_sums(int hb, int B, const float* __restrict
   const bool first = ap && at.opt_init[2] != 0, sync = ap && at.opt_init[3] != 0;
   float th5[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, st5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   float thb5 = 0.f, stb5 = 0.f;
+  // (soft sync: the old P values too, with the same loads)
+  const bool soft = soft_on && sync && aa.tau < 1.f;
+  float po5[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, pob5 = 0.f;
   if (ap && g == 0) {
     const int jj = hb * 64 + lane;
     th5[0] = at.theta[b4_off + jj];
     if (aa.rule != 0 && !first) st5[0] = at.opt[b4_off + jj];
+    if (soft) po5[0] = at.thetaP[b4_off + jj];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       th5[1 + a] = at.theta[w5_off + a * kFc4 + jj];
       if (aa.rule != 0 && !first) st5[1 + a] = at.opt[w5_off + a * kFc4 + jj];
+      if (soft) po5[1 + a] = at.thetaP[w5_off + a * kFc4 + jj];
     }
   }
   if (ap && hb == 0 && t < 4) {
     thb5 = at.theta[b5_off + t];
     if (aa.rule != 0 && !first) stb5 = at.opt[b5_off + t];
+    if (soft) pob5 = at.thetaP[b5_off + t];
   }
   if (hb == 0 && t < 5) {
     // sequential sums over b, loads issued 16 at a time (clamped indices,
@@ -1176,7 +1195,7 @@ __device__ __forceinline__ void head_sums(int hb, int B, const float* __restrict
     }
     if (t < 4) {
       gb5[t] = acc;
-      if (ap) apply_at(at, aa, first, sync, b5_off + t, acc, thb5, stb5, true);
+      if (ap) apply_at(at, aa, first, sync, soft, b5_off + t, acc, thb5, stb5, pob5, true);
     } else {
       *loss_o = acc / (float)B / 2.f;
     }
@@ -1222,11 +1241,11 @@ __device__ __forceinline__ void head_sums(int hb, int B, const float* __restrict
 #pragma unroll
     for (int a = 0; a < 4; ++a) gw5[a * kFc4 + j] = s[1 + a];
     if (ap) {
-      apply_at(at, aa, first, sync, b4_off + j, s[0], th5[0], st5[0], true);
+      apply_at(at, aa, first, sync, soft, b4_off + j, s[0], th5[0], st5[0], po5[0], true);
 #pragma unroll
       for (int a = 0; a < 4; ++a)
-        apply_at(at, aa, first, sync, w5_off + a * kFc4 + j, s[1 + a], th5[1 + a], st5[1 + a],
-                 false);
+        apply_at(at, aa, first, sync, soft, w5_off + a * kFc4 + j, s[1 + a], th5[1 + a], st5[1 + a],
+                 po5[1 + a], false);
     }
   }
 }
@@ -1335,18 +1354,28 @@ __device__ __forceinline__ void apply_elems(const ApplyTail& t, const ApplyArgs&
   const float4 t4 = *reinterpret_cast<const float4*>(t.theta + i);
   float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (a.rule != 0 && !first) s4 = *reinterpret_cast<const float4*>(t.opt + i);
+  const bool soft = sync && a.tau < 1.f;   // (the old P: loaded on a soft sync only)
+  float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (soft) p4 = *reinterpret_cast<const float4*>(t.thetaP + i);
   float th[4] = {t4.x, t4.y, t4.z, t4.w};
   const float g[4] = {g4.x, g4.y, g4.z, g4.w};
   float st[4] = {s4.x, s4.y, s4.z, s4.w};
 #pragma unroll
   for (int e = 0; e < 4; ++e) th[e] = apply_one(a, first, i + e, th[e], g[e], st[e]);
   const float4 o4 = make_float4(th[0], th[1], th[2], th[3]);
+  // what a due sync gives P: the copy, or the blend
+  float tp[4] = {th[0], th[1], th[2], th[3]};
+  if (soft) {
+    const float po[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tp[e] = target_blend(po[e], th[e], a.tau);
+  }
   // write-through (split.h wt_store4): no dirty theta / state lines for the
   // launch's end to write back
   const uint32_t nb = (uint32_t)(((a.n + 3) & ~3ll) * 4), ib = (uint32_t)(i * 4);
   wt_store4(wt_rsrc(t.theta, nb), ib, o4);
   if (a.rule != 0) wt_store4(wt_rsrc(t.opt, nb), ib, make_float4(st[0], st[1], st[2], st[3]));
-  if (sync) wt_store4(wt_rsrc(t.thetaP, nb), ib, o4);
+  if (sync) wt_store4(wt_rsrc(t.thetaP, nb), ib, make_float4(tp[0], tp[1], tp[2], tp[3]));
 #pragma unroll
   for (int l = 0; l < 3; ++l) {
     const ConvDims& d = a.conv[l];
@@ -1355,7 +1384,7 @@ __device__ __forceinline__ void apply_elems(const ApplyTail& t, const ApplyArgs&
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         put_conv_weight(d, (int)e0 + e, th[e], t.wks, t.wks_plane);
-        if (sync) put_conv_weight(d, (int)e0 + e, th[e], t.wksP, t.wks_plane);
+        if (sync) put_conv_weight(d, (int)e0 + e, tp[e], t.wksP, t.wks_plane);
       }
     }
   }
@@ -1367,15 +1396,18 @@ __device__ __forceinline__ void apply_elems(const ApplyTail& t, const ApplyArgs&
 // the element is a bias and which layer it is in, so no range tests here
 // (they kept ~20 more scalars live across the reduce and spilled them).
 __device__ __forceinline__ void apply_at(const ApplyTail& t, const ApplyArgs& a, bool first,
-                                         bool sync, int64_t i, float g, float th, float st,
-                                         bool is_bias, bool conv, const ConvDims& cd, int e) {
+                                         bool sync, bool soft, int64_t i, float g, float th,
+                                         float st, float po, bool is_bias, bool conv,
+                                         const ConvDims& cd, int e) {
   th = apply_rule(a, first, is_bias, th, g, st);
   t.theta[i] = th;
   if (a.rule != 0) t.opt[i] = st;
-  if (sync) t.thetaP[i] = th;
+  // po: the old P (loaded by the caller with theta, on a soft sync only)
+  const float tp = soft ? target_blend(po, th, a.tau) : th;
+  if (sync) t.thetaP[i] = tp;
   if (conv) {
     put_conv_weight(cd, e, th, t.wks, t.wks_plane);
-    if (sync) put_conv_weight(cd, e, th, t.wksP, t.wks_plane);
+    if (sync) put_conv_weight(cd, e, tp, t.wksP, t.wks_plane);
   }
 }
 
@@ -1430,7 +1462,8 @@ __device__ __forceinline__ void fc4_wgrad_sum(int B, int K, const float* __restr
 // sync step).
 constexpr int kFc4ApplyR = 4;   // 2 / 8 rows per wave measured 18.9 / 25.0 us against 13.4
 __device__ __forceinline__ void fc4_apply_tile(const ApplyTail& t, const ApplyArgs& a, int B,
-                                               int K, const float* dh4, const float* x, int blk) {
+                                               int K, const float* dh4, const float* x, int blk,
+                                               bool soft_on) {
   constexpr int R = kFc4ApplyR;
   int o0, k;
   if (!fc4_wgrad_coords<R>(K, blk, o0, k)) return;
@@ -1442,12 +1475,15 @@ __device__ __forceinline__ void fc4_apply_tile(const ApplyTail& t, const ApplyAr
   const uint32_t nb = (uint32_t)(a.n * 4);
   const __amdgpu_buffer_rsrc_t rg = wt_rsrc(t.grad, nb), rt = wt_rsrc(t.theta, nb);
   const __amdgpu_buffer_rsrc_t ro = wt_rsrc(t.opt, nb), rp = wt_rsrc(t.thetaP, nb);
-  float4 t4[R], s4[R];
+  const bool soft = soft_on && sync && a.tau < 1.f;   // (the old P: loaded on a soft sync only)
+  float4 t4[R], s4[R], p4[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     t4[r] = *reinterpret_cast<const float4*>(t.theta + i0 + (int64_t)r * K);
     s4[r] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.rule != 0 && !first) s4[r] = *reinterpret_cast<const float4*>(t.opt + i0 + (int64_t)r * K);
+    p4[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (soft) p4[r] = *reinterpret_cast<const float4*>(t.thetaP + i0 + (int64_t)r * K);
   }
   float g[R][4];
   if (t.ext) {   // summed over the ranks already (all-reduce under the conv backward)
@@ -1471,7 +1507,14 @@ __device__ __forceinline__ void fc4_apply_tile(const ApplyTail& t, const ApplyAr
     const float4 o4 = make_float4(th[0], th[1], th[2], th[3]);
     wt_store4(rt, ib, o4);
     if (a.rule != 0) wt_store4(ro, ib, make_float4(st[0], st[1], st[2], st[3]));
-    if (sync) wt_store4(rp, ib, o4);
+    if (soft) {
+      wt_store4(rp, ib, make_float4(target_blend(p4[r].x, th[0], a.tau),
+                                    target_blend(p4[r].y, th[1], a.tau),
+                                    target_blend(p4[r].z, th[2], a.tau),
+                                    target_blend(p4[r].w, th[3], a.tau)));
+    } else if (sync) {
+      wt_store4(rp, ib, o4);
+    }
   }
 }
 
@@ -1522,7 +1565,7 @@ __device__ __forceinline__ int64_t wred_index(const WredDims& d, int lu, int col
 template <int G>
 __device__ __forceinline__ void wred_block(const float* __restrict__ part, float* __restrict__ grad,
                                            const WredDims& d, int lb, float (*red)[4][64],
-                                           bool rest, const ApplyTail& fat,
+                                           bool rest, bool soft_on, const ApplyTail& fat,
                                            const ApplyArgs& faa) {
   constexpr int NA = 4 / G;   // group accumulators per wave
   // w is per wave: readfirstlane keeps the unit arithmetic scalar
@@ -1535,10 +1578,12 @@ __device__ __forceinline__ void wred_block(const float* __restrict__ part, float
   // fused steps: the unit's element is updated here once its gradient is
   // final; theta / state are loaded before the slab loads
   const bool first = rest && fat.opt_init[2] != 0, sync = rest && fat.opt_init[3] != 0;
-  float th = 0.f, st = 0.f;
+  const bool soft = soft_on && sync && faa.tau < 1.f;
+  float th = 0.f, st = 0.f, po = 0.f;
   if (rest && h == 0 && live) {
     th = fat.theta[idx];
     if (faa.rule != 0 && !first) st = fat.opt[idx];
+    if (soft) po = fat.thetaP[idx];   // (soft sync: the old P)
   }
   float acc[NA];
 #pragma unroll
@@ -1572,7 +1617,7 @@ __device__ __forceinline__ void wred_block(const float* __restrict__ part, float
     if (rest) {
       const ConvDims cd{d.w_off, d.wks_off, d.cout, d.cin, d.ks};
       const bool wt = n < kc;
-      apply_at(fat, faa, first, sync, idx, v, th, st, !wt, wt, cd, (int)(idx - d.w_off));
+      apply_at(fat, faa, first, sync, soft, idx, v, th, st, po, !wt, wt, cd, (int)(idx - d.w_off));
     }
   }
 }
@@ -1582,7 +1627,9 @@ __device__ __forceinline__ void wred_block(const float* __restrict__ part, float
 // block 0 also latches the apply bookkeeping.  Fused steps (fat.rest) update
 // every parameter here, where its gradient becomes final -- no separate apply
 // launch.
-template <bool NS>
+// SOFT: a due target sync blends (ddq_set_target_tau < 1); without it the soft
+// form is compiled out and the default launch keeps its instruction stream.
+template <bool NS, bool SOFT = false>
 __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
     const float* __restrict__ part, float* __restrict__ grad, WredDims d0, WredDims d1,
     WredDims d2, int nub, int64_t* iter, int32_t* opt_init, int book_period,
@@ -1605,12 +1652,12 @@ __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
     if (opt_init && bid == 0 && threadIdx.x == 0)
       apply_book(iter, opt_init, book_period, bump, book_step);
     head_sums(bid, hs.B, hs.dqbuf, hs.lpart, hs.h4q, hs.dh4, hs.loss, hs.gw5, hs.gb5, hs.gb4,
-              rest, fat, faa);
+              rest, SOFT, fat, faa);
     return;
   }
   bid -= kFc4 / 64;
   if (bid < fat.nfa) {
-    fc4_apply_tile(fat, faa, hs.B, fc4_k, hs.dh4, fc4_x, bid);
+    fc4_apply_tile(fat, faa, hs.B, fc4_k, hs.dh4, fc4_x, bid, SOFT);
     return;
   }
   bid -= fat.nfa;
@@ -1618,11 +1665,11 @@ __global__ __launch_bounds__(256, 4) void wgrad_reduce_kernel(
   // three in scratch memory)
   const WredDims d = bid >= d1.blk0 ? d1 : (bid >= d2.blk0 ? d2 : d0);
   if (d.G == 1)
-    wred_block<1>(part, grad, d, bid - d.blk0, red, rest, fat, faa);
+    wred_block<1>(part, grad, d, bid - d.blk0, red, rest, SOFT, fat, faa);
   else if (d.G == 2)
-    wred_block<2>(part, grad, d, bid - d.blk0, red, rest, fat, faa);
+    wred_block<2>(part, grad, d, bid - d.blk0, red, rest, SOFT, fat, faa);
   else
-    wred_block<4>(part, grad, d, bid - d.blk0, red, rest, fat, faa);
+    wred_block<4>(part, grad, d, bid - d.blk0, red, rest, SOFT, fat, faa);
 }
 
 // Blocks [0, pf.ng) of the apply launch draw + gather the NEXT step's
@@ -1662,14 +1709,27 @@ __global__ void apply_book_kernel(int64_t* iter, int32_t* opt_init, int period) 
 // Blocks [0, pf.ng): the next step's draw + gather (pipelined sharded /
 // server steps: the step's bookkeeping in the slab reduce advanced the draw
 // counter already).
-// launch_refresh's per-float4 work: the P copy on a sync step and, for conv
-// weights, the kernel layouts of Q (and P on a sync step)
+// launch_refresh's per-float4 work: the P copy (tau < 1: the blend) on a sync
+// step and, for conv weights, the kernel layouts of Q (and P on a sync step)
+// p4: the old P, loaded by the caller with its other operands (refresh_old_p)
+__device__ __forceinline__ float4 refresh_old_p(const ApplyArgs& a, bool sync, int64_t i,
+                                                const float* thetaP) {
+  if (sync && a.tau < 1.f) return *reinterpret_cast<const float4*>(thetaP + i);
+  return make_float4(0.f, 0.f, 0.f, 0.f);
+}
 __device__ __forceinline__ void refresh_elems(const ApplyArgs& a, bool sync, int64_t i,
-                                              const float (&th)[4], float* __restrict__ thetaP,
-                                              __bf16* wks, __bf16* wksP, int64_t wks_plane) {
+                                              const float (&th)[4], const float4 p4,
+                                              float* thetaP, __bf16* wks, __bf16* wksP,
+                                              int64_t wks_plane) {
+  float tp[4] = {th[0], th[1], th[2], th[3]};
+  if (sync && a.tau < 1.f) {
+    const float po[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tp[e] = target_blend(po[e], th[e], a.tau);
+  }
   if (sync)
     wt_store4(wt_rsrc(thetaP, (uint32_t)(((a.n + 3) & ~3ll) * 4)), (uint32_t)(i * 4),
-              make_float4(th[0], th[1], th[2], th[3]));
+              make_float4(tp[0], tp[1], tp[2], tp[3]));
 #pragma unroll
   for (int l = 0; l < 3; ++l) {
     const ConvDims& d = a.conv[l];
@@ -1678,7 +1738,7 @@ __device__ __forceinline__ void refresh_elems(const ApplyArgs& a, bool sync, int
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         put_conv_weight(d, (int)e0 + e, th[e], wks, wks_plane);
-        if (sync) put_conv_weight(d, (int)e0 + e, th[e], wksP, wks_plane);
+        if (sync) put_conv_weight(d, (int)e0 + e, tp[e], wksP, wks_plane);
       }
     }
   }
@@ -1714,6 +1774,8 @@ __global__ __launch_bounds__(256) void apply_shard_kernel(
   const float4 t4 = *reinterpret_cast<const float4*>(theta + i);
   float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (a.rule != 0 && !first) s4 = *reinterpret_cast<const float4*>(opt + i);
+  const bool rsync = ro.mode == 1 ? opt_init[3] != 0 : ro.mode == 3;
+  const float4 p4 = refresh_old_p(a, ro.mode != 0 && rsync, i, ro.thetaP);
   float th[4] = {t4.x, t4.y, t4.z, t4.w};
   float st[4] = {s4.x, s4.y, s4.z, s4.w};
   for (int w = 0; w < W; ++w) {
@@ -1731,9 +1793,7 @@ __global__ __launch_bounds__(256) void apply_shard_kernel(
   // (async owner applying its own worker's push: the worker's copy of the
   // shard too, instead of a pull copy after the apply)
   if (mirror) wt_store4(wt_rsrc(mirror, nb), ib, make_float4(th[0], th[1], th[2], th[3]));
-  if (ro.mode)
-    refresh_elems(a, ro.mode == 1 ? opt_init[3] != 0 : ro.mode == 3, i, th, ro.thetaP, ro.wks,
-                  ro.wksP, ro.wks_plane);
+  if (ro.mode) refresh_elems(a, rsync, i, th, p4, ro.thetaP, ro.wks, ro.wksP, ro.wks_plane);
 }
 
 // After the theta all-gather: conv kernel layouts of Q, and P <- Q (weights
@@ -1751,8 +1811,9 @@ __global__ __launch_bounds__(256) void refresh_kernel(const float* __restrict__ 
       (!sync && i >= a.conv[2].w_off + (int64_t)a.conv[2].cout * a.conv[2].cin * 9))
     return;
   const float4 o4 = *reinterpret_cast<const float4*>(theta + i);
+  const float4 p4 = refresh_old_p(a, sync, i, thetaP);
   const float th[4] = {o4.x, o4.y, o4.z, o4.w};
-  refresh_elems(a, sync, i, th, thetaP, wks, wksP, wks_plane);
+  refresh_elems(a, sync, i, th, p4, thetaP, wks, wksP, wks_plane);
 }
 
 // out[0..len) = sum_w in[w][0..len) in rank order (in-process group exchange)
@@ -1770,7 +1831,7 @@ static ApplyArgs apply_args(const NetBuffers& nb, const UpdateRule& u) {
   ApplyArgs a;
   a.n = nb.L.total;
   a.lo = 0; a.hi = a.n; a.skip_lo = a.n; a.skip_len = 0;
-  a.rule = u.rule; a.period = u.period;
+  a.rule = u.rule; a.period = u.period; a.tau = nb.target_tau;
   a.lr = u.lr; a.decay = u.decay; a.eps = u.eps; a.momentum = u.momentum; a.wd = u.wd;
   a.one_minus_decay = (float)(1.0 - (double)u.decay);   // numpy: (1 - rmsprop_decay) in double
   for (int l = 0; l < 5; ++l) { a.bias_lo[l] = nb.L.b[l]; a.bias_hi[l] = nb.L.b[l] + nb.L.bn[l]; }
@@ -2198,10 +2259,16 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hip
   // B <= 32: one tower a workgroup (kFcBlk of the P tower, then kFcBlk of
   // Q); B > 32: both towers a workgroup, kFcBlk G (all resident)
   const bool one = c.G == 1, obj = c.obj_target || c.obj_loss || c.weighted;
+  // (soft: the build whose due sync blends; the default launch is the build without it)
+  const bool soft = c.apply && c.aa.tau < 1.f;
   auto kern = obj ? (one ? sm16::fc4_chain16_obj_kernel<1> : sm16::fc4_chain16_obj_kernel<2>)
                   : (one ? sm16::fc4_chain16_kernel<1> : sm16::fc4_chain16_kernel<2>);
-  static std::atomic<uint64_t> attr[4] = {{0}, {0}, {0}, {0}};
-  CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr[(obj ? 2 : 0) + (one ? 0 : 1)],
+  if (soft)
+    kern = obj ? (one ? sm16::fc4_chain16_obj_kernel<1, true> : sm16::fc4_chain16_obj_kernel<2, true>)
+               : (one ? sm16::fc4_chain16_kernel<1, true> : sm16::fc4_chain16_kernel<2, true>);
+  static std::atomic<uint64_t> attr[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+  CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern),
+                              attr[(soft ? 4 : 0) + (obj ? 2 : 0) + (one ? 0 : 1)],
                               sm16::kChainSmem));
   M("fc4_chain");
   ddq_launch(kern, dim3((one ? 2 : 1) * sm16::kFcBlk * c.G - (sl.plan.k2_short ? 1 : 0)), dim3(512),
@@ -2257,6 +2324,16 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
       // K4: a tile's groups meet when it has more than one
       {"wgrad16", reinterpret_cast<const void*>(sm16::wgrad16_kernel<false>), 256, wgrad16_lds(),
        (G3 > 1 ? sm16::kT3 * G3 : 0) + (G2 > 1 ? sm16::kT2 * G2 : 0)},
+      // K2 and K4 built with the soft target update (ddq_set_target_tau < 1)
+      {"fc4_chain16_soft", G == 1 ? reinterpret_cast<const void*>(sm16::fc4_chain16_kernel<1, true>)
+                                  : reinterpret_cast<const void*>(sm16::fc4_chain16_kernel<2, true>),
+       512, sm16::kChainSmem, (G == 1 ? 2 : 1) * sm16::kFcBlk * G},
+      {"fc4_chain16_obj_soft",
+       G == 1 ? reinterpret_cast<const void*>(sm16::fc4_chain16_obj_kernel<1, true>)
+              : reinterpret_cast<const void*>(sm16::fc4_chain16_obj_kernel<2, true>),
+       512, sm16::kChainSmem, (G == 1 ? 2 : 1) * sm16::kFcBlk * G},
+      {"wgrad16_soft", reinterpret_cast<const void*>(sm16::wgrad16_kernel<false, true>), 256,
+       wgrad16_lds(), (G3 > 1 ? sm16::kT3 * G3 : 0) + (G2 > 1 ? sm16::kT2 * G2 : 0)},
   };
   for (const Launch& l : ls) {
     if (l.meeting == 0) continue;
@@ -2343,11 +2420,14 @@ hipError_t launch_small_bwd(const NetBuffers& nb, const StepLaunch& sl, hipStrea
     const int r3 = (w.ipg3 + sm16::Wg3::NI - 1) / sm16::Wg3::NI;
     (void)r2; (void)r3;   // (two buffers always: the staging's dummy slot follows them)
     const int lds = wgrad16_lds();
-    static std::atomic<uint64_t> attr{0}, attr_ns{0};
+    static std::atomic<uint64_t> attr[4] = {{0}, {0}, {0}, {0}};
     const bool ns = nb.nstep > 1;
+    // (soft: the build whose due sync blends; the default launch is the build without it)
+    const bool soft = w.apply && w.aa.tau < 1.f;
     auto kern = ns ? sm16::wgrad16_kernel<true> : sm16::wgrad16_kernel<false>;
-    CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), ns ? attr_ns : attr,
-                                sm16::kWgSmem));
+    if (soft) kern = ns ? sm16::wgrad16_kernel<true, true> : sm16::wgrad16_kernel<false, true>;
+    CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern),
+                                attr[(soft ? 2 : 0) + (ns ? 1 : 0)], sm16::kWgSmem));
     M("wgrad_apply");
     ddq_launch(kern,
                dim3(sm16::kT3 * w.G3 + sm16::kT2 * w.G2 + sm16::kW1Blocks + w.pf.ng + w.nw4 +
@@ -2473,6 +2553,9 @@ hipError_t launch_backward(const NetBuffers& nb, const StepLaunch& sl, hipStream
     Prefetch pf{};
     CHECK_LAUNCH(gather_blocks(sl, Site::SlabReduce, &pf));   // (launch_head drew it: head_draw)
     auto kern = nb.nstep > 1 ? wgrad_reduce_kernel<true> : wgrad_reduce_kernel<false>;
+    // (the build whose due sync blends; the default launch is the build without it)
+    if (p.fused() && faa.tau < 1.f)
+      kern = nb.nstep > 1 ? wgrad_reduce_kernel<true, true> : wgrad_reduce_kernel<false, true>;
     ddq_launch(kern, dim3(pf.ng + nub + kFc4 / 64 + nfa), dim3(256), 0, s,
                        nb.wpart, nb.grad, d[0], d[1], d[2], nub, nb.iter,
                        book ? nb.opt_init : nullptr, p.book_period,

@@ -48,7 +48,8 @@ constexpr int CH_DQ = CH_QP + 2 * kMaxB * 4;
 constexpr int CH_TMP = CH_DQ + kMaxB * 4;          // squared errors [kMaxB]
 constexpr int CH_W5 = CH_TMP + kMaxB;             // Q's Q_out columns of the units [4][16]
 constexpr int CH_PS = CH_W5 + 64;                 // theta / state of the 84 unit-sum params
-constexpr int CH_MB = CH_PS + 2 * 96;             // the minibatch's action (4), reward, nonterm
+                                                  // (and their old P on a soft sync)
+constexpr int CH_MB = CH_PS + 3 * 96;             // the minibatch's action (4), reward, nonterm
 constexpr int kChainSmemF = CH_MB + 6 * kMaxB;
 constexpr int kChainSmem = kChainSmemF * 4;
 static_assert(kChainSmem <= 160 * 1024, "K2 LDS");
@@ -110,7 +111,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 // 159 KB of LDS only if each carries both towers)
 // OBJ: the selectable objective's branches are compiled in (fc4_chain16_obj_kernel);
 // without it the head loop is the reference objective's code and nothing else
-template <int NZ, bool OBJ>
+// SOFT: a due target sync blends (ddq_set_target_tau < 1); without it the soft
+// form is compiled out and the default launch keeps its instruction stream
+template <int NZ, bool OBJ, bool SOFT>
 __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -178,17 +181,19 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
     return q < 80 ? ((q >> 4) == 0 ? c.b4_off + n0 + (q & 15) : c.w5_off + ((q >> 4) - 1) * 512 + n0 + (q & 15))
                   : c.b5_off + (q - 80);
   };
-  float pth = 0.f, pst = 0.f;
+  float pth = 0.f, pst = 0.f, ppo = 0.f;
   const bool ap0 = c.apply != 0 && G == 1 && !ptower;   // (G > 1: K4 applies the batch sums)
   // K1 failed its meeting: no update from this step (the word is read now,
   // used after the fan-in)
   const bool pois = ap0 && step_poisoned(c.sync + 48, nullptr);
   // the update's flags (latched by K1's book block), loaded now
   const bool first = ap0 && c.at.opt_init[2] != 0, sync = ap0 && c.at.opt_init[3] != 0;
+  const bool soft = SOFT && sync && c.aa.tau < 1.f;   // (a blending sync: the old P is read too)
   if (ap0 && tid < 84) {
     const int64_t i = uparam(tid);
     pth = c.at.theta[i];
     if (c.aa.rule != 0) pst = c.at.opt[i];
+    if (soft) ppo = c.at.thetaP[i];
   }
   float b4v[4], w5v[4][4];
 #pragma unroll
@@ -207,6 +212,7 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
   if (!ptower) {
     if (tid < 64) csm[CH_W5 + tid] = w5q;
     if (tid < 84) { csm[CH_PS + tid] = pth; csm[CH_PS + 96 + tid] = pst; }
+    if (soft && tid < 84) csm[CH_PS + 192 + tid] = ppo;
     for (int e = tid; e < 6 * B; e += 512)           // action one-hot, reward, non_terminal
       csm[CH_MB + e] = e < 4 * B ? c.action[e] : (e < 5 * B ? c.reward[e - 4 * B] : c.nonterm[e - 5 * B]);
   }
@@ -405,7 +411,8 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
           const float th = apply_rule(c.aa, first, is_bias, csm[CH_PS + pq], v, st);
           c.at.theta[i] = th;
           if (c.aa.rule != 0) c.at.opt[i] = st;
-          if (sync) c.at.thetaP[i] = th;
+          if (soft) c.at.thetaP[i] = target_blend(csm[CH_PS + 192 + pq], th, c.aa.tau);
+          else if (sync) c.at.thetaP[i] = th;
         }
       }
     }
@@ -494,14 +501,14 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
   DDQ_STAMP(23);
 }
 
-template <int NZ>
+template <int NZ, bool SOFT = false>
 __global__ __launch_bounds__(512) void fc4_chain16_kernel(const ChainArgs c) {
-  fc4_chain16_body<NZ, false>(c);
+  fc4_chain16_body<NZ, false, SOFT>(c);
 }
 // a non-default objective (ChainArgs::obj_*): the same body with its branches
-template <int NZ>
+template <int NZ, bool SOFT = false>
 __global__ __launch_bounds__(512) void fc4_chain16_obj_kernel(const ChainArgs c) {
-  fc4_chain16_body<NZ, true>(c);
+  fc4_chain16_body<NZ, true, SOFT>(c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1335,18 +1342,20 @@ struct WgArgs {
 // th0 / st0: the element's theta and optimizer state, loaded by the caller
 // ahead of the sums
 __device__ __forceinline__ void conv_final(const WgArgs& a, int l, bool is_w, int64_t i, int e,
-                                           float v, float th0, float st0, bool first, bool sync,
-                                           bool ap) {
+                                           float v, float th0, float st0, float po0, bool first,
+                                           bool sync, bool soft, bool ap) {
   a.grad[i] = v;
   if (!ap) return;
   float st = (a.aa.rule != 0 && !first) ? st0 : 0.f;
   const float th = apply_rule(a.aa, first, !is_w, th0, v, st);
   a.at.theta[i] = th;
   if (a.aa.rule != 0) a.at.opt[i] = st;
-  if (sync) a.at.thetaP[i] = th;
+  // what a due sync gives P: the copy, or the blend with its old value po0
+  const float tp = soft ? target_blend(po0, th, a.aa.tau) : th;
+  if (sync) a.at.thetaP[i] = tp;
   if (is_w) {
     put_conv_weight(a.cd[l], e, th, a.at.wks, a.at.wks_plane);
-    if (sync) put_conv_weight(a.cd[l], e, th, a.at.wksP, a.at.wks_plane);
+    if (sync) put_conv_weight(a.cd[l], e, tp, a.at.wksP, a.at.wks_plane);
   }
 }
 
@@ -1380,7 +1389,7 @@ __device__ __forceinline__ int64_t tile_elem(const WgArgs& a, int e, int ky, int
 // a failed meeting of the tile's groups withholds the slice's writes too.
 template <class W, int L, int KX, int D>
 __device__ __forceinline__ void wg_tile(const WgArgs& a, char* smem, int tile, int g, int G, int ipg,
-                                        float* slabs, bool first, bool sync, bool ap) {
+                                        float* slabs, bool first, bool sync, bool soft, bool ap) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   constexpr int KS = W::KS;
   constexpr int NT = KX * W::NCB;                      // accumulators per wave
@@ -1497,6 +1506,19 @@ __device__ __forceinline__ void wg_tile(const WgArgs& a, char* smem, int tile, i
                                              rth, (int)(want && ci >= 0 ? (uint32_t)ci * 4 : kOOB), 0, 0));
       dst[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                              rst, (int)(wst && ci >= 0 ? (uint32_t)ci * 4 : kOOB), 0, 0));
+    }
+  }
+  // (a blending sync: the old P of the same elements, with them)
+  float dpo[EPD];
+#pragma unroll
+  for (int k = 0; k < EPD; ++k) dpo[k] = 0.f;
+  if (soft && G == 1) {
+#pragma unroll
+    for (int k = 0; k < EPD; ++k) {
+      int le;
+      const int e = tid + 256 * k;
+      const int64_t ci = e < SLAB ? tile_elem<W, L, KX>(a, e, ky, kx0, cb, le) : -1;
+      if (ci >= 0) dpo[k] = a.at.thetaP[ci];
     }
   }
   __syncthreads();
@@ -1616,12 +1638,13 @@ __device__ __forceinline__ void wg_tile(const WgArgs& a, char* smem, int tile, i
         int le;
         const int64_t ci = tile_elem<W, L, KX>(a, e, ky, kx0, cb, le);
         if (ci < 0) continue;
-        float th = dth[k], st = dst[k];
+        float th = dth[k], st = dst[k], po = dpo[k];
         if (c0 > 0 && a.apply) {                      // past the preloaded chunk
           th = a.at.theta[ci];
           st = a.aa.rule != 0 ? a.at.opt[ci] : 0.f;
+          if (soft) po = a.at.thetaP[ci];
         }
-        conv_final(a, L, e < ELEMS, ci, le, fin[e], th, st, first, sync, ap);
+        conv_final(a, L, e < ELEMS, ci, le, fin[e], th, st, po, first, sync, soft, ap);
       }
     }
     DDQ_STAMP(SB + 5);
@@ -1641,16 +1664,17 @@ __device__ __forceinline__ void wg_tile(const WgArgs& a, char* smem, int tile, i
   for (int c0 = e0; c0 < e1; c0 += 256 * EPT) {
     int64_t ci_[EPT];
     int le_[EPT];
-    float th_[EPT], st_[EPT];
+    float th_[EPT], st_[EPT], po_[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
       const int e = c0 + tid + 256 * k;
-      ci_[k] = -1; le_[k] = 0; th_[k] = 0.f; st_[k] = 0.f;
+      ci_[k] = -1; le_[k] = 0; th_[k] = 0.f; st_[k] = 0.f; po_[k] = 0.f;
       if (e >= e1) continue;
       ci_[k] = tile_elem<W, L, KX>(a, e, ky, kx0, cb, le_[k]);
       if (ci_[k] >= 0 && a.apply) {
         th_[k] = a.at.theta[ci_[k]];
         if (a.aa.rule != 0) st_[k] = a.at.opt[ci_[k]];
+        if (soft) po_[k] = a.at.thetaP[ci_[k]];
       }
     }
     if (c0 == e0) {
@@ -1689,7 +1713,8 @@ __device__ __forceinline__ void wg_tile(const WgArgs& a, char* smem, int tile, i
     for (int k = 0; k < EPT; ++k) {
       const int e = c0 + tid + 256 * k;
       if (e < e1 && ci_[k] >= 0)
-        conv_final(a, L, e < ELEMS, ci_[k], le_[k], vs[k], th_[k], st_[k], first, sync, ap && mword == 0);
+        conv_final(a, L, e < ELEMS, ci_[k], le_[k], vs[k], th_[k], st_[k], po_[k], first, sync,
+                   soft, ap && mword == 0);
     }
   }
   DDQ_STAMP(SB + 5);
@@ -1698,7 +1723,8 @@ __device__ __forceinline__ void wg_tile(const WgArgs& a, char* smem, int tile, i
 // fc4's weights (512 x 256 at S = 16) updated from the gradient K2 stored, 4
 // consecutive elements a thread (coalesced), the rules of the other apply
 // sites (apply_rule, no FMA contraction: bit-identical updates)
-__device__ __forceinline__ void w4_apply(const WgArgs& a, int blk, bool first, bool sync, bool ap) {
+__device__ __forceinline__ void w4_apply(const WgArgs& a, int blk, bool first, bool sync, bool soft,
+                                         bool ap) {
   constexpr int64_t n = 512LL * kFcK;
   if (a.G == 1 && !ap) return;
   for (int64_t j = ((int64_t)blk * 256 + threadIdx.x) * 4; j < n; j += (int64_t)a.nw4 * 256 * 4) {
@@ -1718,6 +1744,8 @@ __device__ __forceinline__ void w4_apply(const WgArgs& a, int blk, bool first, b
     const float4 t = *reinterpret_cast<const float4*>(a.at.theta + i);
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.aa.rule != 0 && !first) o = *reinterpret_cast<const float4*>(a.at.opt + i);
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);      // (a blending sync: the old P)
+    if (soft) p = *reinterpret_cast<const float4*>(a.at.thetaP + i);
     const float gg[4] = {g.x, g.y, g.z, g.w};
     float th[4] = {t.x, t.y, t.z, t.w}, st[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
@@ -1725,27 +1753,34 @@ __device__ __forceinline__ void w4_apply(const WgArgs& a, int blk, bool first, b
     const float4 t4 = make_float4(th[0], th[1], th[2], th[3]);
     *reinterpret_cast<float4*>(a.at.theta + i) = t4;
     if (a.aa.rule != 0) *reinterpret_cast<float4*>(a.at.opt + i) = make_float4(st[0], st[1], st[2], st[3]);
-    if (sync) *reinterpret_cast<float4*>(a.at.thetaP + i) = t4;
+    if (soft)
+      *reinterpret_cast<float4*>(a.at.thetaP + i) =
+          make_float4(target_blend(p.x, th[0], a.aa.tau), target_blend(p.y, th[1], a.aa.tau),
+                      target_blend(p.z, th[2], a.aa.tau), target_blend(p.w, th[3], a.aa.tau));
+    else if (sync) *reinterpret_cast<float4*>(a.at.thetaP + i) = t4;
   }
 }
 
 // B <= 32: Q_out's biases from the gradient K2 stored (K2 leaves their update
 // here: every K2 workgroup reads them after its fan-in)
-__device__ __forceinline__ void b5_apply(const WgArgs& a, bool first, bool sync, bool ap) {
+__device__ __forceinline__ void b5_apply(const WgArgs& a, bool first, bool sync, bool soft, bool ap) {
   const int t = threadIdx.x;
   if (!ap || t >= 4) return;
   const int64_t i = a.b5_off + t;
   const float v = a.grad[i];
   float st = (a.aa.rule != 0 && !first) ? a.at.opt[i] : 0.f;
+  const float po = soft ? a.at.thetaP[i] : 0.f;
   const float th = apply_rule(a.aa, first, true, a.at.theta[i], v, st);
   a.at.theta[i] = th;
   if (a.aa.rule != 0) a.at.opt[i] = st;
-  if (sync) a.at.thetaP[i] = th;
+  if (soft) a.at.thetaP[i] = target_blend(po, th, a.aa.tau);
+  else if (sync) a.at.thetaP[i] = th;
 }
 
 // B > 32: the unit sums' partials (K2 upart) summed in chunk order -> db4,
 // dW5 (32 blocks x 80), db5 (4), loss; stored, and applied when apply
-__device__ __forceinline__ void units_apply(const WgArgs& a, bool first, bool sync, bool ap) {
+__device__ __forceinline__ void units_apply(const WgArgs& a, bool first, bool sync, bool soft,
+                                            bool ap) {
   for (int q = threadIdx.x; q < kFcBlk * 85; q += 256) {
     const int jb = q / 85, qq = q - jb * 85;
     if (qq >= 80 && jb != 0) continue;                // (db5, loss: block 0's)
@@ -1760,42 +1795,47 @@ __device__ __forceinline__ void units_apply(const WgArgs& a, bool first, bool sy
     a.grad[i] = v;
     if (!ap) continue;
     float st = (a.aa.rule != 0 && !first) ? a.at.opt[i] : 0.f;
+    const float po = soft ? a.at.thetaP[i] : 0.f;
     const float th = apply_rule(a.aa, first, is_bias, a.at.theta[i], v, st);
     a.at.theta[i] = th;
     if (a.aa.rule != 0) a.at.opt[i] = st;
-    if (sync) a.at.thetaP[i] = th;
+    if (soft) a.at.thetaP[i] = target_blend(po, th, a.aa.tau);
+    else if (sync) a.at.thetaP[i] = th;
   }
 }
 
 // Block order: conv3's tiles (the longest chains) first, conv2's, then
 // conv1's slab sums and the next step's gather (short, no meeting) -- every
 // meeting workgroup is dispatched before any block that could hold a CU.
-template <bool NS>
+// SOFT: a due target sync blends (ddq_set_target_tau < 1); without it the soft
+// form is compiled out and the default launch keeps its instruction stream
+template <bool NS, bool SOFT = false>
 __global__ __launch_bounds__(256) void wgrad16_kernel(const WgArgs a) {
   extern __shared__ __attribute__((aligned(16))) char wsm[];
   int bid = blockIdx.x;
   const bool first = a.apply && a.at.opt_init[2] != 0, sync = a.apply && a.at.opt_init[3] != 0;
+  const bool soft = SOFT && sync && a.aa.tau < 1.f;
   // (read now, needed only at the writes: the operand loads do not wait on it)
   const bool pois = a.apply && step_poisoned(a.poison0, a.poison1);
   const bool ap = a.apply && !pois;
   const int n2 = kT2 * a.G2, n3 = kT3 * a.G3;
   if (bid < n3) {
-    wg_tile<Wg3, 2, 3, 2>(a, wsm, bid % kT3, bid / kT3, a.G3, a.ipg3, a.slab3, first, sync, ap);
+    wg_tile<Wg3, 2, 3, 2>(a, wsm, bid % kT3, bid / kT3, a.G3, a.ipg3, a.slab3, first, sync, soft, ap);
     return;
   }
   bid -= n3;
   if (bid < n2) {
-    wg_tile<Wg2, 1, 5, 2>(a, wsm, bid % kT2, bid / kT2, a.G2, a.ipg2, a.slab2, first, sync, ap);
+    wg_tile<Wg2, 1, 5, 2>(a, wsm, bid % kT2, bid / kT2, a.G2, a.ipg2, a.slab2, first, sync, soft, ap);
     return;
   }
   bid -= n2;
   if (bid >= kW1Blocks) {   // the fc4 weights' (and unit sums') update, then the next
     const int x = bid - kW1Blocks;   // step's gather (B = 256: 512 short blocks, last)
     if (x < a.nw4) {
-      w4_apply(a, x, first, sync, ap);
-      if (x == 0 && a.G == 1) b5_apply(a, first, sync, ap);
+      w4_apply(a, x, first, sync, soft, ap);
+      if (x == 0 && a.G == 1) b5_apply(a, first, sync, soft, ap);
     }
-    else if (x < a.nw4 + a.nus) units_apply(a, first, sync, ap);
+    else if (x < a.nw4 + a.nus) units_apply(a, first, sync, soft, ap);
     else prefetch_body<NS>(a.pf, x - a.nw4 - a.nus);
     return;
   }
@@ -1816,10 +1856,11 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgArgs a) {
       le = co;
       i = a.b_off[0] + co;
     }
-    float th0 = 0.f, st0 = 0.f;                                   // ahead of the slab loads
+    float th0 = 0.f, st0 = 0.f, po0 = 0.f;                        // ahead of the slab loads
     if (a.apply) {
       th0 = a.at.theta[i];
       if (a.aa.rule != 0) st0 = a.at.opt[i];
+      if (soft) po0 = a.at.thetaP[i];
     }
     const float* src = a.w1part + co * np + n;
     float v = 0.f;
@@ -1839,7 +1880,7 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(const WgArgs a) {
       for (int u = 0; u < 8; ++u) v += t[u];
     }
     for (; b0 < a.B; ++b0) v += src[(int64_t)b0 * 32 * np];
-    conv_final(a, 0, n < 196, i, le, v, th0, st0, first, sync, ap);
+    conv_final(a, 0, n < 196, i, le, v, th0, st0, po0, first, sync, soft, ap);
   }
   DDQ_STAMP(41);
 }

@@ -116,6 +116,9 @@ _SIGS = {
     "ddq_get_grads": (ctypes.c_int, [_P, _P, _i64, _i32]),
     "ddq_set_grads": (ctypes.c_int, [_P, _P, _i64, _i32]),
     "ddq_sync_target": (ctypes.c_int, [_P]),
+    "ddq_set_target_tau": (ctypes.c_int, [_P, ctypes.c_float]),
+    "ddq_get_target_tau": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "ddq_soft_sync_target": (ctypes.c_int, [_P]),
     "ddq_replay_create": (ctypes.c_int, [_P, _i64]),
     "ddq_replay_add": (ctypes.c_int, [_P, _i32, _i32, _P]),
     "ddq_replay_info": (ctypes.c_int, [_P, ctypes.POINTER(_i64), ctypes.POINTER(_i64),

@@ -2,7 +2,7 @@
 with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
-reset_log=False, objective=None, n_step=None, priority=None)``:
+reset_log=False, objective=None, n_step=None, priority=None, target_tau=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -22,7 +22,12 @@ reset_log=False, objective=None, n_step=None, priority=None)``:
   proportional prioritized replay (``DeepQNet.replay_set_priority``), set on
   every dataset added.  With it ``load_minibatch`` takes the device's
   prioritized draw and ``full_pass`` is followed by the commit of the pass's
-  |TD| to the drawn slots.
+  |TD| to the drawn slots;
+* ``target_tau`` -- None (hard target syncs) or the tau in (0, 1] of soft target
+  updates (``DeepQNet.set_target_tau``), set on the net's context: every target
+  sync of a step taken there (``DeviceActor.act_and_train``, an actor pool's
+  steps) then blends, P <- P + tau (Q - P).  The construction's own P <- Q stays
+  a copy (it defines P).
 
 The input buffers ``state``, ``action``, ``reward``, ``next_state``,
 ``non_terminal`` have the reference's shapes (baristanet.py:30-34).  They are
@@ -76,7 +81,7 @@ class _Blob:
 class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
                  reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
-                 priority=None):
+                 priority=None, target_tau=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
@@ -94,6 +99,9 @@ class BaristaNet:
         else:
             self.dqn.set_flat(0, P.init_params_flat(frame))
         self.dqn.sync_target()
+        self.target_tau = None if target_tau is None else float(target_tau)
+        if self.target_tau is not None:
+            self.dqn.set_target_tau(self.target_tau)
         self.dataset = None
         self.n_step = None if n_step is None else int(n_step)
         self.priority = priority

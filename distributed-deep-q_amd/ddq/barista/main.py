@@ -8,7 +8,7 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
         [--port 50001] [--driver 127.0.0.1:5500|None] [--dataset replay-dataset.hdf5]
         [--dset-size 1000] [--overwrite] [--debug] [--initial-replay 20000]
         [--device-actor [--actor-seed N]] [--logpath PREFIX]
-        [--double-q] [--huber-delta D]
+        [--double-q] [--huber-delta D] [--target-tau T]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
 step on the host through the CPU twin libddq_cpu.so (main.py:128,149-151, the
@@ -23,6 +23,11 @@ the replay add run inside the net's context (ddq_actor_step_async), so
 objective the gradients are computed for (``DeepQNet.set_objective``): the
 Double-DQN target r + gamma P(s', argmax_a Q(s',a)) in place of the max, and the
 Huber loss with band D in place of the Euclidean one.  Both work in either mode.
+
+``--target-tau T`` (default: hard target syncs) sets soft target updates on the
+net's context (``DeepQNet.set_target_tau``), T in (0, 1]: the training steps taken
+there (``--device-actor``'s ``act_and_train``, an actor pool) blend P towards Q at
+every target sync, P <- P + T (Q - P).  Either mode.
 
 ``--n-step N`` (default 1) gathers the minibatches for N-step returns
 (``DeepQNet.replay_set_nstep``): the discounted sum of up to N rewards and
@@ -118,6 +123,8 @@ def get_args(argv=None):
                     help="Double-DQN target: P at argmax_a Q(s',a) instead of max_a P")
     ap.add_argument("--huber-delta", dest="huber_delta", type=float, default=None,
                     help="Huber loss with this band instead of the Euclidean loss")
+    ap.add_argument("--target-tau", dest="target_tau", type=float, default=None,
+                    help="soft target updates: P <- P + T (Q - P) at every target sync, T in (0, 1]")
     ap.add_argument("--n-step", dest="n_step", type=int, default=1,
                     help="N-step returns: the replay gathers N-step windows (default 1)")
     ap.add_argument("--per-alpha", dest="per_alpha", type=float, default=None,
@@ -139,6 +146,8 @@ def get_args(argv=None):
         ap.error("--n-step must be in [1, %d]" % NSTEP_MAX)
     if args.n_step >= args.dset_size:
         ap.error("--n-step must be below --dset-size (%d)" % args.dset_size)
+    if args.target_tau is not None and not 0.0 < args.target_tau <= 1.0:
+        ap.error("--target-tau must be in (0, 1]")
     if args.huber_delta is not None and not args.huber_delta > 0:
         ap.error("--huber-delta must be > 0")
     if args.driver == "None":
@@ -172,7 +181,7 @@ def build_worker(args):
     model = None if args.model in ("none", "None") else args.model
     net = BaristaNet(args.architecture, model, args.driver,
                      logpath=getattr(args, "logpath", None), mode=args.mode,
-                     objective=objective_of(args))
+                     objective=objective_of(args), target_tau=getattr(args, "target_tau", None))
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
                            overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode,
                            n_step=getattr(args, "n_step", 1), priority=priority_of(args))

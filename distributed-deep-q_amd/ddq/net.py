@@ -148,6 +148,23 @@ class DeepQNet:
         """special_update_transform_model (param-server/server.py:127-137)."""
         self._check(self.lib.ddq_sync_target(self.ctx))
 
+    def set_target_tau(self, tau):
+        """Soft target updates (ddq_set_target_tau): with ``tau`` < 1 every
+        target sync of a step writes ``P + tau * (Q - P)`` instead of copying Q
+        (``target_period=1``: the usual Polyak rule); 1 (the default) is the
+        hard copy.  Not under the async exchange."""
+        self._check(self.lib.ddq_set_target_tau(self.ctx, float(tau)))
+
+    def target_tau(self):
+        t = ctypes.c_float()
+        self._check(self.lib.ddq_get_target_tau(self.ctx, ctypes.byref(t)))
+        return float(t.value)
+
+    def soft_sync_target(self):
+        """The host-driven soft update: P <- P + tau * (Q - P) now, with the
+        context's tau (tau = 1: ``sync_target``)."""
+        self._check(self.lib.ddq_soft_sync_target(self.ctx))
+
     # -------------------------------------------------------------- minibatch
     def write_minibatch(self, state=None, action=None, reward=None, next_state=None,
                         non_terminal=None):

@@ -50,7 +50,7 @@ def get_snapshot_name(iteration):
 class ParamServer:
     def __init__(self, frame=16, batch=32, update="rmsprop", lr=1e-4, rmsprop_decay=0.9,
                  special_update=10, snapshot_freq=500, stats_freq=500, device=0,
-                 on_snapshot=None, mode="gpu", on_stats=None, adam=None):
+                 on_snapshot=None, mode="gpu", on_stats=None, adam=None, target_tau=None):
         if update not in ("sgd", "rmsprop", "adagrad", "adam"):
             raise ValueError("update must be one of adagrad, adam, rmsprop, sgd")
         self.net = DeepQNet(batch=batch, frame=frame, device=device, mode=mode)
@@ -58,6 +58,11 @@ class ParamServer:
         # clip), adam = DeepQNet.set_adam's keywords
         if update == "adam":
             self.net.set_adam(**(adam or {}))
+        # no reference counterpart: soft target updates.  With target_tau < 1 a
+        # special update blends, P <- P + tau (Q - P), once a target exists (the
+        # first one still copies, so that P is defined)
+        if target_tau is not None:
+            self.net.set_target_tau(target_tau)
         self.update = update
         self.learning_rate = float(lr)
         self.rmsprop_decay = float(rmsprop_decay)
@@ -107,7 +112,10 @@ class ParamServer:
             if not self.has_model:
                 return messaging.create_message({}, self.iteration)
             if self.iteration % self.special_update_period == 0:
-                self.net.sync_target()
+                if self.has_target:
+                    self.net.soft_sync_target()     # (tau = 1: the copy)
+                else:
+                    self.net.sync_target()
                 self.has_target = True
             return messaging.create_message(self.model_params(), self.iteration)
 

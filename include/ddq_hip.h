@@ -58,7 +58,8 @@ extern "C" {
                               ddq_replay_update_priorities_async; blob "is_weight"),
                               likewise; and the Adam rule (DDQ_RULE_ADAM, ddq_set_adam,
                               ddq_get_adam, ddq_adam_state; blob "grad_norm"),
-                              likewise */
+                              likewise; and soft target updates (ddq_set_target_tau,
+                              ddq_get_target_tau, ddq_soft_sync_target), likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -220,6 +221,25 @@ int ddq_get_grads(ddq_ctx* ctx, float* dst, int64_t n, int32_t dst_on_device);
 int ddq_set_grads(ddq_ctx* ctx, const float* src, int64_t n, int32_t src_on_device);
 /* special_update_transform_model (server.py:127-137): P <- Q. */
 int ddq_sync_target(ddq_ctx* ctx);
+/* Soft target updates (Polyak averaging).  tau in (0, 1], default 1; DDQ_EINVAL
+ * for tau <= 0, tau > 1 or NaN.  With tau < 1 every target sync a step performs
+ * (the update after which iteration % target_period == 0) writes
+ *   P' = P + tau * (Q' - P)
+ * instead of P' = Q': three fp32 operations, each rounded on its own, Q' the
+ * value the step just gave theta_Q; the conv weights' derived copies of P follow
+ * the blended value.  tau = 1 is the hard copy, exactly as before.  The
+ * iteration-0 sync of the first step and ddq_sync_target stay hard copies.
+ * target_period = 1 is the usual every-update Polyak rule; period k blends on
+ * every k-th update.  Holds for eager, graph and pipelined steps, for no
+ * exchange, all-reduce, sharded and server; DDQ_EXCHANGE_ASYNC refuses tau < 1
+ * with DDQ_EINVAL (its P travels by pulls).  tau is a launch argument: setting
+ * it drops every captured graph. */
+int ddq_set_target_tau(ddq_ctx* ctx, float tau);
+int ddq_get_target_tau(const ddq_ctx* ctx, float* tau);
+/* The host-driven soft update beside ddq_sync_target: one launch blends all of
+ * P towards Q with the context's tau (the same rounding) and rewrites P's
+ * derived conv-weight copies.  With tau = 1 it is ddq_sync_target. */
+int ddq_soft_sync_target(ddq_ctx* ctx);
 
 /* ---------------- replay (replay.py) ----------------------------------- */
 /* ReplayDataset.__init__ storage (replay.py:48-61), HBM resident, zeroed. */
