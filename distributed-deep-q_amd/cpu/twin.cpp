@@ -143,6 +143,15 @@ struct ddq_ctx {
   // training monitor (ddq_monitor_*): the ring (empty: off) and the records taken
   std::vector<ddq_monitor_record> m_ring;
   int64_t m_total = 0;
+  // pool: the ring's per-lane head / valid at create, moves made since (the
+  // HIP library's launch constants; here only the "counters" section has them)
+  int64_t p_h0 = 0, p_v0 = 0, p_moves = 0;
+  // checkpoint and resume (ddq_state_*): restoring from the first
+  // ddq_state_write of a section other than "config" until ddq_state_commit;
+  // the counters and the games as written (the games in the sections' layout)
+  bool restoring = false;
+  ddq_state_counters st_ctr{};
+  std::vector<uint8_t> st_actor, st_pool;
   std::string err;
 };
 
@@ -157,6 +166,15 @@ int fail(ddq_ctx* c, int code, const char* fmt, ...) {
   if (c) c->err = buf;
   g_err = buf;
   return code;
+}
+
+// The guard of every call that computes on the training state: not between
+// the first ddq_state_write and ddq_state_commit.
+int not_restoring(ddq_ctx* c) {
+  if (c->restoring)
+    return fail(c, DDQ_ESTATE, "restore not committed: sections were written with ddq_state_write, "
+                               "call ddq_state_commit first");
+  return DDQ_OK;
 }
 
 int cpu_only(ddq_ctx* c, const char* what) {
@@ -959,6 +977,7 @@ int ddq_replay_add(ddq_ctx* c, int32_t action, int32_t reward, const uint8_t* st
   if (c->lanes > 1) return fail(c, DDQ_ESTATE, "ddq_replay_add on a laned ring (%d lanes)", c->lanes);
   if (action < 0 || action > 255) return fail(c, DDQ_EINVAL, "action must fit uint8");
   if (reward < -32768 || reward > 32767) return fail(c, DDQ_EINVAL, "reward must fit int16");
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   const size_t slot = (size_t)kC * c->S * c->S;
   const int64_t h = c->head;
   c->r_action[h] = (uint8_t)action;
@@ -1015,6 +1034,7 @@ int ddq_replay_export(ddq_ctx* c, uint8_t* state, uint8_t* action, int16_t* rewa
 int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
   if (!c || !idx) return fail(c, DDQ_EINVAL, "null argument");
   if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer");
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   if (batch > c->lanes * allowed_slots(c))   // B < valid on a plain ring at n = 1
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 batch, (long long)(c->lanes * c->valid));
@@ -1044,6 +1064,7 @@ int ddq_replay_sample(ddq_ctx* c, const int32_t* idx, int32_t batch) {
 int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
   if (!c || !c->prio_on)
     return cpu_only(c, "ddq_replay_sample_device_async (device index stream)");
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   if (c->B > c->lanes * allowed_slots(c))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 c->B, (long long)(c->lanes * c->valid));
@@ -1125,6 +1146,7 @@ int ddq_index_log_read(ddq_ctx* c, int64_t, int64_t, int32_t*) {
 // ---- compute ----
 int ddq_forward_backward_async(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   return forward_backward(c);
 }
 
@@ -1158,6 +1180,7 @@ int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
 
 int ddq_forward_q(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   tower_fwd(c, 0, c->state.data(), c->B);
   c->q_out = c->tw[0].out;
   return DDQ_OK;
@@ -1201,6 +1224,7 @@ int ddq_read_pool_mask(ddq_ctx* c, int32_t layer, uint8_t* dst, int64_t n) {
 int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* actions) {
   if (!c || !states || !actions) return fail(c, DDQ_EINVAL, "null argument");
   if (n < 1 || n > c->B) return fail(c, DDQ_EINVAL, "n must be in [1,B]");
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   const size_t e = (size_t)n * kC * c->S * c->S;
   std::vector<float> in(states, states + e);
   Tower keep = c->tw[0];            // acting does not touch the last training pass
@@ -1396,6 +1420,7 @@ int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (c->a_env.games.empty()) return fail(c, DDQ_ESTATE, "no actor (call ddq_actor_create)");
   if (nsteps < 1) return fail(c, DDQ_EINVAL, "nsteps must be >= 1 (got %d)", nsteps);
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   const double eps = actor_eps(iter_num);
   ddq_ctx::Game& g = c->a_env.games[0];
   std::vector<uint8_t> frames((size_t)kC * c->S * c->S);
@@ -1459,6 +1484,7 @@ int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (c->e_env.games.empty()) return fail(c, DDQ_ESTATE, "no evaluator (call ddq_eval_create)");
   if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   std::vector<int32_t> greedy;
   for (int m = 0; m < nmoves; ++m) {
     const int rc = env_greedy(c, c->e_env, &greedy);
@@ -1522,6 +1548,9 @@ int ddq_actors_create(ddq_ctx* c, int32_t ngames, const int8_t* init_boards,
                 c->lanes);
   env_reset(&c->p_env, ngames, init_boards, row_map, col_map, c->S);
   for (int g = 0; g < ngames; ++g) c->p_env.games[g].seed = game_seed(seed, g);
+  c->p_h0 = c->head;
+  c->p_v0 = c->valid;
+  c->p_moves = 0;
   return DDQ_OK;
 }
 
@@ -1529,6 +1558,7 @@ int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   if (c->p_env.games.empty()) return fail(c, DDQ_ESTATE, "no actor pool (call ddq_actors_create)");
   if (nmoves < 1) return fail(c, DDQ_EINVAL, "nmoves must be >= 1 (got %d)", nmoves);
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   const double eps = actor_eps(iter_num);
   const int n = (int)c->p_env.games.size();
   const size_t fs = (size_t)kC * c->S * c->S;
@@ -1556,6 +1586,7 @@ int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
     c->head = (h + 1) % c->lane_len;
     c->valid = std::min(c->lane_len, c->valid + 1);
     for (int g = 0; g < n; ++g) prio_on_add(c, (int64_t)g * c->lane_len, h);
+    c->p_moves++;
   }
   return DDQ_OK;
 }
@@ -1653,6 +1684,7 @@ int ddq_apply_async(ddq_ctx* c, const ddq_update_cfg* u) {
   if (!u) return fail(c, DDQ_EINVAL, "null update cfg");
   if (u->rule < 0 || u->rule > DDQ_RULE_ADAM)
     return fail(c, DDQ_EINVAL, "unknown update rule %d", u->rule);
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   if (u->rule == DDQ_RULE_ADAM) {
     if (!c->adam_on) return fail(c, DDQ_ESTATE, "DDQ_RULE_ADAM before ddq_set_adam");
     return adam_apply(c, u->lr);
@@ -1815,6 +1847,345 @@ double ddq_step_flops(const ddq_ctx* c) {
   const double F = (double)c->B * (6272 * s1 * s1 + 51200 * s2 * s2 + 36864 * s3 * s3 +
                                    32768 * s4 * s4 + 2048);
   return 2.0 * (4.0 * F - (double)c->B * 6272 * s1 * s1);
+}
+
+}  // extern "C"
+
+// ---- checkpoint and resume (include/ddq_hip.h ddq_state_*) ----
+// The same sections, byte for byte, as the HIP library's: the vectors in
+// place, the games in the device struct's layout (544 bytes each), the two
+// fixed structs assembled here.  The digest is the plain loop of its definition.
+namespace {
+
+constexpr int kStateMax = 16;
+constexpr int64_t kGameBytes = 544;   // ActorState of the HIP library
+
+struct StateSec {
+  const char* name;
+  int64_t bytes;
+  uint8_t* mem;     // nullptr: assembled (config, counters, actor, pool)
+};
+
+int state_table(ddq_ctx* c, StateSec* t) {
+  const int64_t P4 = c->L.total * 4, cap = c->capacity;
+  auto u8 = [](auto& v) { return reinterpret_cast<uint8_t*>(v.data()); };
+  int n = 0;
+  t[n++] = {"config", (int64_t)sizeof(ddq_state_config), nullptr};
+  t[n++] = {"theta_q", P4, u8(c->theta[0])};
+  t[n++] = {"theta_p", P4, u8(c->theta[1])};
+  t[n++] = {"opt", P4, u8(c->opt)};
+  if (c->adam_on) t[n++] = {"opt2", P4, u8(c->opt2)};
+  t[n++] = {"counters", (int64_t)sizeof(ddq_state_counters), nullptr};
+  if (cap) {
+    t[n++] = {"ring_state", cap * kC * c->S * c->S, u8(c->r_state)};
+    t[n++] = {"ring_action", cap, u8(c->r_action)};
+    t[n++] = {"ring_reward", 2 * cap, u8(c->r_reward)};
+    t[n++] = {"ring_nonterm", cap, u8(c->r_nonterm)};
+  }
+  if (c->prio_on) t[n++] = {"prio_leaf", 4 * cap, u8(c->prio_q)};
+  if (!c->a_env.games.empty()) t[n++] = {"actor", kGameBytes, nullptr};
+  if (!c->p_env.games.empty())
+    t[n++] = {"pool", kGameBytes * (int64_t)c->p_env.games.size(), nullptr};
+  return n;
+}
+
+ddq_state_config state_config(const ddq_ctx* c) {
+  ddq_state_config k;
+  memset(&k, 0, sizeof(k));
+  k.batch = (int16_t)c->B;
+  k.frame = (int16_t)c->S;
+  memcpy(&k.gamma_bits, &c->gamma, 4);
+  k.capacity = c->capacity;
+  k.lanes = c->capacity ? c->lanes : 1;
+  k.nstep = (uint8_t)(c->capacity ? c->nstep : 1);
+  if (c->prio_on) {
+    k.prio_enabled = 1;
+    k.prio_alpha = c->prio_cfg.alpha; k.prio_beta = c->prio_cfg.beta; k.prio_eps = c->prio_cfg.eps;
+  }
+  k.obj_target = (uint8_t)c->obj.target;
+  k.obj_loss = (uint8_t)c->obj.loss;
+  k.huber_delta = c->obj.huber_delta;
+  if (c->adam_on) {
+    k.adam_on = 1;
+    k.adam_beta1 = c->adam.beta1; k.adam_beta2 = c->adam.beta2;
+    k.adam_eps = c->adam.eps; k.adam_max_grad_norm = c->adam.max_grad_norm;
+  }
+  k.actor = c->a_env.games.empty() ? 0 : 1;
+  k.pool_games = (int16_t)c->p_env.games.size();
+  k.target_tau = c->target_tau;
+  return k;
+}
+
+const char* state_config_diff(const ddq_state_config& a, const ddq_state_config& b) {
+#define DDQ_CFG_FIELD(f) \
+  if (memcmp(&a.f, &b.f, sizeof(a.f)) != 0) return #f;
+  DDQ_CFG_FIELD(batch) DDQ_CFG_FIELD(frame) DDQ_CFG_FIELD(gamma_bits) DDQ_CFG_FIELD(capacity)
+  DDQ_CFG_FIELD(lanes) DDQ_CFG_FIELD(nstep) DDQ_CFG_FIELD(prio_enabled) DDQ_CFG_FIELD(obj_target)
+  DDQ_CFG_FIELD(obj_loss) DDQ_CFG_FIELD(prio_alpha) DDQ_CFG_FIELD(prio_beta) DDQ_CFG_FIELD(prio_eps)
+  DDQ_CFG_FIELD(huber_delta) DDQ_CFG_FIELD(adam_on) DDQ_CFG_FIELD(actor) DDQ_CFG_FIELD(pool_games)
+  DDQ_CFG_FIELD(adam_beta1) DDQ_CFG_FIELD(adam_beta2) DDQ_CFG_FIELD(adam_eps)
+  DDQ_CFG_FIELD(adam_max_grad_norm) DDQ_CFG_FIELD(target_tau)
+#undef DDQ_CFG_FIELD
+  return nullptr;
+}
+
+ddq_state_counters state_counters_now(const ddq_ctx* c) {
+  ddq_state_counters k;
+  memset(&k, 0, sizeof(k));
+  k.iteration = c->iter;
+  k.steps = c->steps;
+  k.opt_init = c->first ? 0 : 1;
+  if (c->capacity) {
+    k.head = c->head;
+    k.valid = c->valid;
+    k.draws = c->prio_ctr;
+  }
+  if (!c->p_env.games.empty()) {
+    k.pool_h0 = c->p_h0;
+    k.pool_v0 = c->p_v0;
+    k.pool_moves = c->p_moves;
+  }
+  if (c->prio_on) k.pmax = c->prio_pmax;
+  return k;
+}
+
+// a game <-> its 544 bytes: seed, draws, steps, games, reward sum, the four
+// history boards, the start board, four zero bytes
+void game_pack(const ddq_ctx::Game& g, uint8_t* out) {
+  memset(out, 0, (size_t)kGameBytes);
+  const uint64_t w[5] = {g.seed, g.draws, (uint64_t)g.steps, (uint64_t)g.games, (uint64_t)g.reward};
+  memcpy(out, w, 40);
+  memcpy(out + 40, g.boards, 400);
+  memcpy(out + 440, g.init, 100);
+}
+void game_unpack(const uint8_t* in, ddq_ctx::Game* g) {
+  uint64_t w[5];
+  memcpy(w, in, 40);
+  g->seed = w[0]; g->draws = w[1];
+  g->steps = (int64_t)w[2]; g->games = (int64_t)w[3]; g->reward = (int64_t)w[4];
+  memcpy(g->boards, in + 40, 400);
+  memcpy(g->init, in + 440, 100);
+}
+std::vector<uint8_t> games_pack(const std::vector<ddq_ctx::Game>& gs) {
+  std::vector<uint8_t> out(gs.size() * (size_t)kGameBytes);
+  for (size_t i = 0; i < gs.size(); ++i) game_pack(gs[i], out.data() + i * kGameBytes);
+  return out;
+}
+
+bool board_ok(const int8_t* b) {
+  std::vector<Cell> body;
+  if (!snake_body(b, &body) || body.size() < 2) return false;
+  return std::abs(body[0].x - body[1].x) + std::abs(body[0].y - body[1].y) == 1;
+}
+
+// an assembled section's bytes: as written while restoring, as the ctx has them otherwise
+std::vector<uint8_t> state_assembled(ddq_ctx* c, const StateSec& s) {
+  std::vector<uint8_t> out((size_t)s.bytes);
+  if (!strcmp(s.name, "config")) {
+    const ddq_state_config k = state_config(c);
+    memcpy(out.data(), &k, sizeof(k));
+  } else if (!strcmp(s.name, "counters")) {
+    const ddq_state_counters k = c->restoring ? c->st_ctr : state_counters_now(c);
+    memcpy(out.data(), &k, sizeof(k));
+  } else if (!strcmp(s.name, "actor")) {
+    out = c->restoring ? c->st_actor : games_pack(c->a_env.games);
+  } else {
+    out = c->restoring ? c->st_pool : games_pack(c->p_env.games);
+  }
+  return out;
+}
+
+uint64_t state_digest_bytes(const uint8_t* p, uint64_t n) {
+  uint64_t d = mix64(n);
+  const uint64_t K = (n + 7) / 8;
+  for (uint64_t k = 0; k < K; ++k) {
+    uint64_t w = 0;
+    const uint64_t have = std::min<uint64_t>(8, n - 8 * k);
+    for (uint64_t b = 0; b < have; ++b) w |= (uint64_t)p[8 * k + b] << (8 * b);
+    d += mix64(w ^ ((k + 1) * 0x9E3779B97F4A7C15ull));
+  }
+  return d;
+}
+
+uint64_t state_section_digest(ddq_ctx* c, const StateSec& s) {
+  if (s.mem) return state_digest_bytes(s.mem, (uint64_t)s.bytes);
+  const std::vector<uint8_t> b = state_assembled(c, s);
+  return state_digest_bytes(b.data(), b.size());
+}
+
+int state_find(ddq_ctx* c, const char* name, StateSec* out) {
+  if (!name) return fail(c, DDQ_EINVAL, "null section name");
+  StateSec t[kStateMax];
+  const int n = state_table(c, t);
+  for (int i = 0; i < n; ++i)
+    if (!strcmp(t[i].name, name)) {
+      *out = t[i];
+      return DDQ_OK;
+    }
+  return fail(c, DDQ_EINVAL, "no section '%s' on this ctx", name);
+}
+
+int state_range(ddq_ctx* c, const StateSec& s, int64_t offset, int64_t bytes) {
+  if (offset < 0 || bytes <= 0 || offset > s.bytes || bytes > s.bytes - offset)
+    return fail(c, DDQ_EINVAL, "section '%s' has %lld bytes: [%lld, %lld + %lld) is not inside it",
+                s.name, (long long)s.bytes, (long long)offset, (long long)offset, (long long)bytes);
+  return DDQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ddq_state_sections(ddq_ctx* c, ddq_state_section* out, int32_t cap, int32_t* n) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!n) return fail(c, DDQ_EINVAL, "null argument");
+  StateSec t[kStateMax];
+  const int k = state_table(c, t);
+  *n = k;
+  if (!out) return DDQ_OK;
+  if (cap < k) return fail(c, DDQ_EINVAL, "the ctx has %d sections (cap = %d)", k, cap);
+  for (int i = 0; i < k; ++i) {
+    memset(&out[i], 0, sizeof(out[i]));
+    snprintf(out[i].name, sizeof(out[i].name), "%s", t[i].name);
+    out[i].bytes = t[i].bytes;
+    out[i].digest = state_section_digest(c, t[i]);
+  }
+  return DDQ_OK;
+}
+
+int ddq_state_digest(ddq_ctx* c, const char* name, uint64_t* digest) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!digest) return fail(c, DDQ_EINVAL, "null argument");
+  StateSec s{};
+  int rc = state_find(c, name, &s);
+  if (rc != DDQ_OK) return rc;
+  *digest = state_section_digest(c, s);
+  return DDQ_OK;
+}
+
+int ddq_state_read(ddq_ctx* c, const char* name, int64_t offset, void* dst, int64_t bytes) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!dst) return fail(c, DDQ_EINVAL, "null argument");
+  StateSec s{};
+  int rc = state_find(c, name, &s);
+  if (rc == DDQ_OK) rc = state_range(c, s, offset, bytes);
+  if (rc != DDQ_OK) return rc;
+  if (s.mem) {
+    memcpy(dst, s.mem + offset, (size_t)bytes);
+    return DDQ_OK;
+  }
+  const std::vector<uint8_t> b = state_assembled(c, s);
+  memcpy(dst, b.data() + offset, (size_t)bytes);
+  return DDQ_OK;
+}
+
+int ddq_state_write(ddq_ctx* c, const char* name, int64_t offset, const void* src, int64_t bytes) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!src) return fail(c, DDQ_EINVAL, "null argument");
+  StateSec s{};
+  int rc = state_find(c, name, &s);
+  if (rc == DDQ_OK) rc = state_range(c, s, offset, bytes);
+  if (rc != DDQ_OK) return rc;
+  if (!strcmp(s.name, "config")) {   // compared, never written
+    if (offset != 0 || bytes != s.bytes)
+      return fail(c, DDQ_EINVAL, "section 'config' is compared as a whole (%lld bytes)", (long long)s.bytes);
+    ddq_state_config theirs;
+    memcpy(&theirs, src, sizeof(theirs));
+    if (const char* f = state_config_diff(state_config(c), theirs))
+      return fail(c, DDQ_EINVAL, "config mismatch: field '%s' of the checkpoint differs from this ctx "
+                                 "(configure the ctx as the writer was configured)", f);
+    return DDQ_OK;
+  }
+  if (!c->restoring) {
+    c->st_ctr = state_counters_now(c);
+    c->st_actor = games_pack(c->a_env.games);
+    c->st_pool = games_pack(c->p_env.games);
+    c->restoring = true;
+  }
+  uint8_t* to = s.mem;
+  if (!to)
+    to = !strcmp(s.name, "counters") ? reinterpret_cast<uint8_t*>(&c->st_ctr)
+         : !strcmp(s.name, "actor")  ? c->st_actor.data()
+                                     : c->st_pool.data();
+  memcpy(to + offset, src, (size_t)bytes);
+  return DDQ_OK;
+}
+
+int ddq_state_commit(ddq_ctx* c) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->restoring) return DDQ_OK;
+  const ddq_state_counters k = c->st_ctr;
+  const bool ring = c->capacity != 0;
+  const int64_t L = c->lane_len;
+  if (k.iteration < 0 || k.steps < 0 || (k.opt_init != 0 && k.opt_init != 1) || k.ring_err < 0 ||
+      k.ring_err > 2 || k.reserved[0] || k.reserved[1] || k.reserved[2])
+    return fail(c, DDQ_EINVAL, "counters: iteration %lld, steps %lld, opt_init %d, ring_err %d or a "
+                               "reserved word out of range",
+                (long long)k.iteration, (long long)k.steps, k.opt_init, k.ring_err);
+  if (ring ? (k.head < 0 || k.head >= L || k.valid < 0 || k.valid > L)
+           : (k.head != 0 || k.valid != 0 || k.draws != 0 || k.batch_ctr != 0))
+    return fail(c, DDQ_EINVAL, "counters: head %lld / valid %lld outside the ring's lane length %lld",
+                (long long)k.head, (long long)k.valid, (long long)(ring ? L : 0));
+  const bool pool = !c->p_env.games.empty();
+  if (pool ? (k.pool_h0 < 0 || k.pool_h0 >= L || k.pool_v0 < 0 || k.pool_v0 > L ||
+              k.pool_moves < 0 || k.head != (k.pool_h0 + k.pool_moves % L) % L ||
+              k.valid != std::min(L, k.pool_v0 + std::min(k.pool_moves, L)))
+           : (k.pool_h0 != 0 || k.pool_v0 != 0 || k.pool_moves != 0))
+    return fail(c, DDQ_EINVAL, "counters: the pool's h0 %lld, v0 %lld, moves %lld do not give the "
+                               "ring's head %lld / valid %lld",
+                (long long)k.pool_h0, (long long)k.pool_v0, (long long)k.pool_moves,
+                (long long)k.head, (long long)k.valid);
+  for (int role = 0; role < 2; ++role) {
+    const std::vector<uint8_t>& blob = role ? c->st_pool : c->st_actor;
+    const int n = (int)(blob.size() / (size_t)kGameBytes);
+    for (int g = 0; g < n; ++g) {
+      ddq_ctx::Game gm;
+      game_unpack(blob.data() + (size_t)g * kGameBytes, &gm);
+      for (int f = 0; f < 5; ++f)
+        if (!board_ok(f < 4 ? gm.boards[f] : gm.init))
+          return fail(c, DDQ_EINVAL, "%s: game %d, board %d is not a Snake board", role ? "pool" : "actor",
+                      g, f);
+      if (gm.steps < 0 || (role && gm.steps != k.pool_moves))
+        return fail(c, DDQ_EINVAL, "%s: game %d made %lld steps (the pool's moves: %lld)",
+                    role ? "pool" : "actor", g, (long long)gm.steps, (long long)k.pool_moves);
+    }
+  }
+  if (c->prio_on) {
+    if (k.pmax < kPrioOne || k.pmax > kPrioMax)
+      return fail(c, DDQ_EINVAL, "counters: pmax %u outside [65536, 2^24]", k.pmax);
+    int64_t bad = 0, first = -1;
+    for (int64_t i = 0; i < c->capacity; ++i) {
+      const int64_t x = i % L;
+      const bool zero = !(x < k.valid) || prio_forbidden(x, k.head, k.valid, L, c->nstep);
+      if (c->prio_q[i] > kPrioMax || (c->prio_q[i] == 0) != zero) {
+        if (!bad) first = i;
+        ++bad;
+      }
+    }
+    if (bad)
+      return fail(c, DDQ_EINVAL, "prio_leaf: %lld leaves are above 2^24 or break \"zero <=> slot unfilled "
+                                 "or forbidden\" under head %lld, valid %lld, n %d (first: slot %lld)",
+                  (long long)bad, (long long)k.head, (long long)k.valid, c->nstep, (long long)first);
+  } else if (k.pmax != 0) {
+    return fail(c, DDQ_EINVAL, "counters: pmax %u while prioritized replay is off", k.pmax);
+  }
+  c->iter = k.iteration;
+  c->steps = k.steps;
+  c->first = k.opt_init ? 0 : 1;
+  c->head = k.head;
+  c->valid = k.valid;
+  c->prio_ctr = k.draws;
+  c->p_h0 = k.pool_h0;
+  c->p_v0 = k.pool_v0;
+  c->p_moves = k.pool_moves;
+  if (c->prio_on) c->prio_pmax = k.pmax;
+  for (size_t g = 0; g < c->a_env.games.size(); ++g)
+    game_unpack(c->st_actor.data() + g * kGameBytes, &c->a_env.games[g]);
+  for (size_t g = 0; g < c->p_env.games.size(); ++g)
+    game_unpack(c->st_pool.data() + g * kGameBytes, &c->p_env.games[g]);
+  c->idx_bound = false;
+  c->restoring = false;
+  return DDQ_OK;
 }
 
 }  // extern "C"

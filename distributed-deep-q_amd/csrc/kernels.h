@@ -447,6 +447,21 @@ hipError_t launch_prio_set(const PrioTree& t, const int32_t* idx, const uint32_t
                            hipStream_t s);
 // fill n floats with 1.0f (the weights of a host-given minibatch)
 hipError_t launch_fill_ones(float* dst, int n, hipStream_t s);
+// the sums bottom-up and the total from the leaves as they are (ddq_state_commit)
+hipError_t launch_prio_resum(const PrioTree& t, hipStream_t s);
+
+// Checkpoint and resume (state.hip, ddq_state_*).
+constexpr int kStateThreads = 256;
+constexpr int kStateParts = 2048;   // the digest launch's workgroups at most: its partials
+// *out <- the digest (include/ddq_hip.h) of the n bytes at p, an allocation's
+// base (16-byte aligned); part: kStateParts words of scratch.  Two launches.
+hipError_t launch_state_digest(const void* p, uint64_t n, uint64_t* part, uint64_t* out,
+                               hipStream_t s);
+// bad[0] += the leaves that are above 2^24 or break "q == 0 <=> slot unfilled or
+// forbidden" under (head, valid, nstep) per lane of lane_len slots; bad[1] = min
+// with the lowest such slot
+hipError_t launch_state_check_leaves(const PrioTree& t, int64_t lane_len, int64_t head,
+                                     int64_t valid, int nstep, int32_t* bad, hipStream_t s);
 
 double step_flops(int B, int S);
 

@@ -74,6 +74,19 @@ hipError_t launch_prio_rebuild(const PrioTree& t, const ReplayMeta* meta, hipStr
   return hipSuccess;
 }
 
+// the rebuild's sum passes alone, over leaves written by ddq_state_write
+hipError_t launch_prio_resum(const PrioTree& t, hipStream_t s) {
+  if (!t.leaf || t.nlev < 1 || t.nlev > kPrioLevels) return hipErrorInvalidValue;
+  for (int k = 1; k <= t.nlev; ++k) {
+    ddq_launch(prio_rebuild_level_kernel, dim3((uint32_t)((t.padded[k] + 255) / 256)), dim3(256), 0,
+               s, t, k);
+    CHECK_LAUNCH(hipGetLastError());
+  }
+  ddq_launch(prio_rebuild_root_kernel, dim3(1), dim3(64), 0, s, t);
+  CHECK_LAUNCH(hipGetLastError());
+  return hipSuccess;
+}
+
 // ---- the stratified draw: thread j < B descends for sample j ----
 // One node's 64 children: the first child whose inclusive prefix exceeds u.
 // The loads of a chunk are independent and issued together, so a level costs a

@@ -83,6 +83,27 @@ class AdamCfg(ctypes.Structure):
                 ("eps", ctypes.c_float), ("max_grad_norm", ctypes.c_float)]
 
 
+class StateSection(ctypes.Structure):
+    """include/ddq_hip.h ddq_state_section (32 bytes)."""
+    _fields_ = [("name", ctypes.c_char * 16), ("bytes", ctypes.c_int64),
+                ("digest", ctypes.c_uint64)]
+
+
+# include/ddq_hip.h ddq_state_config (64 bytes) and ddq_state_counters (96 bytes)
+STATE_CONFIG_DTYPE = np.dtype([
+    ("batch", "<i2"), ("frame", "<i2"), ("gamma_bits", "<u4"), ("capacity", "<i8"),
+    ("lanes", "<i4"), ("nstep", "u1"), ("prio_enabled", "u1"), ("obj_target", "u1"),
+    ("obj_loss", "u1"), ("prio_alpha", "<f4"), ("prio_beta", "<f4"), ("prio_eps", "<f4"),
+    ("huber_delta", "<f4"), ("adam_on", "u1"), ("actor", "u1"), ("pool_games", "<i2"),
+    ("adam_beta1", "<f4"), ("adam_beta2", "<f4"), ("adam_eps", "<f4"),
+    ("adam_max_grad_norm", "<f4"), ("target_tau", "<f4")])
+STATE_COUNTERS_DTYPE = np.dtype([
+    ("iteration", "<i8"), ("steps", "<i8"), ("head", "<i8"), ("valid", "<i8"), ("draws", "<u8"),
+    ("batch_ctr", "<u8"), ("pool_h0", "<i8"), ("pool_v0", "<i8"), ("pool_moves", "<i8"),
+    ("opt_init", "<i4"), ("ring_err", "<i4"), ("pmax", "<u4"), ("reserved", "<i4", (3,))])
+assert STATE_CONFIG_DTYPE.itemsize == 64 and STATE_COUNTERS_DTYPE.itemsize == 96
+STATE_GAME_BYTES = 544     # one game of the "actor" / "pool" sections
+
 PRIO_ONE, PRIO_MAX = 1 << 16, 1 << 24      # a leaf of 1.0; the largest leaf
 TARGETS = {"max": 0, "double": 1}          # include/ddq_hip.h enum ddq_target
 LOSSES = {"euclidean": 0, "huber": 1}      # include/ddq_hip.h enum ddq_loss
@@ -193,6 +214,12 @@ _SIGS = {
     "ddq_monitor_enable": (ctypes.c_int, [_P, _i64, _i32]),
     "ddq_monitor_record_async": (ctypes.c_int, [_P, _i64]),
     "ddq_monitor_read": (ctypes.c_int, [_P, _i64, _i64, _P, ctypes.POINTER(_i64)]),
+    "ddq_state_sections": (ctypes.c_int, [_P, ctypes.POINTER(StateSection), _i32,
+                                          ctypes.POINTER(_i32)]),
+    "ddq_state_read": (ctypes.c_int, [_P, ctypes.c_char_p, _i64, _P, _i64]),
+    "ddq_state_write": (ctypes.c_int, [_P, ctypes.c_char_p, _i64, _P, _i64]),
+    "ddq_state_commit": (ctypes.c_int, [_P]),
+    "ddq_state_digest": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_u64)]),
     "ddq_profile_step": (ctypes.c_int, [_P, ctypes.POINTER(StepCfg), _P, _fp, _i32,
                                         ctypes.POINTER(_i32)]),
     "ddq_time_layer": (ctypes.c_int, [_P, ctypes.c_char_p, _i32, _fp]),

@@ -2,7 +2,8 @@
 with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
-reset_log=False, objective=None, n_step=None, priority=None, target_tau=None)``:
+reset_log=False, objective=None, n_step=None, priority=None, target_tau=None,
+checkpoint=None, checkpoint_every=0, resume=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -27,7 +28,13 @@ reset_log=False, objective=None, n_step=None, priority=None, target_tau=None)``:
   updates (``DeepQNet.set_target_tau``), set on the net's context: every target
   sync of a step taken there (``DeviceActor.act_and_train``, an actor pool's
   steps) then blends, P <- P + tau (Q - P).  The construction's own P <- Q stays
-  a copy (it defines P).
+  a copy (it defines P);
+* ``checkpoint`` / ``checkpoint_every`` -- a file ``maybe_checkpoint()`` rewrites
+  (atomically) whenever the iteration is a multiple of ``checkpoint_every``: the
+  context's whole training state (``DeepQNet.save_checkpoint``) plus the
+  worker's iteration and index-draw state;
+* ``resume`` -- a checkpoint to continue from, loaded once the dataset is added
+  (``load_checkpoint``); the net then steps exactly as its writer would have.
 
 The input buffers ``state``, ``action``, ``reward``, ``next_state``,
 ``non_terminal`` have the reference's shapes (baristanet.py:30-34).  They are
@@ -71,6 +78,17 @@ def parse_architecture(architecture):
     return batch, h, gamma
 
 
+def step_cfg_dict(cfg):
+    """A ``DeepQNet.step_cfg`` (or a dict) as a JSON-able dict."""
+    if isinstance(cfg, dict):
+        return dict(cfg)
+    u = cfg.update
+    return {"rule": int(u.rule), "lr": float(u.lr), "decay": float(u.decay), "eps": float(u.eps),
+            "momentum": float(u.momentum), "weight_decay": float(u.weight_decay),
+            "target_period": int(cfg.target_period), "exchange": int(cfg.exchange),
+            "seed": int(cfg.seed), "overlap": int(cfg.overlap), "flags": int(cfg.flags)}
+
+
 class _Blob:
     """pycaffe-like blob view: ``.data`` / ``.diff`` numpy arrays."""
 
@@ -81,7 +99,8 @@ class _Blob:
 class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
                  reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
-                 priority=None, target_tau=None):
+                 priority=None, target_tau=None, checkpoint=None, checkpoint_every=0,
+                 resume=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
@@ -119,6 +138,9 @@ class BaristaNet:
         self.non_terminal = np.zeros((B, 1, 1, 1), np.float32)
         self.batch_size = B
         self.iteration = 0
+        self.checkpoint = checkpoint
+        self.checkpoint_every = int(checkpoint_every or 0)
+        self._resume = resume
         if dataset is not None:
             self.add_dataset(dataset)
 
@@ -148,6 +170,56 @@ class BaristaNet:
         if self.priority is not None:
             dset.set_priority(self.priority)
         self.dataset = dset
+        if self._resume and not self._resume_deferred:
+            self.load_checkpoint(self._resume)
+
+    # ----------------------------------------------------------- checkpoints
+    # ``resume=PATH`` loads at the first add_dataset: the ring must exist and be
+    # configured as the writer's was.  A worker that also creates a device actor
+    # or pool on the context (after the dataset: they need the ring) defers the
+    # load with ``defer_resume()`` and calls ``load_checkpoint`` itself once the
+    # actor exists, as barista/main.py does.
+    _resume_deferred = False
+
+    def defer_resume(self):
+        self._resume_deferred = True
+
+    def save_checkpoint(self, path=None, step_cfg=None):
+        """The context's whole training state (``DeepQNet.save_checkpoint``) with
+        the worker's own: the iteration, the prioritized draws' seed, Python's
+        ``random`` state (the reference's host index draws) and, when given, the
+        step cfg as a dict."""
+        path = path or self.checkpoint
+        if not path:
+            raise ValueError("no checkpoint path")
+        st = random.getstate()
+        meta = {"iteration": int(self.iteration), "per_seed": int(self.per_seed),
+                "py_random": [st[0], list(st[1]), st[2]]}
+        if step_cfg is not None:
+            meta["step_cfg"] = step_cfg_dict(step_cfg)
+        self.dqn.save_checkpoint(path, meta)
+        return path
+
+    def load_checkpoint(self, path):
+        """Restore the context from ``path`` and the worker's own state from its
+        meta; returns the meta."""
+        meta = self.dqn.load_checkpoint(path)
+        self.iteration = int(meta.get("iteration", self.iteration))
+        self.per_seed = int(meta.get("per_seed", self.per_seed))
+        if "py_random" in meta:
+            v, words, gauss = meta["py_random"]
+            random.setstate((v, tuple(words), gauss))
+        self._resume = None
+        return meta
+
+    def maybe_checkpoint(self, step_cfg=None):
+        """Write ``checkpoint`` when the iteration is a multiple of
+        ``checkpoint_every`` (the worker calls this once per step); True if it did."""
+        if not self.checkpoint or self.checkpoint_every <= 0 or \
+                self.iteration % self.checkpoint_every:
+            return False
+        self.save_checkpoint(step_cfg=step_cfg)
+        return True
 
     # --------------------------------------------------------------- inputs
     def push_inputs(self):

@@ -85,6 +85,7 @@ def process_connection(sock, net, exp_gain, debug=False):
             print("Loss:", netutils.extract_net_data(net, ("loss",))["loss"])
         response = net.send_gradient_update()
         net.log()
+        net.maybe_checkpoint()
         sock.sendall(response if isinstance(response, bytes) else str(response).encode())
     elif message == DARWIN_UPDATE:
         raise NotImplementedError("Darwinian SGD not implemented")
@@ -133,7 +134,19 @@ def get_args(argv=None):
                     help="prioritized replay: importance-sampling exponent in [0, 1] (default 0.4)")
     ap.add_argument("--per-eps", dest="per_eps", type=float, default=None,
                     help="prioritized replay: priority floor, > 0 (default 0.01)")
+    ap.add_argument("--checkpoint", default=None,
+                    help="file the whole training state is written to (atomically) every "
+                         "--checkpoint-every steps")
+    ap.add_argument("--checkpoint-every", dest="checkpoint_every", type=int, default=0,
+                    help="steps between checkpoints (default 0: none)")
+    ap.add_argument("--resume", default=None,
+                    help="checkpoint to continue from; the worker must be started with the "
+                         "options of the run that wrote it")
     args = ap.parse_args(argv)
+    if args.checkpoint_every < 0:
+        ap.error("--checkpoint-every must be >= 0")
+    if args.checkpoint_every and not args.checkpoint:
+        ap.error("--checkpoint-every needs --checkpoint")
     if args.per_alpha is None and (args.per_beta is not None or args.per_eps is not None):
         ap.error("--per-beta / --per-eps need --per-alpha")
     if args.per_alpha is not None and not 0.0 <= args.per_alpha <= 1.0:
@@ -181,7 +194,13 @@ def build_worker(args):
     model = None if args.model in ("none", "None") else args.model
     net = BaristaNet(args.architecture, model, args.driver,
                      logpath=getattr(args, "logpath", None), mode=args.mode,
-                     objective=objective_of(args), target_tau=getattr(args, "target_tau", None))
+                     objective=objective_of(args), target_tau=getattr(args, "target_tau", None),
+                     checkpoint=getattr(args, "checkpoint", None),
+                     checkpoint_every=getattr(args, "checkpoint_every", 0))
+    # --resume: loaded below, once everything the checkpoint holds exists on the
+    # context (the ring, and the device actor when there is one); the initial
+    # replay fill is the checkpoint's then
+    resume = getattr(args, "resume", None)
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
                            overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode,
                            n_step=getattr(args, "n_step", 1), priority=priority_of(args))
@@ -192,12 +211,16 @@ def build_worker(args):
         from ..actor import DeviceActor
         seed = args.actor_seed if args.actor_seed is not None else random.getrandbits(64)
         exp_gain = DeviceActor(net, game.encode_state(), seed, preprocessor=pre)
-        if args.overwrite:                              # main.py:176-178
+        if resume:                                      # the actor's game and stream too
+            net.load_checkpoint(resume)
+        elif args.overwrite:                            # main.py:176-178
             exp_gain.fill(min(args.initial_replay, args.dset_size))
         return net, replay, exp_gain
     exp_gain = eg.ExpGain(net, ["w", "a", "s", "d"], pre, game.cpu_play, replay,
                           game.encode_state())
-    if args.overwrite:                                  # main.py:176-178
+    if resume:       # (the host ExpGain's game is not device state: it starts a new game)
+        net.load_checkpoint(resume)
+    elif args.overwrite:                                # main.py:176-178
         for _ in range(min(args.initial_replay, args.dset_size)):
             exp_gain.generate_experience(0)
     return net, replay, exp_gain

@@ -628,6 +628,29 @@ class DeepQNet:
         self._check(self.lib.ddq_read_indices(self.ctx, ptr(out), self.batch))
         return out
 
+    # -------------------------------------------------------------- checkpoint
+    def save_checkpoint(self, path, meta=None):
+        """Write the whole training state -- both towers, the optimizer state,
+        every counter, the ring, the priorities, the actors' games -- to one
+        file, atomically (ddq.checkpoint).  ``meta``: a JSON-able dict kept in
+        the header."""
+        from . import checkpoint
+        return checkpoint.save(self, path, meta)
+
+    def load_checkpoint(self, path):
+        """Restore a net configured as the writer was (ring, lanes, n-step,
+        priority, objective, Adam, tau, actor or pool) from ``path``; it then
+        continues exactly as the writer would have.  Raises
+        ``ddq.checkpoint.CheckpointError``; returns the writer's ``meta``.
+        ``ddq.checkpoint.restore`` builds the net from the file as well."""
+        from . import checkpoint
+        return checkpoint.load(self, path)
+
+    def state_sections(self):
+        """[(name, bytes, digest)] of the state's sections (ddq_state_sections)."""
+        from . import checkpoint
+        return checkpoint.state_sections(self)
+
     # -------------------------------------------------------------------- step
     def step_cfg(self, rule="rmsprop", lr=1e-4, target_period=10, allreduce=False, seed=0,
                  exchange=None, overlap=False, store_grads=True, **kw):

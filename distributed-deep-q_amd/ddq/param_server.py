@@ -25,6 +25,10 @@ Semantics kept:
   the device-resident monitor (the RMS of every blob of the model just applied
   and of the gradient just pushed, tagged with the iteration) is handed to
   ``on_stats(iteration, record)``.
+Beside the snapshots (theta_Q only), ``checkpoint_path`` / ``checkpoint_freq``
+write the server's whole state -- both towers, the optimizer state, the
+iteration (``DeepQNet.save_checkpoint``) -- every that many iterations, and
+``resume=PATH`` continues from such a file bit for bit.
 The apply runs in ``apply_kernel`` on the device (``ddq_set_grads`` +
 ``ddq_apply``), not in numpy.
 """
@@ -50,7 +54,8 @@ def get_snapshot_name(iteration):
 class ParamServer:
     def __init__(self, frame=16, batch=32, update="rmsprop", lr=1e-4, rmsprop_decay=0.9,
                  special_update=10, snapshot_freq=500, stats_freq=500, device=0,
-                 on_snapshot=None, mode="gpu", on_stats=None, adam=None, target_tau=None):
+                 on_snapshot=None, mode="gpu", on_stats=None, adam=None, target_tau=None,
+                 checkpoint_path=None, checkpoint_freq=0, resume=None):
         if update not in ("sgd", "rmsprop", "adagrad", "adam"):
             raise ValueError("update must be one of adagrad, adam, rmsprop, sgd")
         self.net = DeepQNet(batch=batch, frame=frame, device=device, mode=mode)
@@ -80,6 +85,38 @@ class ParamServer:
         self.has_model = False
         self.has_target = False
         self.model_lock = threading.Lock()
+        # no reference counterpart (its snapshots keep theta_Q only): every
+        # checkpoint_freq iterations the whole server state -- both towers, the
+        # optimizer state, the iteration -- goes to checkpoint_path, atomically;
+        # resume: continue from such a file, exactly
+        self.checkpoint_path = checkpoint_path
+        self.checkpoint_frequency = int(checkpoint_freq or 0)
+        if resume:
+            self.load_checkpoint(resume)
+
+    def save_checkpoint(self, path=None):
+        """The server's whole state to ``path`` (default: ``checkpoint_path``).
+        The caller holds ``model_lock`` or is the only thread."""
+        path = path or self.checkpoint_path
+        if not path:
+            raise ValueError("no checkpoint path")
+        self.net.save_checkpoint(path, meta={
+            "iteration": int(self.iteration), "has_model": bool(self.has_model),
+            "has_target": bool(self.has_target),
+            "step_cfg": {"rule": self.update, "lr": self.learning_rate,
+                         "decay": self.rmsprop_decay,
+                         "target_period": self.special_update_period}})
+        return path
+
+    def load_checkpoint(self, path):
+        """Continue from a checkpoint written by a server configured like this
+        one (frame, batch, update rule's Adam constants, target_tau)."""
+        with self.model_lock:
+            meta = self.net.load_checkpoint(path)
+            self.iteration = int(meta.get("iteration", 0))
+            self.has_model = bool(meta.get("has_model", True))
+            self.has_target = bool(meta.get("has_target", False))
+        return meta
 
     # server.py:218-257 initParams(reset=True)
     def init_params(self, params=None, seed=42):
@@ -138,6 +175,9 @@ class ParamServer:
             if self.snapshot_frequency and self.iteration % self.snapshot_frequency == 0 \
                     and self.on_snapshot is not None:
                 self.on_snapshot(get_snapshot_name(self.iteration), self.model_params())
+            if self.checkpoint_path and self.checkpoint_frequency and \
+                    self.iteration % self.checkpoint_frequency == 0:
+                self.save_checkpoint()
             if self.on_stats is not None and self.stats_frequency and \
                     self.iteration % self.stats_frequency == 0:
                 self.net.monitor_record(self.iteration)

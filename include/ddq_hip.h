@@ -59,7 +59,10 @@ extern "C" {
                               likewise; and the Adam rule (DDQ_RULE_ADAM, ddq_set_adam,
                               ddq_get_adam, ddq_adam_state; blob "grad_norm"),
                               likewise; and soft target updates (ddq_set_target_tau,
-                              ddq_get_target_tau, ddq_soft_sync_target), likewise */
+                              ddq_get_target_tau, ddq_soft_sync_target), likewise; and
+                              checkpoint and resume (ddq_state_sections, ddq_state_read,
+                              ddq_state_write, ddq_state_commit, ddq_state_digest),
+                              likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -766,6 +769,119 @@ int ddq_monitor_record_async(ddq_ctx* ctx, int64_t tag);
  * otherwise).  out may be NULL with n == 0. */
 int ddq_monitor_read(ddq_ctx* ctx, int64_t first, int64_t n, ddq_monitor_record* out,
                      int64_t* total);
+
+/* ---------------- checkpoint and bit-exact resume ----------------------- */
+/* The whole training state of a ctx as named byte sections, so that a ctx
+ * restored from them continues exactly -- bit for bit, draw for draw -- as the
+ * ctx that was read.  No reference counterpart (the reference persists the
+ * ring's HDF5 file and the model snapshots only).
+ *
+ * Sections, in this fixed order; a section is listed only when what it holds
+ * exists on the ctx:
+ *   "config"       64                    ddq_state_config: a fingerprint, not state
+ *   "theta_q"      4 P                   the flat Q tower, as ddq_get_params(0)
+ *   "theta_p"      4 P                   the flat P tower
+ *   "opt"          4 P                   the state word every rule uses (Adam: m); under
+ *                                        a sharded exchange the rank's own buffer
+ *   "opt2"         4 P                   Adam's v (once ddq_set_adam was called)
+ *   "counters"     96                    ddq_state_counters
+ *   "ring_state"   capacity 4 S S        the ring's arrays in slot order, as
+ *   "ring_action"  capacity              ddq_replay_export writes them (once
+ *   "ring_reward"  2 capacity            ddq_replay_create was called)
+ *   "ring_nonterm" capacity
+ *   "prio_leaf"    4 capacity            the leaves (while prioritization is on);
+ *                                        the sums are derived and not stored
+ *   "actor"        544                   the single actor's game (ddq_actor_create)
+ *   "pool"         544 games             the pool's games (ddq_actors_create)
+ * A game is: uint64 seed, draws; int64 steps, games ended, reward sum; int8
+ * boards[5][100] (the 4-frame history, oldest first, then the start board); 4
+ * zero bytes.  The zoom maps come from the create call.
+ *
+ * NOT state: the evaluator (ddq_eval_*: create it again), the monitor ring, the
+ * index log, captured graphs, the small-map step's meeting counters,
+ * communicators and groups, the gradient buffer and every blob, and the bound
+ * minibatch: after ddq_state_commit none is bound (ddq_replay_update_priorities_async
+ * returns DDQ_ESTATE until the next draw) and the step modes draw their own.
+ *
+ * Reading.  ddq_state_sections synchronises the ctx's streams, computes every
+ * section's digest on the device and fills out[0..*n) (out == NULL: *n only;
+ * cap < *n: DDQ_EINVAL).  ddq_state_read copies bytes [offset, offset + bytes)
+ * of a section to the host: a ring of any size goes to disk through a small
+ * staging buffer.  ddq_state_digest: one section's digest.
+ *
+ * Digest of a section of n bytes: w_k = the little-endian uint64 of bytes
+ * 8k .. 8k+7, zero-padded past n; K = ceil(n / 8);
+ *   digest = splitmix64(n) + sum_{k<K} splitmix64(w_k ^ ((k + 1) * 0x9E3779B97F4A7C15))
+ * every operation mod 2^64, splitmix64 the hash of the index draws.  The sum
+ * wraps, so it is the same in any order; it is not cryptographic: it catches
+ * torn or corrupted files and lets two ctxs or ranks compare their state
+ * without copying it.
+ *
+ * Restoring.  The caller first configures a ctx as the writer was configured,
+ * with the existing calls (create, ring, lanes, n-step, priority, objective,
+ * Adam, tau, actor or pool), then writes the sections and commits:
+ *  - writing "config" compares it with the ctx and changes nothing; on a
+ *    difference DDQ_EINVAL, the message names the first differing field;
+ *  - writing any other section needs bytes > 0 and [offset, offset + bytes)
+ *    inside the section (DDQ_EINVAL otherwise; nothing is written);
+ *  - from the first such write on the ctx is "restoring": every call that
+ *    launches work reading the state (the step modes, ddq_forward_backward,
+ *    ddq_forward_q, ddq_select_action, the applies, the actor, pool and
+ *    evaluator steps, the replay samplers and adds) returns DDQ_ESTATE
+ *    ("restore not committed") until ddq_state_commit succeeds;
+ *  - "counters" written while restoring is held on the host until the commit
+ *    (ddq_state_read returns what was written).
+ * ddq_state_commit validates the counters against the ring (head < lane_len,
+ * valid <= lane_len, counts >= 0, reserved == 0, pmax in [65536, 2^24] while
+ * prioritization is on) and the leaves (every leaf 0 or in [1, 2^24], and the
+ * invariant q[i] == 0 <=> slot unfilled or forbidden under the restored head,
+ * valid and n); on a failure DDQ_EINVAL and the ctx stays restoring.  Then it
+ * pushes the counters to device memory and the host mirrors, rebuilds both
+ * towers' derived conv-weight copies, the sum tree's levels and total from the
+ * leaves (exact integers: order does not matter) and the actors' rendered
+ * states, and drops every captured graph.  Without a preceding write it is a
+ * no-op.
+ * While the async exchange has begun every state call returns DDQ_ESTATE (the
+ * central model lives in the owners' shards).  Members of a communicator or a
+ * group are fine: each rank writes its own file. */
+typedef struct ddq_state_section { char name[16]; int64_t bytes; uint64_t digest; } ddq_state_section; /* 32 B */
+
+typedef struct ddq_state_config {   /* 64 bytes, no padding */
+  int16_t  batch, frame;            /* ddq_net_desc                                  */
+  uint32_t gamma_bits;              /* ddq_net_desc.gamma's bits                     */
+  int64_t  capacity;                /* ring capacity; 0: no ring                     */
+  int32_t  lanes;                   /* 1 without a ring                              */
+  uint8_t  nstep;                   /* 1 without a ring                              */
+  uint8_t  prio_enabled;            /* 0 / 1                                         */
+  uint8_t  obj_target, obj_loss;    /* enum ddq_target, enum ddq_loss                */
+  float    prio_alpha, prio_beta, prio_eps;   /* 0 while prioritization is off       */
+  float    huber_delta;             /* 0 unless DDQ_LOSS_HUBER                       */
+  uint8_t  adam_on;                 /* ddq_set_adam was called                       */
+  uint8_t  actor;                   /* ddq_actor_create was called (0 / 1)           */
+  int16_t  pool_games;              /* ddq_actors_create's games; 0: no pool         */
+  float    adam_beta1, adam_beta2, adam_eps, adam_max_grad_norm;   /* 0 unless adam_on */
+  float    target_tau;
+} ddq_state_config;                 /* floats are compared by their bits             */
+
+typedef struct ddq_state_counters { /* 96 bytes, no padding */
+  int64_t  iteration;               /* the device iteration counter (Adam's t)       */
+  int64_t  steps;                   /* ddq_step_count                                */
+  int64_t  head, valid;             /* the ring's (per lane on a laned ring); 0 without */
+  uint64_t draws;                   /* the ring's draw counter (ddq_replay_draws)    */
+  uint64_t batch_ctr;               /* the large-batch sampler's counter             */
+  int64_t  pool_h0, pool_v0;        /* the pool's ring head / valid at its create    */
+  int64_t  pool_moves;              /* the pool's moves since                        */
+  int32_t  opt_init;                /* 0 until the first apply after a reset, then 1 */
+  int32_t  ring_err;                /* the ring's sticky error (ddq_replay_status)   */
+  uint32_t pmax;                    /* prioritized replay's pmax; 0 while it is off  */
+  int32_t  reserved[3];             /* 0 */
+} ddq_state_counters;
+
+int ddq_state_sections(ddq_ctx* ctx, ddq_state_section* out, int32_t cap, int32_t* n);
+int ddq_state_read(ddq_ctx* ctx, const char* name, int64_t offset, void* dst, int64_t bytes);
+int ddq_state_write(ddq_ctx* ctx, const char* name, int64_t offset, const void* src, int64_t bytes);
+int ddq_state_commit(ddq_ctx* ctx);
+int ddq_state_digest(ddq_ctx* ctx, const char* name, uint64_t* digest);
 
 /* ---------------- measurement ------------------------------------------ */
 /* Kernel ids for ddq_profile_step. */
