@@ -30,6 +30,9 @@ static_assert(sizeof(MonitorRecord) == sizeof(ddq_monitor_record) && sizeof(Moni
 
 static thread_local std::string g_last_error;
 
+// the largest frame side: launch_wgrads_conv23 (wgrads.h) has forms for conv2
+// maps up to 64 x 64
+static constexpr int kMaxFrame = 128;
 static constexpr int kMaxRanks = 64;
 static constexpr int64_t kShardPad = 64 * kMaxRanks;
 
@@ -335,14 +338,37 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* desc) {
                 desc->frame);
   if (desc->batch < 1 || desc->batch > 1024)
     return fail(nullptr, DDQ_EINVAL, "batch must be in [1,1024] (got %d)", desc->batch);
-  // the kernels address every tensor through 32-bit buffer descriptors /
-  // offsets (kOOB = 2^31 marks an out-of-range vector): the largest ones are
-  // a split activation plane (16 B S^2 bytes) and fc4's weights (2^11 S^2)
+  // The kernels address every tensor through 32-bit buffer descriptors and
+  // offsets, and give an out-of-image vector the offset kOOB = 2^31, which
+  // reads 0 only while it is >= the descriptor's num_records.  The largest
+  // extents, in bytes (tests/_limit_shapes.py has the whole table):
+  //   fp32 pool1 (conv2 forward's source, one descriptor)        32 B S^2
+  //   the three split planes of pool1 (conv2 forward's side
+  //     output for the weight gradient, one descriptor)          48 B S^2
+  //   the three split planes of dpool2 (conv2 data gradient)     24 B S^2
+  //   conv1's weight-gradient slabs (stores only, one
+  //     descriptor, 32 KB a tile of conv2's data gradient)       64 B S^2 (8 x 16 tiles)
+  //   fc4's weights                                              2^11 S^2
+  // This guard bounds a split plane (16 B S^2) and W4 only: alone it would let
+  // pool1 pass 2^31 from B S^2 = 2^26 on (kOOB then lies inside it and a halo
+  // vector reads another image) and the slab and 48 B S^2 descriptors wrap
+  // 2^32.  The frame limit below is what keeps them in range: with S <= 128
+  // and B <= 1024, B S^2 <= 2^24, so pool1 is at most 2^29 bytes, the three
+  // pool1 planes 3 * 2^28, the slabs 2^30 (2^31 if every map took 8 x 8
+  // tiles), W4 2^25: every descriptor that is read through stays below kOOB.
   if ((int64_t)16 * desc->batch * desc->frame * desc->frame >= (1ll << 31) ||
       (int64_t)2048 * desc->frame * desc->frame >= (1ll << 31))
     return fail(nullptr, DDQ_EINVAL,
                 "batch * frame^2 too large for 32-bit tensor offsets (need 16*B*S^2 < 2^31 "
                 "and S < 1024; got B=%d, S=%d)", desc->batch, desc->frame);
+  // conv2's and conv3's weight gradients (wgrads.h) stage whole map rows in
+  // LDS, one region per wave: maps wider than 64 do not fit, and the backward
+  // pass of a frame past 128 used to end in hipErrorInvalidValue after its
+  // first launches.  Such a context could act but never train: refused here.
+  if (desc->frame > kMaxFrame)
+    return fail(nullptr, DDQ_EINVAL,
+                "frame side %d not supported: the backward pass handles frames up to %d (the "
+                "conv weight gradients stage whole map rows in LDS)", desc->frame, kMaxFrame);
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev == 0)

@@ -176,7 +176,10 @@ typedef struct ddq_step_cfg {
 
 /* ---------------- context ---------------------------------------------- */
 /* caffe.Net(prototxt, model) + set_mode_gpu + set_phase_test
- * (baristanet.py:16, main.py:147-151).  Dropout is identity (TEST phase). */
+ * (baristanet.py:16, main.py:147-151).  Dropout is identity (TEST phase).
+ * DDQ_EINVAL unless desc->frame is a multiple of 8 in [16, 128] (the backward
+ * pass has no form for wider maps) and desc->batch is in [1, 1024]; checked
+ * before any device is looked for. */
 int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* desc);
 int ddq_destroy(ddq_ctx* ctx);
 const char* ddq_last_error(const ddq_ctx* ctx);

@@ -65,7 +65,9 @@ def test_abi_version(lib):
 def test_create_rejects_sizes_past_32bit_offsets(lib, batch, frame, ok):
     """ddq_create refuses shapes whose tensors exceed the kernels' 32-bit
     buffer offsets (16 B S^2 and 2^11 S^2 bytes < 2^31), before it looks for
-    a device: those sizes fail with DDQ_EINVAL on any host."""
+    a device: those sizes fail with DDQ_EINVAL on any host.  (ok: not refused
+    for that reason.  The frame limit below refuses (1024, 256) and (128, 1016)
+    as well, with its own message.)"""
     from ddq import _lib
     desc = _lib.NetDesc(batch, frame, 4, 4, 0.85)
     ctx = ctypes.c_void_p()
@@ -77,6 +79,26 @@ def test_create_rejects_sizes_past_32bit_offsets(lib, batch, frame, ok):
     else:
         assert rc == _lib.DDQ_EINVAL
         assert b"32-bit" in lib.ddq_last_error(None)
+
+
+@pytest.mark.parametrize("batch,frame,ok", [(1024, 128, True), (1, 128, True), (1, 136, False),
+                                            (1024, 256, False), (128, 1016, False)])
+def test_create_rejects_frames_the_backward_pass_cannot_run(lib, batch, frame, ok):
+    """Frames past 128 are refused (the conv weight gradients stage whole map
+    rows in LDS; maps wider than 64 do not fit), before any device is looked
+    for.  (1024, 128) is the corner of the accepted domain:
+    tests/test_gpu_limit_shapes.py runs it."""
+    from ddq import _lib
+    desc = _lib.NetDesc(batch, frame, 4, 4, 0.85)
+    ctx = ctypes.c_void_p()
+    rc = lib.ddq_create(ctypes.byref(ctx), 0, ctypes.byref(desc))
+    if ok:
+        assert rc != _lib.DDQ_EINVAL, lib.ddq_last_error(None)
+        if rc == 0:
+            lib.ddq_destroy(ctx)
+    else:
+        assert rc == _lib.DDQ_EINVAL
+        assert b"frames up to 128" in lib.ddq_last_error(None)
 
 
 def test_no_gpu_fails_loudly(lib):
