@@ -97,6 +97,7 @@ struct ddq_ctx {
   // selectable objective (ddq_set_objective) and its two blobs
   ddq_objective obj{DDQ_TARGET_MAX, DDQ_LOSS_EUCLIDEAN, 0.f, 0};
   std::vector<float> qn_out, dq_out;
+  int32_t act_path = DDQ_ACT_BATCH;   // ddq_set_acting_path: stored (one forward here)
   // replay ring (replay.py:23-68)
   std::vector<uint8_t> r_state, r_action, r_nonterm;
   std::vector<int16_t> r_reward;
@@ -1175,6 +1176,21 @@ int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
 int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
   if (!c || !o) return fail(nullptr, DDQ_EINVAL, "null argument");
   *o = c->obj;
+  return DDQ_OK;
+}
+
+// ---- acting path: a choice between the GPU library's kernels; stored ----
+int ddq_set_acting_path(ddq_ctx* c, int32_t path) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (path != DDQ_ACT_BATCH && path != DDQ_ACT_SPREAD && path != DDQ_ACT_AUTO)
+    return fail(c, DDQ_EINVAL, "unknown acting path %d", (int)path);
+  c->act_path = path;
+  return DDQ_OK;
+}
+
+int ddq_get_acting_path(const ddq_ctx* c, int32_t* path) {
+  if (!c || !path) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *path = c->act_path;
   return DDQ_OK;
 }
 

@@ -207,6 +207,8 @@ struct ddq_ctx {
   std::vector<Mark> marks;
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
+  // ddq_set_acting_path: which convs every launch_act of the ctx launches
+  int32_t act_path = DDQ_ACT_BATCH;
 };
 
 static int fail(ddq_ctx* c, int code, const char* fmt, ...) {
@@ -1334,7 +1336,7 @@ static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
   if (nb.obj_target != DDQ_TARGET_DOUBLE) return DDQ_OK;
   const Marks qn = m.fn ? Marks{qn_mark, &m} : Marks{};
   HIP_TRY(c, launch_act(nb, nb.mb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
-                        nullptr, c->act_p1s, c->act_p2s, c->stream, qn));
+                        nullptr, c->act_p1s, c->act_p2s, c->stream, qn, c->act_path));
   return DDQ_OK;
 }
 
@@ -1411,7 +1413,7 @@ int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
     // one run of the extra forward now: its kernels' function attributes are set
     // outside any capture (the result is overwritten by the first pass)
     HIP_TRY(c, launch_act(nb, nb.mb.next_state, nb.B, c->act_p3, c->act_h4, c->act_part, nb.qn_out,
-                          nullptr, c->act_p1s, c->act_p2s, c->stream));
+                          nullptr, c->act_p1s, c->act_p2s, c->stream, {}, c->act_path));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   nb.obj_target = o->target;
@@ -1426,11 +1428,38 @@ int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
   return DDQ_OK;
 }
 
+// ---------------- acting path ----------------
+int ddq_set_acting_path(ddq_ctx* c, int32_t path) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (path != DDQ_ACT_BATCH && path != DDQ_ACT_SPREAD && path != DDQ_ACT_AUTO)
+    return fail(c, DDQ_EINVAL, "unknown acting path %d", (int)path);
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);   // captured steps hold the Qn_out forward's launches
+  NetBuffers& nb = c->nb;
+  c->act_path = path;
+  if (path != DDQ_ACT_BATCH && !nb.small) {
+    // one run at n = 1 and at n = B into the acting scratch: the kernels'
+    // function attributes are set outside any capture
+    for (int n : {1, nb.B})
+      HIP_TRY(c, launch_act(nb, c->act_in, n, c->act_p3, c->act_h4, c->act_part, c->act_q, nullptr,
+                            c->act_p1s, c->act_p2s, c->stream, {}, c->act_path));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return DDQ_OK;
+}
+
+int ddq_get_acting_path(const ddq_ctx* c, int32_t* path) {
+  if (!c || !path) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *path = c->act_path;
+  return DDQ_OK;
+}
+
 int ddq_forward_q(ddq_ctx* c) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(guard(c));
   HIP_TRY(c, launch_act(c->nb, c->nb.mb.state, c->nb.B, c->act_p3, c->act_h4, c->act_part,
-                        c->nb.q_out, nullptr, c->act_p1s, c->act_p2s, c->stream));
+                        c->nb.q_out, nullptr, c->act_p1s, c->act_p2s, c->stream, {}, c->act_path));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;
 }
@@ -1486,7 +1515,7 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
   HIP_TRY(c, hipMemcpyAsync(c->act_u8, states, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, launch_u8_to_nhwc(c->act_u8, n, c->nb.S, c->act_in, c->stream));
   HIP_TRY(c, launch_act(c->nb, c->act_in, n, c->act_p3, c->act_h4, c->act_part, c->act_q,
-                        c->act_out, c->act_p1s, c->act_p2s, c->stream));
+                        c->act_out, c->act_p1s, c->act_p2s, c->stream, {}, c->act_path));
   HIP_TRY(c, hipMemcpyAsync(actions, c->act_out, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;
@@ -1629,7 +1658,7 @@ static int env_create(ddq_ctx* c, EnvBufs<Game>* b, int room, const std::vector<
 template <class Role, class Game>
 static int env_move(ddq_ctx* c, const Role& r, const EnvBufs<Game>& b, uint64_t thresh) {
   HIP_TRY(c, launch_act(c->nb, b.in, b.n, c->act_p3, c->act_h4, c->act_part, c->act_q, nullptr,
-                        c->act_p1s, c->act_p2s, c->stream));
+                        c->act_p1s, c->act_p2s, c->stream, {}, c->act_path));
   HIP_TRY(c, launch_env(r, env_io(c, b), c->act_q, thresh, 1, c->stream));
   return DDQ_OK;
 }

@@ -215,7 +215,8 @@ hipError_t launch_sample_gather(const NetBuffers& nb, const ReplayRing& ring, ui
                                 hipStream_t s);
 hipError_t launch_gather(const NetBuffers& nb, const ReplayRing& ring, hipStream_t s);
 hipError_t launch_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s);
-// only: 0 = every layer, l + 1 = conv layer l alone (ddq_time_layer)
+// only: 0 = every layer, l + 1 = conv layer l alone (ddq_time_layer), -1 = no
+// conv layer: fc4 and the head on a pool3 already written (launch_act)
 hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, Marks M = {},
                           bool out = true, int only = 0);
 // deepq16 (nb.small): K1 (towers + the head's bookkeeping, as launch_head's)
@@ -299,10 +300,17 @@ hipError_t launch_book(const NetBuffers& nb, int period, hipStream_t s);
 hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, int64_t slice,
                              hipStream_t s);
 // Q-tower forward of n states (NHWC f32 in `in`) into scratch, argmax into out.
-// M: the launches' profile names (ddq_profile_step).
+// M: the launches' profile names (ddq_profile_step).  act_path
+// (ddq_set_acting_path): 0 launch_forward's convs, 1 the spread convs
+// (act_spread.h), 2 spread at n <= act_spread_max_n(S).
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s, Marks M = {});
+                      __bf16* pool2s, hipStream_t s, Marks M = {}, int act_path = 0);
+// The three convs of launch_act in their small-n form (act_spread.h): n images
+// of nb.mb.state through nb.pool1f[0] / pool2f[0] into nb.pool3[0]
+hipError_t launch_act_spread_convs(const NetBuffers& nb, int n, hipStream_t s, Marks M);
+// DDQ_ACT_AUTO's crossover: the largest n the spread convs are launched for
+int act_spread_max_n(int S);
 // Device-resident Snake environment (env.h): one kernel body, three roles.
 // ActorState: one acting game.  boards: the 4-frame history of 10x10 board
 // codes [x*10+y] (SnakeGame.encode_state), oldest first, then init_board;

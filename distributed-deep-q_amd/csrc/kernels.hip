@@ -2208,7 +2208,7 @@ hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, Marks M, 
     M("conv3_fwd");
     CHECK_LAUNCH(pick_tile(kConv3Fwd, H, H).launch(a3, nz, s));
   }
-  if (only) return hipSuccess;   // ddq_time_layer: one conv layer
+  if (only > 0) return hipSuccess;   // ddq_time_layer: one conv layer
   // fc4 (train_val.prototxt:159-185): split bf16 MFMA register-direct, split-K
   // partials (reduced by the head kernel, or by fc4_reduce_out below)
   const int s4 = S / 8;
@@ -2579,9 +2579,16 @@ __global__ void argmax_kernel(int n, const float* __restrict__ qout, int32_t* __
   actions[b] = best;
 }
 
+// DDQ_ACT_AUTO's crossover, from the n sweep of profiles/acting_spread.json
+// (forward_q per call, batch against spread on one ctx): spread is the faster
+// through n = 24 at S = 64 (59.4 against 61.2 us; n = 32: 69.7 against 62.0)
+// and through n = 6 at S = 128 (70.1 against 72.5; n = 8: 80.7 against 73.2)
+// -- both n S^2 = 98304 pixels -- and at every n measured (<= 32) at S = 24.
+int act_spread_max_n(int S) { return std::min(32, 98304 / (S * S)); }
+
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s, Marks M) {
+                      __bf16* pool2s, hipStream_t s, Marks M, int act_path) {
   NetBuffers a = nb;
   a.B = n;
   a.mb.state = const_cast<float*>(in);
@@ -2595,7 +2602,12 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
   a.mask1 = a.mask2 = a.mask3 = nullptr;
   a.fc4_part = part;
   a.q_out = qout; a.p_out = qout;
-  CHECK_LAUNCH(launch_forward(a, 1, s, M));
+  // ddq_set_acting_path: the convs spread over the chip (act_spread.h), then
+  // launch_forward's fc4 and head as ever (only = -1: no conv layer)
+  const bool spread = !nb.small && (act_path == 1 ||
+                                    (act_path == 2 && n <= act_spread_max_n(nb.S)));
+  if (spread) CHECK_LAUNCH(launch_act_spread_convs(a, n, s, M));
+  CHECK_LAUNCH(launch_forward(a, 1, s, M, true, spread ? -1 : 0));
   if (actions) {
     M("argmax");
     ddq_launch(argmax_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, qout, actions);

@@ -107,6 +107,7 @@ STATE_GAME_BYTES = 544     # one game of the "actor" / "pool" sections
 PRIO_ONE, PRIO_MAX = 1 << 16, 1 << 24      # a leaf of 1.0; the largest leaf
 TARGETS = {"max": 0, "double": 1}          # include/ddq_hip.h enum ddq_target
 LOSSES = {"euclidean": 0, "huber": 1}      # include/ddq_hip.h enum ddq_loss
+ACTING_PATHS = {"batch": 0, "spread": 1, "auto": 2}   # include/ddq_hip.h enum ddq_acting_path
 STEP_NO_GRAD_STORE = 1     # include/ddq_hip.h DDQ_STEP_NO_GRAD_STORE
 FAULT_NONE, FAULT_MEET_TIMEOUT = 0, 1   # include/ddq_hip.h enum ddq_fault
 NSTEP_MAX = 8              # include/ddq_hip.h DDQ_NSTEP_MAX
@@ -163,6 +164,8 @@ _SIGS = {
     "ddq_forward_q": (ctypes.c_int, [_P]),
     "ddq_set_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
     "ddq_get_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
+    "ddq_set_acting_path": (ctypes.c_int, [_P, _i32]),
+    "ddq_get_acting_path": (ctypes.c_int, [_P, ctypes.POINTER(_i32)]),
     "ddq_read_blob": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _i64]),
     "ddq_read_pool_mask": (ctypes.c_int, [_P, _i32, _P, _i64]),
     "ddq_select_action": (ctypes.c_int, [_P, _P, _i32, _P]),

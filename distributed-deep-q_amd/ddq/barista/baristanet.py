@@ -3,7 +3,7 @@ with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
 reset_log=False, objective=None, n_step=None, priority=None, target_tau=None,
-checkpoint=None, checkpoint_every=0, resume=None)``:
+checkpoint=None, checkpoint_every=0, resume=None, acting_path=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -33,6 +33,10 @@ checkpoint=None, checkpoint_every=0, resume=None)``:
   (atomically) whenever the iteration is a multiple of ``checkpoint_every``: the
   context's whole training state (``DeepQNet.save_checkpoint``) plus the
   worker's iteration and index-draw state;
+* ``acting_path`` -- None (the default "batch") or "batch" / "spread" / "auto":
+  the kernels of every acting forward of the net's context
+  (``DeepQNet.set_acting_path``); "spread" suits a worker that acts on one or
+  a few states at a time;
 * ``resume`` -- a checkpoint to continue from, loaded once the dataset is added
   (``load_checkpoint``); the net then steps exactly as its writer would have.
 
@@ -100,13 +104,15 @@ class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
                  reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
                  priority=None, target_tau=None, checkpoint=None, checkpoint_every=0,
-                 resume=None):
+                 resume=None, acting_path=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
         self.dqn = DeepQNet(batch=batch, frame=frame, device=device, gamma=gamma, mode=mode)
         if objective is not None:
             self.dqn.set_objective(**objective)
+        if acting_path is not None:
+            self.dqn.set_acting_path(acting_path)
         if model is not None and os.path.exists(str(model)):
             with np.load(model, allow_pickle=False) as f:
                 blobs = {k: f[k] for k in f.files}

@@ -9,6 +9,7 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
         [--dset-size 1000] [--overwrite] [--debug] [--initial-replay 20000]
         [--device-actor [--actor-seed N]] [--logpath PREFIX]
         [--double-q] [--huber-delta D] [--target-tau T]
+        [--acting-path batch|spread|auto]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
 step on the host through the CPU twin libddq_cpu.so (main.py:128,149-151, the
@@ -23,6 +24,11 @@ the replay add run inside the net's context (ddq_actor_step_async), so
 objective the gradients are computed for (``DeepQNet.set_objective``): the
 Double-DQN target r + gamma P(s', argmax_a Q(s',a)) in place of the max, and the
 Huber loss with band D in place of the Euclidean one.  Both work in either mode.
+
+``--acting-path`` (default ``batch``) selects the kernels of every acting
+forward of the net's context (``DeepQNet.set_acting_path``): ``spread`` runs a
+worker's one-state acts (the host ``ExpGain`` and ``--device-actor`` alike) on
+kernels that spread one image over the chip.  Stored without effect in cpu mode.
 
 ``--target-tau T`` (default: hard target syncs) sets soft target updates on the
 net's context (``DeepQNet.set_target_tau``), T in (0, 1]: the training steps taken
@@ -126,6 +132,9 @@ def get_args(argv=None):
                     help="Huber loss with this band instead of the Euclidean loss")
     ap.add_argument("--target-tau", dest="target_tau", type=float, default=None,
                     help="soft target updates: P <- P + T (Q - P) at every target sync, T in (0, 1]")
+    ap.add_argument("--acting-path", dest="acting_path", default=None,
+                    choices=("batch", "spread", "auto"),
+                    help="kernels of the acting forward (default batch)")
     ap.add_argument("--n-step", dest="n_step", type=int, default=1,
                     help="N-step returns: the replay gathers N-step windows (default 1)")
     ap.add_argument("--per-alpha", dest="per_alpha", type=float, default=None,
@@ -196,7 +205,8 @@ def build_worker(args):
                      logpath=getattr(args, "logpath", None), mode=args.mode,
                      objective=objective_of(args), target_tau=getattr(args, "target_tau", None),
                      checkpoint=getattr(args, "checkpoint", None),
-                     checkpoint_every=getattr(args, "checkpoint_every", 0))
+                     checkpoint_every=getattr(args, "checkpoint_every", 0),
+                     acting_path=getattr(args, "acting_path", None))
     # --resume: loaded below, once everything the checkpoint holds exists on the
     # context (the ring, and the device actor when there is one); the initial
     # replay fill is the checkpoint's then

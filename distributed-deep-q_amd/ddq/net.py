@@ -230,6 +230,23 @@ class DeepQNet:
         return {"target": names(_lib.TARGETS, o.target), "loss": names(_lib.LOSSES, o.loss),
                 "huber_delta": float(o.huber_delta)}
 
+    def set_acting_path(self, path):
+        """Which convolution kernels the acting forward launches
+        (ddq_set_acting_path) -- forward_q, select_action, the device actor,
+        the pool, the evaluator, the double target's Qn_out pass: "batch" (the
+        default: the training step's forward kernels), "spread" (kernels that
+        spread a handful of images over the whole chip) or "auto" (spread up
+        to a per-frame crossover in n, batch above it)."""
+        if path not in _lib.ACTING_PATHS:
+            raise ValueError("acting path must be one of %s" % (tuple(_lib.ACTING_PATHS),))
+        self._check(self.lib.ddq_set_acting_path(self.ctx, _lib.ACTING_PATHS[path]))
+
+    @property
+    def acting_path(self):
+        v = ctypes.c_int32(0)
+        self._check(self.lib.ddq_get_acting_path(self.ctx, ctypes.byref(v)))
+        return next(k for k, x in _lib.ACTING_PATHS.items() if x == v.value)
+
     def blob(self, name):
         if name not in BLOBS:
             raise KeyError(name)

@@ -62,7 +62,8 @@ extern "C" {
                               ddq_get_target_tau, ddq_soft_sync_target), likewise; and
                               checkpoint and resume (ddq_state_sections, ddq_state_read,
                               ddq_state_write, ddq_state_commit, ddq_state_digest),
-                              likewise */
+                              likewise; and the acting path (ddq_set_acting_path,
+                              ddq_get_acting_path), likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -522,6 +523,23 @@ typedef struct ddq_objective {      /* 16 bytes */
  * the async exchange has begun on the ctx. */
 int ddq_set_objective(ddq_ctx* ctx, const ddq_objective* obj);
 int ddq_get_objective(const ddq_ctx* ctx, ddq_objective* obj);
+
+/* ---------------- acting path (no reference counterpart) ------------------- */
+/* Which convolution kernels the acting forward launches -- ddq_forward_q,
+ * ddq_select_action, the device actor, the actor pool, the evaluator and the
+ * double target's Qn_out pass.  BATCH (the default): the training step's
+ * forward kernels, one workgroup per image and pixel tile, cut for B = 32.
+ * SPREAD: kernels for a handful of images, a workgroup per image, small tile
+ * and slice of 16 output channels (at least 64 workgroups an image at 64 x 64).
+ * AUTO: SPREAD while n is at most a per-frame crossover, BATCH above it.  Both
+ * forms are fp32-exact and deterministic; their Q values agree within the
+ * parity bounds, not bit for bit.  A property of the ctx: not written to
+ * checkpoints.  The call synchronises the stream and drops captured graphs.  On
+ * a small-path ctx (ddq_small_path) it is stored and has no effect: the tower
+ * kernel keeps acting.  DDQ_EINVAL: unknown value. */
+enum ddq_acting_path { DDQ_ACT_BATCH = 0, DDQ_ACT_SPREAD = 1, DDQ_ACT_AUTO = 2 };
+int ddq_set_acting_path(ddq_ctx* ctx, int32_t path);
+int ddq_get_acting_path(const ddq_ctx* ctx, int32_t* path);
 
 /* ---------------- device-resident actor (expgain.py, gamesim/SnakeGame.py) -- */
 /* The worker's "act once, add the transition" (main.py:61-103) without the

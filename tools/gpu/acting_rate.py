@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--preheat-ms", type=float, default=100.0)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--acting-path", dest="acting_path", default="batch",
+                    choices=("batch", "spread", "auto"),
+                    help="kernels of the acting forward (DeepQNet.set_acting_path)")
     args = ap.parse_args()
 
     import bench
@@ -51,6 +54,7 @@ def main():
 
     S, B, n = args.frame, args.batch, args.updates
     net = bench.make_net(B, S, args.replay, 0, 0)
+    net.set_acting_path(args.acting_path)
     cfg = net.step_cfg("rmsprop", lr=1e-4, target_period=10, exchange="none", seed=5)
     actor = DeviceActor(net, SnakeGame().encode_state(), seed=1)
     hot = bench.preheat(B, S, 0, args.preheat_ms)
@@ -86,6 +90,7 @@ def main():
     ra, rb = statistics.median(a), statistics.median(b)
     out = {
         "metric": "acting_rate", "unit": "updates/s", "frame": S, "batch": B,
+        "acting_path": args.acting_path,
         "replay": args.replay, "rule": "rmsprop", "updates_per_loop": n, "warmup": args.warmup,
         "host_actor": {"value": round(ra, 1), "runs": [round(v, 1) for v in a],
                        "loop": "eager step + batch-1 select_action + replay_add per update"},

@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--preheat-ms", type=float, default=100.0)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--acting-path", dest="acting_path", default="batch",
+                    choices=("batch", "spread", "auto"),
+                    help="kernels of the acting forward (DeepQNet.set_acting_path)")
     args = ap.parse_args()
 
     import bench
@@ -56,6 +59,7 @@ def main():
 
     S, B, T = args.frame, args.batch, args.trials
     net = BaristaNet({"batch": B, "frame": S}, None, None)
+    net.dqn.set_acting_path(args.acting_path)
     theta = init_params_flat(S, seed=42)          # bench.make_net's parameters
     net.dqn.set_flat(0, theta)
     net.dqn.set_flat(1, theta)
@@ -115,6 +119,7 @@ def main():
     a = res["host"]["trials_per_s"]
     out = {
         "metric": "eval_rate", "frame": S, "batch": B, "games": B, "trials": T,
+        "acting_path": args.acting_path,
         "max_moves": args.max_moves, "epsilon": args.epsilon, "chunk": args.chunk,
         "average_score": runs["host"][0]["avg"], "same_trials_in_all_runs": same,
         "host": res["host"], "device": res["device"],

@@ -51,6 +51,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--preheat-ms", type=float, default=100.0)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--acting-path", dest="acting_path", default="batch",
+                    choices=("batch", "spread", "auto"),
+                    help="kernels of the acting forward (DeepQNet.set_acting_path)")
     args = ap.parse_args()
 
     import numpy as np
@@ -81,6 +84,8 @@ def main():
     laned.replay_import(st[slot], ac[slot], rw[slot], nt[slot].astype(np.uint8), 0, cap // N)
     del st
     pool = DeviceActorPool(laned, np.stack([init] * N), seed=1)
+    for net in (single, laned):
+        net.set_acting_path(args.acting_path)
 
     cfgs = {net: net.step_cfg("rmsprop", lr=1e-4, target_period=10, exchange="none", seed=5)
             for net in (single, laned)}
@@ -123,6 +128,7 @@ def main():
     keys = ("steps", "games", "reward_sum", "draws")
     out = {
         "metric": "actor_pool_rate", "unit": "updates/s", "frame": S, "batch": B, "rule": "rmsprop",
+        "acting_path": args.acting_path,
         "updates_per_loop": n, "warmup": wrounds * N,
         "device_actor": {"value": round(rb, 1), "runs": [round(v, 1) for v in b],
                          "enqueue_us_per_update": [round(v, 1) for v in enq_b],
