@@ -115,6 +115,8 @@ struct ddq_ctx {
   uint32_t prio_pmax = 65536u;
   uint64_t prio_ctr = 0;           // prioritized draws so far (the draw counter)
   std::vector<float> isw;
+  int32_t aug_pad = 0;             // random-shift augmentation (ddq_replay_set_augment)
+  std::vector<float> aug_shift;    // (B,4): dy_s, dx_s, dy_s', dx_s' of the bound minibatch
   bool idx_bound = false;
   int64_t steps = 0;
   // Snake environments.  A game: its RNG stream and position, its counters, the
@@ -616,6 +618,38 @@ void prio_commit(ddq_ctx* c) {
   }
 }
 
+// Random-shift augmentation (ddq_replay_set_augment): the shift of draw ctr's
+// sample j, side z, as gather_shift.h's aug_shift, and the replicate-padded crop.
+void aug_shift_of(uint64_t seed, uint64_t ctr, int j, int z, int pad, int* dy, int* dx) {
+  const uint64_t r = prio_mix64((seed ^ 0xD1B54A32D192ED03ull) ^
+                                prio_mix64(ctr * 0x100000001B3ull + (uint64_t)(2 * j + z) * 0x9E37ull));
+  const uint32_t w = 2u * (uint32_t)pad + 1u;
+  *dy = (int)(r % w) - pad;
+  *dx = (int)((uint32_t)(r >> 32) % w) - pad;
+}
+
+void shift_frames(ddq_ctx* c, uint64_t seed, uint64_t ctr) {
+  const int B = c->B, S = c->S, SS = S * S;
+  std::vector<float> tmp((size_t)kC * SS);
+  c->aug_shift.assign((size_t)B * 4, 0.f);
+  for (int b = 0; b < B; ++b)
+    for (int z = 0; z < 2; ++z) {
+      int dy, dx;
+      aug_shift_of(seed, ctr, b, z, c->aug_pad, &dy, &dx);
+      c->aug_shift[(size_t)b * 4 + 2 * z] = (float)dy;
+      c->aug_shift[(size_t)b * 4 + 2 * z + 1] = (float)dx;
+      float* f = (z ? c->next_state : c->state).data() + (size_t)b * kC * SS;
+      std::copy(f, f + (size_t)kC * SS, tmp.begin());
+      for (int ch = 0; ch < kC; ++ch)
+        for (int y = 0; y < S; ++y)
+          for (int x = 0; x < S; ++x) {
+            const int ys = std::min(std::max(y + dy, 0), S - 1);
+            const int xs = std::min(std::max(x + dx, 0), S - 1);
+            f[((size_t)ch * S + y) * S + x] = tmp[((size_t)ch * S + ys) * S + xs];
+          }
+    }
+}
+
 void gather(ddq_ctx* c) {
   const int B = c->B, SS = c->S * c->S;
   const size_t slot = (size_t)kC * SS;
@@ -843,6 +877,7 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->lanes = 1;
   c->lane_len = capacity;
   c->nstep = 1;
+  c->aug_pad = 0;
   c->prio_on = false;
   c->prio_cfg = ddq_priority_cfg{0, 0.f, 0.f, 0.f};
   return DDQ_OK;
@@ -885,6 +920,23 @@ int ddq_replay_set_nstep(ddq_ctx* c, int32_t n) {
                 DDQ_NSTEP_MAX, (long long)c->lane_len, n);
   c->nstep = n;
   prio_rebuild(c);
+  return DDQ_OK;
+}
+
+int ddq_replay_set_augment(ddq_ctx* c, int32_t pad) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->capacity) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (pad < 0 || pad > DDQ_AUGMENT_PAD_MAX || 4 * pad > c->S)
+    return fail(c, DDQ_EINVAL, "augmentation pad must be in [0, %d] and at most frame / 4 = %d "
+                               "(got %d)", DDQ_AUGMENT_PAD_MAX, c->S / 4, pad);
+  c->aug_pad = pad;
+  return DDQ_OK;
+}
+
+int ddq_replay_get_augment(const ddq_ctx* c, int32_t* pad) {
+  if (!c || !pad) return fail(nullptr, DDQ_EINVAL, "null argument");
+  if (!c->capacity) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  *pad = c->aug_pad;
   return DDQ_OK;
 }
 
@@ -1069,13 +1121,15 @@ int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
   if (c->B > c->lanes * allowed_slots(c))
     return fail(c, DDQ_EINVAL, "Can't draw sample of size %d from replay dataset of size %lld",
                 c->B, (long long)(c->lanes * c->valid));
-  prio_draw(c, seed, c->prio_ctr++);
+  const uint64_t ctr = c->prio_ctr++;
+  prio_draw(c, seed, ctr);
   for (int b = 0; b < c->B; ++b) {
     const int64_t j = (int64_t)c->idx[b] + 1, nxt = j % c->lane_len == 0 ? j - c->lane_len : j;
     if (c->r_action[nxt] >= kA)
       return fail(c, DDQ_ERANGE, "stored action index out of range for %d actions", kA);
   }
   gather(c);
+  if (c->aug_pad > 0) shift_frames(c, seed, ctr);
   c->idx_bound = true;
   return DDQ_OK;
 }
@@ -1209,12 +1263,16 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_sa", c->q_sa.data(), c->B},         {"P_sa", c->p_sa.data(), c->B},
       {"target_Q_sa", c->target.data(), c->B}, {"loss", &c->loss, 1},
       {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B},
-      {"is_weight", c->isw.data(), c->B},       {"grad_norm", &c->gnorm, 1}};
+      {"is_weight", c->isw.data(), c->B},       {"grad_norm", &c->gnorm, 1},
+      {"aug_shift", c->aug_shift.data(), 4ll * c->B}};
   for (auto& e : t)
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
       if (!strcmp(name, "grad_norm") && !(c->adam_on && c->adam.max_grad_norm > 0.f))
         return fail(c, DDQ_ESTATE, "blob grad_norm exists while Adam's gradient clipping is on");
+      if (!strcmp(name, "aug_shift") && (c->aug_pad == 0 || c->aug_shift.empty()))
+        return fail(c, DDQ_ESTATE, "blob aug_shift exists while augmentation is on "
+                                   "(ddq_replay_set_augment)");
       if (!strcmp(name, "is_weight") && !c->prio_on)
         return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       if (!strcmp(name, "Qn_out") && c->obj.target != DDQ_TARGET_DOUBLE)

@@ -122,6 +122,7 @@ struct ddq_ctx {
   int32_t lanes = 1;               // laned ring (ddq_replay_set_lanes): head / valid per lane
   int64_t lane_len = 0;            // capacity / lanes
   int32_t nstep = 1;               // n-step returns (ddq_replay_set_nstep)
+  int32_t aug_pad = 0;             // random-shift augmentation (ddq_replay_set_augment): 0 = off
   // prioritized replay (ddq_replay_set_priority): nb.prio and the sets' isw are bound while on
   bool prio_on = false;
   ddq_priority_cfg prio_cfg{0, 0.f, 0.f, 0.f};
@@ -282,6 +283,7 @@ static int mb_alloc(ddq_ctx* c, Minibatch* out) {
   TRY(dalloc(c, &m.reward, 2 * B));
   TRY(dalloc(c, &m.nonterm, B));
   TRY(dalloc(c, &m.idx, B));
+  TRY(dalloc(c, &m.shift, B * 4));
   *out = m;
   return DDQ_OK;
 }
@@ -772,6 +774,7 @@ int ddq_replay_create(ddq_ctx* c, int64_t capacity) {
   c->lane_len = capacity;
   c->nstep = 1;
   c->nb.nstep = 1;
+  c->aug_pad = 0;
   prio_release(c);
   ReplayMeta m{};
   m.capacity = capacity;
@@ -893,6 +896,31 @@ int ddq_replay_nstep(const ddq_ctx* c, int32_t* n) {
   if (!c || !n) return fail(nullptr, DDQ_EINVAL, "null argument");
   if (!c->ring.state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
   *n = c->nstep;
+  return DDQ_OK;
+}
+
+static_assert(kAugPadMax == DDQ_AUGMENT_PAD_MAX, "a run's window covers pad <= DDQ_AUGMENT_PAD_MAX");
+
+int ddq_replay_set_augment(ddq_ctx* c, int32_t pad) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->ring.state) return fail(c, DDQ_ESTATE, "no replay buffer (call ddq_replay_create)");
+  if (c->async_on)
+    return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: it takes no "
+                               "augmentation");
+  if (pad < 0 || pad > DDQ_AUGMENT_PAD_MAX || 4 * pad > c->nb.S)
+    return fail(c, DDQ_EINVAL, "augmentation pad must be in [0, %d] and at most frame / 4 = %d "
+                               "(got %d)", DDQ_AUGMENT_PAD_MAX, c->nb.S / 4, pad);
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);   // captured steps hold the fused gather blocks, or the shifting launch
+  c->aug_pad = pad;
+  return DDQ_OK;
+}
+
+int ddq_replay_get_augment(const ddq_ctx* c, int32_t* pad) {
+  if (!c || !pad) return fail(nullptr, DDQ_EINVAL, "null argument");
+  if (!c->ring.state) return fail(const_cast<ddq_ctx*>(c), DDQ_ESTATE, "no replay buffer");
+  *pad = c->aug_pad;
   return DDQ_OK;
 }
 
@@ -1115,7 +1143,10 @@ int ddq_replay_sample_device_async(ddq_ctx* c, uint64_t seed) {
   } else {
     HIP_TRY(c, launch_sample(c->nb, c->ring.meta, seed, c->stream));
   }
-  HIP_TRY(c, launch_gather(c->nb, c->ring, c->stream));
+  if (c->aug_pad > 0)   // (both draws above moved the counter on: back = 1)
+    HIP_TRY(c, launch_gather_shift(c->nb, c->ring, seed, c->aug_pad, 1, c->stream));
+  else
+    HIP_TRY(c, launch_gather(c->nb, c->ring, c->stream));
   c->idx_bound = true;
   return DDQ_OK;
 }
@@ -1363,6 +1394,12 @@ static int enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, const StepLaunch& s
     m("prio_commit");
     HIP_TRY(c, launch_prio_commit_draw(nb, sl.meta, sl.plan.draw == Site::PrioCommit ? prio_next : nullptr,
                                        prio_seed, c->stream));
+    // augmented: the shifting gather of the set the commit launch just drew (under the
+    // counter it advanced: back = 0)
+    if (sl.plan.gather == Site::PrioCommit) {
+      m("gather_shift");
+      HIP_TRY(c, launch_gather_shift(*prio_next, c->ring, prio_seed, c->aug_pad, 0, c->stream));
+    }
   }
   hipError_t e = nb.small ? launch_small_bwd(nb, sl, c->stream, m, fc4_done)
                           : launch_backward(nb, sl, c->stream, m, fc4_done);
@@ -1472,7 +1509,8 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Q_sa", c->nb.q_sa, B},         {"P_sa", c->nb.p_sa, B},
       {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1},
       {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B},
-      {"is_weight", c->nb.mb.isw, B},       {"grad_norm", c->nb.gnorm, 1}};
+      {"is_weight", c->nb.mb.isw, B},       {"grad_norm", c->nb.gnorm, 1},
+      {"aug_shift", c->nb.mb.shift, 4ll * B}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
@@ -1480,6 +1518,9 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
         return fail(c, DDQ_ESTATE, "blob grad_norm exists while Adam's gradient clipping is on");
       if (!strcmp(name, "Qn_out") && c->nb.obj_target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
+      if (!strcmp(name, "aug_shift") && c->aug_pad == 0)
+        return fail(c, DDQ_ESTATE, "blob aug_shift exists while augmentation is on "
+                                   "(ddq_replay_set_augment)");
       if (!strcmp(name, "is_weight") && !c->nb.mb.isw)
         return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       TRY(set_dev(c));
@@ -2088,7 +2129,8 @@ static StepFacts step_facts(const ddq_ctx* c, const ddq_step_cfg* cfg) {
   f.fused_apply_ok = fused_apply_ok(c->nb.L);
   f.no_grad_store = (cfg->flags & DDQ_STEP_NO_GRAD_STORE) != 0;
   // (only the two-launch draw moved the counter on itself: enqueue_draw)
-  f.holds_counter = c->prio_on || c->nb.B <= 256;
+  f.augment = c->aug_pad > 0;
+  f.holds_counter = c->prio_on || (c->nb.B <= 256 && !f.augment);
   // (the owners keep the async exchange's iteration)
   const bool worker = f.ex == Exchange::AsyncWorker;
   f.book_period = worker ? -1 : book_period(cfg);
@@ -2192,7 +2234,15 @@ static int enqueue_exchange_apply(ddq_ctx* c, const ddq_step_cfg* cfg, const Net
 // The draw of a minibatch and its gather into nb's set, on `stream`.
 static int enqueue_draw(ddq_ctx* c, const NetBuffers& nb, uint64_t seed, hipStream_t stream,
                         Marks m = {}) {
-  if (c->prio_on) {   // one workgroup descends the sum tree, then the plain gather
+  if (c->aug_pad > 0) {   // the draw, then the shifting gather: never fused (gather_shift.h)
+    m(c->prio_on ? "prio_sample" : "sample");
+    if (c->prio_on)       // (leaves the counter to the step's commit: back = 0)
+      HIP_TRY(c, launch_prio_sample(nb, c->ring.meta, seed, stream));
+    else
+      HIP_TRY(c, launch_sample(nb, c->ring.meta, seed, stream));
+    m("gather_shift");
+    HIP_TRY(c, launch_gather_shift(nb, c->ring, seed, c->aug_pad, c->prio_on ? 0 : 1, stream));
+  } else if (c->prio_on) {   // one workgroup descends the sum tree, then the plain gather
     m("prio_sample");
     HIP_TRY(c, launch_prio_sample(nb, c->ring.meta, seed, stream));
     m("gather");
@@ -2307,6 +2357,9 @@ static int check_step(ddq_ctx* c, const ddq_step_cfg* cfg) {
     return fail(c, DDQ_EINVAL, "DDQ_RULE_ADAM runs without an exchange or under "
                                "DDQ_EXCHANGE_ALLREDUCE only (exchange %d shards one state buffer)",
                 cfg->exchange);
+  if (c->aug_pad > 0 && is_async(c, cfg))
+    return fail(c, DDQ_EINVAL, "augmentation (pad %d) with DDQ_EXCHANGE_ASYNC: its workers' draws "
+                               "ride on the owner applies", c->aug_pad);
   if (c->nb.target_tau < 1.f && is_async(c, cfg))
     return fail(c, DDQ_EINVAL, "soft target updates (tau %g < 1) with DDQ_EXCHANGE_ASYNC: its P "
                                "travels by pulls, not by the steps' syncs",
@@ -2542,6 +2595,9 @@ int ddq_async_begin(ddq_ctx* c, const ddq_step_cfg* cfg) {
     return fail(c, DDQ_EINVAL, "soft target updates (tau %g < 1) with DDQ_EXCHANGE_ASYNC: its P "
                                "travels by pulls, not by the steps' syncs",
                 (double)c->nb.target_tau);
+  if (c->aug_pad > 0)
+    return fail(c, DDQ_EINVAL, "augmentation (pad %d) with DDQ_EXCHANGE_ASYNC: its workers' draws "
+                               "ride on the owner applies", c->aug_pad);
   if (c->mon.ring && c->mon_period > 0)
     return fail(c, DDQ_ESTATE, "the async exchange takes no monitor records: disable the monitor or "
                                "enable it with period 0");

@@ -110,11 +110,13 @@ struct ReplayRing {
 // weights (B) of prioritized replay, bound only while it is on and then always
 // reward + B, the second half of the reward buffer (the head then runs its
 // objective instantiation, reads them there and scales dQ and the loss terms
-// by them).
+// by them).  shift: the (B,4) random shifts (dy_s, dx_s, dy_s', dx_s') the augmenting
+// gather applied (gather_shift.h), blob "aug_shift".
 struct Minibatch {
   float *state, *next_state, *action, *reward, *nonterm;
   int32_t* idx;
   float* isw;
+  float* shift;
 };
 
 // The profile marks of a step (ddq_profile_step): m(name) names the kernel
@@ -215,6 +217,11 @@ hipError_t launch_sample_gather(const NetBuffers& nb, const ReplayRing& ring, ui
                                 hipStream_t s);
 hipError_t launch_gather(const NetBuffers& nb, const ReplayRing& ring, hipStream_t s);
 hipError_t launch_sample(const NetBuffers& nb, ReplayMeta* meta, uint64_t seed, hipStream_t s);
+constexpr int kAugPadMax = 8;   // DDQ_AUGMENT_PAD_MAX; < 16: a run's window is 32 bytes
+// the augmenting gather (gather_shift.h, ddq_replay_set_augment): launch_gather's work with
+// every frame shifted by the (seed, draw counter - back, sample, side) stream's offsets
+hipError_t launch_gather_shift(const NetBuffers& nb, const ReplayRing& ring, uint64_t seed, int pad,
+                               int back, hipStream_t s);
 // only: 0 = every layer, l + 1 = conv layer l alone (ddq_time_layer), -1 = no
 // conv layer: fc4 and the head on a pool3 already written (launch_act)
 hipError_t launch_forward(const NetBuffers& nb, int nz, hipStream_t s, Marks M = {},

@@ -396,6 +396,10 @@ hipError_t launch_gather(const NetBuffers& nb, const ReplayRing& r, hipStream_t 
   return hipGetLastError();
 }
 
+}  // namespace ddq
+#include "gather_shift.h"
+namespace ddq {
+
 // ---------------------------------------------------------------------------
 // large-batch sampling + Caffe-layout gather (SURVEY 8(d) C5 gather stress;
 // same selection semantics as replay.py:144-183 for any n <= valid/2)

@@ -47,6 +47,9 @@ struct StepFacts {
   int book_period = 0;           // target period of the apply bookkeeping; < 0: no bookkeeping
   int book_step = 1;              // param-server iterations per apply (1, or W)
   bool fault_k2_short = false;   // ddq_inject_fault: this step's fc4 chain one workgroup short
+  bool augment = false;          // ddq_replay_set_augment, pad > 0: every draw is two launches,
+                                 // the draw and then the shifting gather (gather_shift.h),
+                                 // never blocks of another launch
 };
 
 struct StepPlan {
@@ -56,7 +59,8 @@ struct StepPlan {
                                          // always moves: it must then be the bump site)
   Site bump = Site::Nobody;              // who advances the draw counter
   Site draw = Site::Nobody;              // who draws the next step's index set
-  Site gather = Site::Nobody;            // who gathers it
+  Site gather = Site::Nobody;            // who gathers it (augmented and PrioCommit: the
+                                         // shifting gather, the launch after the commit's)
   Site latch = Site::Nobody;             // who latches the apply flags first
   Site book = Site::Nobody;              // who does the apply bookkeeping (Apply: a launch of
                                          // its own before it, plan_apply_only)
@@ -104,8 +108,10 @@ inline bool plan_step(const StepFacts& f, StepPlan* p, const char** why) {
   if (f.prio && (!(fused || f.adam) || !f.holds_counter))
     return no("a prioritized step without the fused apply or the draw counter");
   if (f.small && !f.b_le_256) return no("the small path with B > 256");
-  if (f.holds_counter != f.b_le_256)
+  // (an augmented draw is sample_kernel + the shifting gather at every B, unless prioritized)
+  if (f.holds_counter != (f.b_le_256 && (!f.augment || f.prio)))
     return no("the one-launch draw is the draw of B <= 256, and leaves the counter to the step");
+  if (f.augment && async) return no("the async exchange with augmentation");
   if (f.prio && f.ex != Exchange::None) return no("a prioritized step with an exchange");
   if (f.adam && f.ex != Exchange::None && f.ex != Exchange::AllReduce)
     return no("Adam with an exchange other than the one-call all-reduce");
@@ -126,8 +132,12 @@ inline bool plan_step(const StepFacts& f, StepPlan* p, const char** why) {
             : f.prio         ? Site::PrioCommit
             : fused || async ? Site::Head
                              : Site::SlabReduce;
-  if (f.prefetch && !f.b_le_256) {
+  if (f.prefetch && !f.holds_counter) {
     p->draw = p->gather = Site::Side;   // the two-launch draw
+  } else if (f.prefetch && f.augment) {
+    // prioritized: the draw must see this step's commit, so it stays the commit launch's,
+    // and the shifting gather follows it on the ctx stream
+    p->draw = p->gather = Site::PrioCommit;
   } else if (f.prefetch) {
     p->gather = fused ? Site::SlabReduce : owner ? Site::OwnerApply : Site::Apply;
     p->draw = f.prio ? Site::PrioCommit : fused ? Site::Head : p->gather;

@@ -179,6 +179,8 @@ _SIGS = {
     "ddq_replay_lanes": (ctypes.c_int, [_P, _P, _P]),
     "ddq_replay_set_nstep": (ctypes.c_int, [_P, _i32]),
     "ddq_replay_nstep": (ctypes.c_int, [_P, _P]),
+    "ddq_replay_set_augment": (ctypes.c_int, [_P, _i32]),
+    "ddq_replay_get_augment": (ctypes.c_int, [_P, _P]),
     "ddq_replay_set_priority": (ctypes.c_int, [_P, ctypes.POINTER(PriorityCfg)]),
     "ddq_replay_get_priority": (ctypes.c_int, [_P, ctypes.POINTER(PriorityCfg)]),
     "ddq_replay_update_priorities_async": (ctypes.c_int, [_P]),

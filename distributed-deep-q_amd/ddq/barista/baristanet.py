@@ -3,7 +3,7 @@ with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
 reset_log=False, objective=None, n_step=None, priority=None, target_tau=None,
-checkpoint=None, checkpoint_every=0, resume=None, acting_path=None)``:
+checkpoint=None, checkpoint_every=0, resume=None, acting_path=None, augment_pad=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -18,6 +18,10 @@ checkpoint=None, checkpoint_every=0, resume=None, acting_path=None)``:
 * ``n_step`` -- None (the dataset's own n-step length, 1 unless it was made with
   ``ReplayDataset(n_step=)``) or the n of the n-step returns the minibatches are
   gathered for (``DeepQNet.replay_set_nstep``), set on every dataset added;
+* ``augment_pad`` -- None (the dataset's own setting, off unless it was made with
+  ``ReplayDataset(augment_pad=)``) or the pad of the random-shift augmentation of
+  the device-drawn minibatches (``DeepQNet.replay_set_augment``), set on every
+  dataset added;
 * ``priority`` -- None (the dataset's own setting, uniform unless it was made with
   ``ReplayDataset(priority=)``) or a dict ``{"alpha":, "beta":, "eps":}`` of
   proportional prioritized replay (``DeepQNet.replay_set_priority``), set on
@@ -104,7 +108,7 @@ class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
                  reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
                  priority=None, target_tau=None, checkpoint=None, checkpoint_every=0,
-                 resume=None, acting_path=None):
+                 resume=None, acting_path=None, augment_pad=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
@@ -130,6 +134,7 @@ class BaristaNet:
         self.dataset = None
         self.n_step = None if n_step is None else int(n_step)
         self.priority = priority
+        self.augment_pad = None if augment_pad is None else int(augment_pad)
         self.per_seed = random.getrandbits(63)   # the prioritized draws' index stream
         self.driver = driver
         # logpath: the reference's per-step loss / norm files (baristanet.py:45-46,
@@ -175,6 +180,8 @@ class BaristaNet:
             dset.set_n_step(self.n_step)
         if self.priority is not None:
             dset.set_priority(self.priority)
+        if self.augment_pad is not None:
+            dset.set_augment_pad(self.augment_pad)
         self.dataset = dset
         if self._resume and not self._resume_deferred:
             self.load_checkpoint(self._resume)

@@ -39,6 +39,11 @@ every target sync, P <- P + T (Q - P).  Either mode.
 (``DeepQNet.replay_set_nstep``): the discounted sum of up to N rewards and
 gamma^N P(s_{t+N}, .), cut at the first terminal step.  Either mode.
 
+``--augment-pad P`` (default 0, off) shifts every device-drawn frame by a random
+offset in [-P, P]^2 over a replicate-padded copy (``DeepQNet.replay_set_augment``);
+it acts where the minibatch is drawn on the device (prioritized replay, the step
+modes), not on ``sample_direct``'s host-index gather.  Either mode.
+
 ``--per-alpha A`` (off by default) turns on proportional prioritized replay
 (``DeepQNet.replay_set_priority``) with exponent A in [0, 1]; ``--per-beta``
 (default 0.4, in [0, 1]) is the importance-sampling exponent and ``--per-eps``
@@ -137,6 +142,9 @@ def get_args(argv=None):
                     help="kernels of the acting forward (default batch)")
     ap.add_argument("--n-step", dest="n_step", type=int, default=1,
                     help="N-step returns: the replay gathers N-step windows (default 1)")
+    ap.add_argument("--augment-pad", dest="augment_pad", type=int, default=0,
+                    help="random-shift augmentation of device-drawn minibatches, pad in [0, 8] "
+                         "(default 0: off)")
     ap.add_argument("--per-alpha", dest="per_alpha", type=float, default=None,
                     help="prioritized replay with this priority exponent in [0, 1] (default: off)")
     ap.add_argument("--per-beta", dest="per_beta", type=float, default=None,
@@ -166,6 +174,8 @@ def get_args(argv=None):
         ap.error("--per-eps must be > 0")
     if not 1 <= args.n_step <= NSTEP_MAX:
         ap.error("--n-step must be in [1, %d]" % NSTEP_MAX)
+    if not 0 <= args.augment_pad <= 8:
+        ap.error("--augment-pad must be in [0, 8]")
     if args.n_step >= args.dset_size:
         ap.error("--n-step must be below --dset-size (%d)" % args.dset_size)
     if args.target_tau is not None and not 0.0 < args.target_tau <= 1.0:
@@ -213,7 +223,8 @@ def build_worker(args):
     resume = getattr(args, "resume", None)
     replay = ReplayDataset(args.dataset, net.state[0].shape, dset_size=args.dset_size,
                            overwrite=args.overwrite, batch_size=net.batch_size, mode=args.mode,
-                           n_step=getattr(args, "n_step", 1), priority=priority_of(args))
+                           n_step=getattr(args, "n_step", 1), priority=priority_of(args),
+                           augment_pad=getattr(args, "augment_pad", 0))
     net.add_dataset(replay)
     game = SnakeGame()
     pre = eg.generate_preprocessor(net.state.shape[2:], gray_scale)

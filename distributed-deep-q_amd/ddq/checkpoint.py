@@ -252,6 +252,8 @@ def restore(path, device=0, mode="gpu", setup=None):
                 net.replay_set_lanes(int(k["lanes"]))
             if k["nstep"] > 1:
                 net.replay_set_nstep(int(k["nstep"]))
+            # (the augmentation pad, ddq_replay_set_augment, is a property of sampling that
+            # no section stores: the caller sets it again, as it set it the first time)
             if k["prio_enabled"]:
                 net.replay_set_priority(alpha=float(k["prio_alpha"]), beta=float(k["prio_beta"]),
                                         eps=float(k["prio_eps"]))

@@ -21,7 +21,7 @@ NUM_ACTIONS = 4     # barista/constants.py:8
 NFRAME = 4          # expgain.py:9
 
 BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0,
-         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1, "grad_norm": 0}
+         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1, "grad_norm": 0, "aug_shift": 4}
 
 # include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
 MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
@@ -503,6 +503,22 @@ class DeepQNet:
         n = _lib._i32()
         self._check(self.lib.ddq_replay_nstep(self.ctx, ctypes.byref(n)))
         return int(n.value)
+
+    def replay_set_augment(self, pad):
+        """Random-shift augmentation (ddq_replay_set_augment): every later device
+        draw (``replay_sample_device``, the step modes) replicate-pads each
+        gathered frame by ``pad`` pixels and crops it back at a random offset,
+        one shift per frame, independent for state and next_state.  The indices
+        and scalars are those of the run without it; blob ``aug_shift`` (B, 4)
+        holds the bound minibatch's (dy_s, dx_s, dy_s', dx_s').  0 (the default)
+        is off, bit for bit."""
+        self._check(self.lib.ddq_replay_set_augment(self.ctx, int(pad)))
+
+    def replay_augment(self):
+        """The augmentation's pad (0 = off)."""
+        p = _lib._i32()
+        self._check(self.lib.ddq_replay_get_augment(self.ctx, ctypes.byref(p)))
+        return int(p.value)
 
     def replay_set_priority(self, alpha=0.6, beta=0.4, eps=1e-2, enabled=True):
         """Proportional prioritized replay (ddq_replay_set_priority): device draws

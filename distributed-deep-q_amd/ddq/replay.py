@@ -56,11 +56,13 @@ class ReplayDataset:
     # stub ring to check draw_indices against the reference's recorded draws)
     n_step = 1
     priority = None
+    augment_pad = 0
 
     def __init__(self, filename, state_shape, dset_size=1000, overwrite=False, batch_size=32,
-                 device=0, net=None, mode="gpu", n_step=1, priority=None):
+                 device=0, net=None, mode="gpu", n_step=1, priority=None, augment_pad=0):
         self.filename = filename
         self.n_step = int(n_step)
+        self.augment_pad = int(augment_pad)
         self.priority = _priority_dict(priority)
         self.state_shape = tuple(int(x) for x in state_shape)
         if len(self.state_shape) != 3 or self.state_shape[0] != 4 or \
@@ -91,6 +93,8 @@ class ReplayDataset:
             self._net.replay_set_nstep(self.n_step)
         if self.priority is not None:
             self._net.replay_set_priority(**self.priority)
+        if self.augment_pad:
+            self._net.replay_set_augment(self.augment_pad)
 
     def set_priority(self, priority):
         """Turn prioritized replay on (a dict of alpha / beta / eps; on an enabled
@@ -102,6 +106,12 @@ class ReplayDataset:
         else:
             self._net.replay_set_priority(**priority)
         self.priority = priority
+
+    def set_augment_pad(self, pad):
+        """Random-shift augmentation of the device draws (``DeepQNet.replay_set_augment``);
+        ``sample_direct`` with host indices stays the reference's gather."""
+        self._net.replay_set_augment(int(pad))
+        self.augment_pad = int(pad)
 
     def set_n_step(self, n):
         """Change the n-step length of the ring (legal on a filled ring)."""
@@ -130,6 +140,8 @@ class ReplayDataset:
             net.replay_set_nstep(self.n_step)
         if self.priority is not None:
             net.replay_set_priority(**self.priority)
+        if self.augment_pad:
+            net.replay_set_augment(self.augment_pad)
         if self._own_net:
             self._net.close()
         self._net, self._own_net = net, False

@@ -63,7 +63,9 @@ extern "C" {
                               checkpoint and resume (ddq_state_sections, ddq_state_read,
                               ddq_state_write, ddq_state_commit, ddq_state_digest),
                               likewise; and the acting path (ddq_set_acting_path,
-                              ddq_get_acting_path), likewise */
+                              ddq_get_acting_path), likewise; and random-shift
+                              augmentation (ddq_replay_set_augment,
+                              ddq_replay_get_augment; blob "aug_shift"), likewise */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -321,6 +323,38 @@ int ddq_replay_lanes(const ddq_ctx* ctx, int32_t* lanes, int64_t* lane_len);
 #define DDQ_NSTEP_MAX 8
 int ddq_replay_set_nstep(ddq_ctx* ctx, int32_t n);
 int ddq_replay_nstep(const ddq_ctx* ctx, int32_t* n);
+/* Random-shift augmentation (DrQ, RAD; no reference counterpart).  pad = 0 (the
+ * default, reset by ddq_replay_create) is off, and then every launch and every
+ * bit is what it is without this call.  With pad = p > 0 every device draw that
+ * fills the training minibatch -- ddq_replay_sample_device_async and the eager,
+ * graph and pipelined step modes, with n-step windows, lanes, prioritized replay,
+ * every update rule and objective -- replicate-pads each gathered frame by p
+ * pixels and crops it back at a random offset:
+ *     out[c][y][x] = S[slot][c][clamp(y + dy, 0, S-1)][clamp(x + dx, 0, S-1)]
+ * one (dy, dx) for the four channels of a frame, independent between a sample's
+ * state and next_state.  For draw ctr (ddq_replay_draws before the draw), sample
+ * position j in [0, B) of the sorted set and side z (0 state, 1 next_state):
+ *     r  = splitmix64((seed ^ 0xD1B54A32D192ED03)
+ *                     ^ splitmix64(ctr * 0x100000001B3 + (2 j + z) * 0x9E37))
+ *     dy = (r mod (2 p + 1)) - p            dx = ((r >> 32) mod (2 p + 1)) - p
+ * r an unsigned 64-bit value.  The index stream is not touched: the indices,
+ * action, reward and non_terminal are those of the same run with pad = 0.  Blob
+ * "aug_shift" (B*4: dy_s, dx_s, dy_s', dx_s' per sample, as floats) holds the
+ * bound minibatch's shifts; DDQ_ESTATE while pad = 0.  The draw is then always
+ * the draw launch followed by the shifting gather ("sample" or "prio_sample",
+ * then "gather_shift" in ddq_profile_step); a pipelined chain runs the pair
+ * beside the step on the side stream, or right after "prio_commit" under
+ * prioritized replay.  Not augmented: ddq_replay_sample (host indices, the
+ * reference's bit-exact path), ddq_write_minibatch and the large-batch sampler
+ * ddq_replay_sample_batch_async / ddq_replay_gather_batch_async.
+ * Synchronises and drops captured graphs.  DDQ_EINVAL: pad < 0,
+ * pad > DDQ_AUGMENT_PAD_MAX or pad > frame / 4.  DDQ_ESTATE: no ring, or the
+ * async exchange has begun; DDQ_EXCHANGE_ASYNC steps and ddq_async_begin refuse
+ * pad > 0 with DDQ_EINVAL.  pad is a property of sampling, like n: it is not
+ * stored with the ring or in a checkpoint. */
+#define DDQ_AUGMENT_PAD_MAX 8
+int ddq_replay_set_augment(ddq_ctx* ctx, int32_t pad);   /* 0 = off (default) */
+int ddq_replay_get_augment(const ddq_ctx* ctx, int32_t* pad);
 /* Proportional prioritized replay (Schaul et al. 2016; no reference counterpart).
  * Off by default; while off every launch and every bit is what it is without
  * this section.  While on, the device draws (the step modes,
