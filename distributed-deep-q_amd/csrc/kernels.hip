@@ -9,8 +9,8 @@
 
 namespace ddq {
 
-// first failing launch site of the last failed launch sequence (api.hip
-// appends it to the error message)
+// first failing launch site of the last failed launch sequence (HIP_TRY in
+// ctx.h appends it to the error message)
 thread_local const char* g_launch_where = "";
 thread_local ExtTiming g_ext_timing;
 thread_local bool g_profiling = false;

@@ -35,7 +35,7 @@ def apply_ref(ref, rule, theta, g, state, lr):
 
 def owner_state(nets):
     """Optimizer state as the owners hold it (shard r on member r,
-    L = ceil(P / (64 W)) * 64, api.hip setup_shards)."""
+    L = ceil(P / (64 W)) * 64, api_exchange.hip setup_shards)."""
     P = nets[0].num_params
     L = -(-P // (64 * len(nets))) * 64
     out = np.empty(P, np.float32)

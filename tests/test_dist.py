@@ -83,7 +83,7 @@ def test_world2_gloo_sync_dp_semantics():
 
 
 def _shard_len(P, W):
-    """Shard geometry of ddq_comm_init / ddq_group_init (api.hip setup_shards)."""
+    """Shard geometry of ddq_comm_init / ddq_group_init (api_exchange.hip setup_shards)."""
     return ((P + W * 64 - 1) // (W * 64)) * 64
 
 
@@ -218,7 +218,7 @@ def _fake_grad(theta, w, k):
 
 
 def _async_worker(rank, world, port, rounds, period, out):
-    """DDQ_EXCHANGE_ASYNC's round-robin schedule (api.hip rccl_async_round)
+    """DDQ_EXCHANGE_ASYNC's round-robin schedule (api_exchange.hip rccl_async_round)
     restated over gloo point-to-point: at tick w worker w sends its gradient
     slices to the owners, each owner applies its slice to its shard of the
     central model on arrival (rmsprop, lagged cache), the central P shard

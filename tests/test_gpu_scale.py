@@ -137,8 +137,8 @@ def run_exchange(ddq, ref, nets, theta, exchange, rule="rmsprop", lr=1e-4, steps
 def owner_state(nets, exchange):
     """The optimizer state as the W owners hold it: allreduce keeps a full
     replica per member; sharded / server exchanges keep rank r's state only on
-    its shard [r * L, (r + 1) * L), L = ceil(P / (64 W)) * 64 (api.hip
-    setup_shards)."""
+    its shard [r * L, (r + 1) * L), L = ceil(P / (64 W)) * 64
+    (api_exchange.hip setup_shards)."""
     if exchange == "allreduce":
         return nets[0].optimizer_state()
     P = nets[0].num_params
