@@ -1145,9 +1145,30 @@ int ddq_read_minibatch(ddq_ctx* c, float* state, float* action, float* reward, f
   return DDQ_OK;
 }
 
+// index of the first of n floats that bf16 does not hold exactly (low 16 bits
+// of the fp32 pattern set, or not finite), -1 if none
+static int64_t first_not_bf16(const float* v, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t u;
+    memcpy(&u, v + i, 4);
+    if ((u & 0xFFFFu) || (u & 0x7F800000u) == 0x7F800000u) return i;
+  }
+  return -1;
+}
+
 int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, const float* reward,
                         const float* next_state, const float* nonterm) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  // the HIP library's conv1 reads a frame as one bf16 plane: one contract, one
+  // refusal in both libraries, before anything of the bound minibatch changes
+  for (int which = 0; which < 2; ++which) {
+    const float* src = which ? next_state : state;
+    if (!src) continue;
+    const int64_t bad = first_not_bf16(src, (int64_t)c->state.size());
+    if (bad >= 0)
+      return fail(c, DDQ_EINVAL, "%s[%lld] = %.9g is not exactly representable in bf16",
+                  which ? "next_state" : "state", (long long)bad, (double)src[bad]);
+  }
   if (state) std::copy(state, state + c->state.size(), c->state.begin());
   if (next_state) std::copy(next_state, next_state + c->next_state.size(), c->next_state.begin());
   if (action) std::copy(action, action + c->action.size(), c->action.begin());

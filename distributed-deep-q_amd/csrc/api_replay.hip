@@ -628,11 +628,33 @@ int ddq_read_minibatch(ddq_ctx* c, float* state, float* action, float* reward, f
   return DDQ_OK;
 }
 
+// index of the first of n floats that bf16 does not hold exactly (low 16 bits
+// of the fp32 pattern set, or not finite), -1 if none
+static int64_t first_not_bf16(const float* v, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t u;
+    memcpy(&u, v + i, 4);
+    if ((u & 0xFFFFu) || (u & 0x7F800000u) == 0x7F800000u) return i;
+  }
+  return -1;
+}
+
 int ddq_write_minibatch(ddq_ctx* c, const float* state, const float* action, const float* reward,
                         const float* next_state, const float* nonterm) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
   TRY(set_dev(c));
   const int B = c->nb.B, SS = c->nb.S * c->nb.S;
+  // conv1 reads a frame as ONE bf16 plane (split.h), so a value with more than
+  // 8 significant bits would lose them without a word: refuse it here, before
+  // anything of the bound minibatch is touched
+  for (int which = 0; which < 2; ++which) {
+    const float* src = which ? next_state : state;
+    if (!src) continue;
+    const int64_t bad = first_not_bf16(src, (int64_t)B * 4 * SS);
+    if (bad >= 0)
+      return fail(c, DDQ_EINVAL, "%s[%lld] = %.9g is not exactly representable in bf16",
+                  which ? "next_state" : "state", (long long)bad, (double)src[bad]);
+  }
   std::vector<float> tmp((size_t)B * SS * 4);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (int which = 0; which < 2; ++which) {

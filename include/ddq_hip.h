@@ -458,7 +458,18 @@ int ddq_replay_sample_device_async(ddq_ctx* ctx, uint64_t seed);
 int ddq_read_minibatch(ddq_ctx* ctx, float* state, float* action, float* reward,
                        float* next_state, float* non_terminal);
 /* Set the minibatch directly (set_input_arrays binding, baristanet.py:41-43;
- * dummy_load_minibatch :70-83). */
+ * dummy_load_minibatch :70-83).  A null array leaves that part as it is.
+ * Frames contract: every state and next_state value must be exactly
+ * representable in bf16 (finite, at most 8 significant bits) -- the integers
+ * 0..255 of the reference's uint8 frames are, and so is 100.5; 200.5 or
+ * frame / 255.0 are not.  The first convolution reads a frame as one bf16
+ * plane (csrc/split.h), so any other value would be rounded to 2^-9 of itself
+ * silently.  DDQ_EINVAL otherwise, the message naming the array, the flat
+ * (B,4,S,S) index and the first offending value; the bound minibatch is then
+ * unchanged.  The CPU-mode library refuses identically.  The check is on the
+ * bit pattern, so negative values and bf16 subnormals (|v| < 2^-126) pass it;
+ * the matrix cores may flush a subnormal to zero where the CPU-mode library
+ * keeps it, so frames are to be zero or normal numbers. */
 int ddq_write_minibatch(ddq_ctx* ctx, const float* state, const float* action,
                         const float* reward, const float* next_state,
                         const float* non_terminal);

@@ -235,7 +235,7 @@ def route_codes(act, arg):
 
 
 def full_pass(pQ, pP, state, action, reward, next_state, non_terminal, routes=None,
-              return_cache=False, h4_mask=None):
+              return_cache=False, h4_mask=None, gamma=GAMMA):
     """BaristaNet.full_pass (baristanet.py:138-140) = net.forward(); net.backward().
 
     Inputs in the reference's MEMORY_DATA shapes: state/next_state (B,4,S,S),
@@ -256,7 +256,7 @@ def full_pass(pQ, pP, state, action, reward, next_state, non_terminal, routes=No
     Q, P = cq["out"], cp["out"]
     q_sa = (Q * act).sum(axis=1)                    # :386-422 PROD, SLICE, SUM
     p_sa = P.max(axis=1) * nt                       # :429-464 SLICE, MAX, PROD
-    target = GAMMA * p_sa + 1.0 * r                 # :465-476 SUM coeff 0.85, 1
+    target = gamma * p_sa + 1.0 * r                 # :465-476 SUM coeff 0.85, 1 (gamma: the net's)
     diff = q_sa - target
     loss = float(diff @ diff) / B / 2.0             # EUCLIDEAN_LOSS :477-483
 
