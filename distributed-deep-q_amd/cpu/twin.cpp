@@ -93,10 +93,14 @@ struct ddq_ctx {
   // blobs of the last forward
   std::vector<float> q_out, p_out, q_sa, p_sa, target;
   float loss = 0.f;
-  Tower tw[3];                   // Q on state, P on next_state, Q on next_state (DOUBLE)
+  Tower tw[4];                   // Q on state, P on next_state, Q on next_state (DOUBLE),
+                                 // P on state (Munchausen, alpha != 0)
   // selectable objective (ddq_set_objective) and its two blobs
   ddq_objective obj{DDQ_TARGET_MAX, DDQ_LOSS_EUCLIDEAN, 0.f, 0};
   std::vector<float> qn_out, dq_out;
+  // Munchausen / soft-Q target (ddq_set_munchausen) and its two blobs
+  ddq_munchausen_cfg munch{0, 0.f, 0.f, 0.f};
+  std::vector<float> pc_out, m_bonus;
   int32_t act_path = DDQ_ACT_BATCH;   // ddq_set_acting_path: stored (one forward here)
   // replay ring (replay.py:23-68)
   std::vector<uint8_t> r_state, r_action, r_nonterm;
@@ -379,6 +383,22 @@ int forward_backward(ddq_ctx* c) {
     tower_fwd(c, 2, c->next_state.data(), B, 0);
     c->qn_out = c->tw[2].out;
   }
+  // Munchausen: the soft value and log-policy bonus in double, rounded once each
+  const bool munch = c->munch.enabled != 0, pcs = munch && c->munch.alpha != 0.f;
+  if (pcs) {   // P(s, .) under theta_P
+    tower_fwd(c, 3, c->state.data(), B, 1);
+    c->pc_out = c->tw[3].out;
+  }
+  if (munch) c->m_bonus.assign(B, 0.f);
+  // lse = log sum_a exp((v[a] - m) / tau), m = max_a v[a]
+  auto lse4 = [&](const float* v, double& m) {
+    const double tau = c->munch.tau;
+    m = v[0];
+    for (int a = 1; a < kA; ++a) m = std::max(m, (double)v[a]);
+    double s = 0.0;
+    for (int a = 0; a < kA; ++a) s += std::exp((v[a] - m) / tau);
+    return std::log(s);
+  };
   const Tower& q = c->tw[0];
   const Tower& p = c->tw[1];
   c->q_out = q.out;
@@ -403,9 +423,26 @@ int forward_backward(ddq_ctx* c) {
         if (qn[a] > qn[best]) best = a;
       pm = p.out[(size_t)b * kA + best];
     }
+    double bonus = 0.0;
+    if (munch) {
+      double m;
+      const double lse = lse4(p.out.data() + (size_t)b * kA, m);
+      pm = m + (double)c->munch.tau * lse;                       // V'
+      if (pcs) {
+        const float* pc = c->pc_out.data() + (size_t)b * kA;
+        const float* ac = c->action.data() + (size_t)b * kA;
+        const int at = ac[0] != 0.f ? 0 : (ac[1] != 0.f ? 1 : (ac[2] != 0.f ? 2 : 3));
+        double mc;
+        const double lsec = lse4(pc, mc);
+        const double lp = (pc[at] - mc) / (double)c->munch.tau - lsec;
+        bonus = (float)((double)c->munch.alpha *
+                        std::min(std::max((double)c->munch.tau * lp, (double)c->munch.clip_lo), 0.0));
+      }
+      c->m_bonus[b] = (float)bonus;
+    }
     const float qsf = (float)qs;
     const float psf = (float)(pm * c->nonterm[b]);
-    const float tg = (float)((double)c->gamma * psf + 1.0 * c->reward[b]);
+    const float tg = (float)((double)c->gamma * psf + (1.0 * c->reward[b] + bonus));
     c->q_sa[b] = qsf; c->p_sa[b] = psf; c->target[b] = tg;
     const double diff = (double)qsf - tg;
     double dc = diff;
@@ -721,6 +758,7 @@ int ddq_create(ddq_ctx** out, int device, const ddq_net_desc* d) {
   c->q_out.assign((size_t)c->B * kA, 0.f); c->p_out.assign((size_t)c->B * kA, 0.f);
   c->q_sa.assign(c->B, 0.f); c->p_sa.assign(c->B, 0.f); c->target.assign(c->B, 0.f);
   c->qn_out.assign((size_t)c->B * kA, 0.f); c->dq_out.assign((size_t)c->B * kA, 0.f);
+  c->pc_out.assign((size_t)c->B * kA, 0.f); c->m_bonus.assign((size_t)c->B, 0.f);
   *out = c;
   return DDQ_OK;
 }
@@ -1243,6 +1281,9 @@ int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
   if (o->loss == DDQ_LOSS_HUBER && !(std::isfinite(o->huber_delta) && o->huber_delta > 0.f))
     return fail(c, DDQ_EINVAL, "huber_delta must be finite and > 0 (got %g)", (double)o->huber_delta);
   if (o->reserved != 0) return fail(c, DDQ_EINVAL, "reserved must be 0");
+  if (o->target == DDQ_TARGET_DOUBLE && c->munch.enabled)
+    return fail(c, DDQ_EINVAL, "the double target with the Munchausen target on: turn that off "
+                               "first (ddq_set_munchausen)");
   c->obj = *o;
   if (o->loss != DDQ_LOSS_HUBER) c->obj.huber_delta = 0.f;
   return DDQ_OK;
@@ -1251,6 +1292,35 @@ int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
 int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
   if (!c || !o) return fail(nullptr, DDQ_EINVAL, "null argument");
   *o = c->obj;
+  return DDQ_OK;
+}
+
+// ---- Munchausen / soft-Q target ----
+int ddq_set_munchausen(ddq_ctx* c, const ddq_munchausen_cfg* m) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!m) return fail(c, DDQ_EINVAL, "null munchausen cfg");
+  if (m->enabled != 0 && m->enabled != 1)
+    return fail(c, DDQ_EINVAL, "enabled must be 0 or 1 (got %d)", (int)m->enabled);
+  if (!m->enabled) {
+    c->munch = ddq_munchausen_cfg{0, 0.f, 0.f, 0.f};
+    return DDQ_OK;
+  }
+  if (!(m->alpha >= 0.f && m->alpha <= 1.f))
+    return fail(c, DDQ_EINVAL, "alpha must be in [0, 1] (got %g)", (double)m->alpha);
+  if (!(std::isfinite(m->tau) && m->tau > 0.f))
+    return fail(c, DDQ_EINVAL, "tau must be finite and > 0 (got %g)", (double)m->tau);
+  if (!(std::isfinite(m->clip_lo) && m->clip_lo < 0.f))
+    return fail(c, DDQ_EINVAL, "clip_lo must be finite and < 0 (got %g)", (double)m->clip_lo);
+  if (c->obj.target == DDQ_TARGET_DOUBLE)
+    return fail(c, DDQ_EINVAL, "the Munchausen target with the double target: set "
+                               "DDQ_TARGET_MAX first (ddq_set_objective)");
+  c->munch = *m;
+  return DDQ_OK;
+}
+
+int ddq_get_munchausen(const ddq_ctx* c, ddq_munchausen_cfg* m) {
+  if (!c || !m) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *m = c->munch;
   return DDQ_OK;
 }
 
@@ -1285,7 +1355,8 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"target_Q_sa", c->target.data(), c->B}, {"loss", &c->loss, 1},
       {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B},
       {"is_weight", c->isw.data(), c->B},       {"grad_norm", &c->gnorm, 1},
-      {"aug_shift", c->aug_shift.data(), 4ll * c->B}};
+      {"aug_shift", c->aug_shift.data(), 4ll * c->B}, {"Pc_out", c->pc_out.data(), 4ll * c->B},
+      {"m_bonus", c->m_bonus.data(), c->B}};
   for (auto& e : t)
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
@@ -1298,6 +1369,11 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
         return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       if (!strcmp(name, "Qn_out") && c->obj.target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
+      if (!strcmp(name, "m_bonus") && !c->munch.enabled)
+        return fail(c, DDQ_ESTATE, "blob m_bonus exists while the Munchausen target is on");
+      if (!strcmp(name, "Pc_out") && !(c->munch.enabled && c->munch.alpha != 0.f))
+        return fail(c, DDQ_ESTATE, "blob Pc_out exists while the Munchausen target is on with "
+                                   "alpha != 0");
       std::copy(e.p, e.p + n, dst);
       return DDQ_OK;
     }

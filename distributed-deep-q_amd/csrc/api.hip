@@ -477,6 +477,28 @@ static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
   return DDQ_OK;
 }
 
+// Munchausen target (ddq_set_munchausen) with alpha != 0: P(s,.) under theta_P for
+// the minibatch view the pass trains on, the pass's first launch group -- the
+// acting forward's kernels at n = B over nb.mb.state with the P tower's
+// parameters and split copies (launch_act's tower argument), in the acting
+// scratch, into the ctx's Pc_out buffer.  It depends on theta_P and the bound
+// view only: stream order after the previous step's apply -- which is also what
+// writes P on a sync or Polyak step -- is enough.  Profile names: "pc_<kernel>".
+static void pc_mark(void* a, const char* name) {
+  const std::string s = std::string("pc_") + name;
+  (*reinterpret_cast<const Marks*>(a))(s.c_str());
+}
+static hipError_t launch_pc_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
+  return launch_act(nb, nb.mb.state, nb.B, c->act.act_p3, c->act.act_h4, c->act.act_part, nb.pc_out,
+                    nullptr, c->act.act_p1s, c->act.act_p2s, c->stream, m, c->act.act_path, 1);
+}
+static int enqueue_pc_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
+  if (!nb.m_on || nb.m_alpha == 0.f) return DDQ_OK;
+  const Marks pc = m.fn ? Marks{pc_mark, &m} : Marks{};
+  HIP_TRY(c, launch_pc_forward(c, nb, pc));
+  return DDQ_OK;
+}
+
 // The gradient launches of a step as sl.plan has them; fc4_done: the
 // overlapped all-reduce's start, its argument the ctx (launch_backward).
 // (one stream: forking the weight-gradient kernels onto a side stream cost
@@ -485,6 +507,7 @@ static int enqueue_qn_forward(ddq_ctx* c, const NetBuffers& nb, Marks m) {
 int ddq::enqueue_fwd_bwd(ddq_ctx* c, const NetBuffers& nb, const StepLaunch& sl, Marks m,
                          Fc4Done fc4_done, const NetBuffers* prio_next, uint64_t prio_seed) {
   TRY(enqueue_qn_forward(c, nb, m));
+  TRY(enqueue_pc_forward(c, nb, m));
   if (nb.small) {
     HIP_TRY(c, launch_small_fwd_head(nb, sl, c->stream, m));
   } else {
@@ -543,6 +566,9 @@ int ddq_set_objective(ddq_ctx* c, const ddq_objective* o) {
   if (o->loss == DDQ_LOSS_HUBER && !(std::isfinite(o->huber_delta) && o->huber_delta > 0.f))
     return fail(c, DDQ_EINVAL, "huber_delta must be finite and > 0 (got %g)", (double)o->huber_delta);
   if (o->reserved != 0) return fail(c, DDQ_EINVAL, "reserved must be 0");
+  if (o->target == DDQ_TARGET_DOUBLE && c->nb.m_on)
+    return fail(c, DDQ_EINVAL, "the double target with the Munchausen target on: turn that off "
+                               "first (ddq_set_munchausen)");
   if (c->async.async_on)
     return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: set the objective "
                                "before ddq_async_begin");
@@ -570,6 +596,54 @@ int ddq_get_objective(const ddq_ctx* c, ddq_objective* o) {
   return DDQ_OK;
 }
 
+// ---------------- Munchausen / soft-Q target ----------------
+int ddq_set_munchausen(ddq_ctx* c, const ddq_munchausen_cfg* m) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!m) return fail(c, DDQ_EINVAL, "null munchausen cfg");
+  if (m->enabled != 0 && m->enabled != 1)
+    return fail(c, DDQ_EINVAL, "enabled must be 0 or 1 (got %d)", (int)m->enabled);
+  if (m->enabled) {
+    if (!(m->alpha >= 0.f && m->alpha <= 1.f))
+      return fail(c, DDQ_EINVAL, "alpha must be in [0, 1] (got %g)", (double)m->alpha);
+    if (!(std::isfinite(m->tau) && m->tau > 0.f))
+      return fail(c, DDQ_EINVAL, "tau must be finite and > 0 (got %g)", (double)m->tau);
+    if (!(std::isfinite(m->clip_lo) && m->clip_lo < 0.f))
+      return fail(c, DDQ_EINVAL, "clip_lo must be finite and < 0 (got %g)", (double)m->clip_lo);
+    if (c->nb.obj_target == DDQ_TARGET_DOUBLE)
+      return fail(c, DDQ_EINVAL, "the Munchausen target with the double target: set "
+                                 "DDQ_TARGET_MAX first (ddq_set_objective)");
+  }
+  if (c->async.async_on)
+    return fail(c, DDQ_ESTATE, "the async exchange is in progress on this ctx: set the Munchausen "
+                               "target before ddq_async_begin");
+  TRY(set_dev(c));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  invalidate_graph(c);   // captured steps hold (or lack) the extra forward and the head's constants
+  NetBuffers& nb = c->nb;
+  if (!m->enabled) {
+    nb.m_on = 0;
+    nb.m_alpha = nb.m_tau = nb.m_clip = 0.f;
+    return DDQ_OK;
+  }
+  if (!nb.pc_out) TRY(dalloc(c, &nb.pc_out, (size_t)nb.B * 4));
+  if (!nb.m_bonus) TRY(dalloc(c, &nb.m_bonus, (size_t)nb.B));
+  if (m->alpha != 0.f) {
+    // one run of the extra forward now: its kernels' function attributes are set
+    // outside any capture (the result is overwritten by the first pass)
+    HIP_TRY(c, launch_pc_forward(c, nb, {}));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  nb.m_on = 1;
+  nb.m_alpha = m->alpha; nb.m_tau = m->tau; nb.m_clip = m->clip_lo;
+  return DDQ_OK;
+}
+
+int ddq_get_munchausen(const ddq_ctx* c, ddq_munchausen_cfg* m) {
+  if (!c || !m) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *m = ddq_munchausen_cfg{c->nb.m_on, c->nb.m_alpha, c->nb.m_tau, c->nb.m_clip};
+  return DDQ_OK;
+}
+
 // ---------------- acting path ----------------
 int ddq_set_acting_path(ddq_ctx* c, int32_t path) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
@@ -577,7 +651,7 @@ int ddq_set_acting_path(ddq_ctx* c, int32_t path) {
     return fail(c, DDQ_EINVAL, "unknown acting path %d", (int)path);
   TRY(set_dev(c));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  invalidate_graph(c);   // captured steps hold the Qn_out forward's launches
+  invalidate_graph(c);   // captured steps hold the Qn_out / Pc_out forward's launches
   NetBuffers& nb = c->nb;
   c->act.act_path = path;
   if (path != DDQ_ACT_BATCH && !nb.small) {
@@ -615,7 +689,8 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"target_Q_sa", c->nb.target, B}, {"loss", c->nb.loss, 1},
       {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B},
       {"is_weight", c->nb.mb.isw, B},       {"grad_norm", c->nb.gnorm, 1},
-      {"aug_shift", c->nb.mb.shift, 4ll * B}};
+      {"aug_shift", c->nb.mb.shift, 4ll * B}, {"Pc_out", c->nb.pc_out, 4ll * B},
+      {"m_bonus", c->nb.m_bonus, B}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
@@ -623,6 +698,11 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
         return fail(c, DDQ_ESTATE, "blob grad_norm exists while Adam's gradient clipping is on");
       if (!strcmp(name, "Qn_out") && c->nb.obj_target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
+      if (!strcmp(name, "m_bonus") && !c->nb.m_on)
+        return fail(c, DDQ_ESTATE, "blob m_bonus exists while the Munchausen target is on");
+      if (!strcmp(name, "Pc_out") && !(c->nb.m_on && c->nb.m_alpha != 0.f))
+        return fail(c, DDQ_ESTATE, "blob Pc_out exists while the Munchausen target is on with "
+                                   "alpha != 0");
       if (!strcmp(name, "aug_shift") && c->replay.aug_pad == 0)
         return fail(c, DDQ_ESTATE, "blob aug_shift exists while augmentation is on "
                                    "(ddq_replay_set_augment)");

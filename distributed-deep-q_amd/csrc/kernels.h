@@ -186,7 +186,13 @@ struct NetBuffers {
   int obj_target = 0, obj_loss = 0;
   float huber_delta = 0.f;
   float* qn_out = nullptr;
-  PrioTree prio{};                  // prioritized replay: the tree (leaf == nullptr: off)
+  // Munchausen / soft-Q target (ddq_set_munchausen, munchausen.h): m_on launches
+  // the heads' Munchausen instantiation; pc_out: P(s,.) under theta_P, (B,4),
+  // the pass's first launch group while m_alpha != 0; m_bonus (B)
+  int m_on = 0;
+  float m_alpha = 0.f, m_tau = 0.f, m_clip = 0.f;
+  float *pc_out = nullptr, *m_bonus = nullptr;
+  PrioTree prio{};               // prioritized replay: the tree (leaf == nullptr: off)
   // Adam (ddq_set_adam, adam.h): opt holds the first moment, opt2 the second;
   // gn_part: the gradient-norm launch's partials; gnorm: the last pre-clip norm
   float* opt2 = nullptr;
@@ -309,10 +315,13 @@ hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, in
 // Q-tower forward of n states (NHWC f32 in `in`) into scratch, argmax into out.
 // M: the launches' profile names (ddq_profile_step).  act_path
 // (ddq_set_acting_path): 0 launch_forward's convs, 1 the spread convs
-// (act_spread.h), 2 spread at n <= act_spread_max_n(S).
+// (act_spread.h), 2 spread at n <= act_spread_max_n(S).  tower: whose
+// parameters and derived split copies every launch reads, 0 = Q (every caller
+// but the Munchausen target's P(s,.) pass), 1 = P.
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s, Marks M = {}, int act_path = 0);
+                      __bf16* pool2s, hipStream_t s, Marks M = {}, int act_path = 0,
+                      int tower = 0);
 // The three convs of launch_act in their small-n form (act_spread.h): n images
 // of nb.mb.state through nb.pool1f[0] / pool2f[0] into nb.pool3[0]
 hipError_t launch_act_spread_convs(const NetBuffers& nb, int n, hipStream_t s, Marks M);

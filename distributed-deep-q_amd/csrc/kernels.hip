@@ -5,6 +5,7 @@
 #include "fc.h"
 #include "split.h"
 #include "small.h"
+#include "munchausen.h"
 #include "replay_dev.h"
 
 namespace ddq {
@@ -799,6 +800,11 @@ struct HeadArgs {
 static_assert(offsetof(HeadArgs, qn) == offsetof(HeadArgs, huber_delta) + 8 &&
                   sizeof(HeadArgs) == offsetof(HeadArgs, qn) + 8,
               "HeadArgs: the weight flag fills padding");
+// The Munchausen target's alpha, tau, l0 and two pointers (MunchArgs) are a
+// second argument of fc4_head_munch_kernel alone: grown by them, HeadArgs made
+// every head launch's kernarg segment 32 bytes longer, and the default
+// objective's launches are to stay what they were
+static_assert(sizeof(MunchArgs) == 32, "MunchArgs: three floats, padding, two pointers");
 
 template <bool NS>
 __device__ __forceinline__ void head_draw(const HeadArgs& H) {
@@ -875,11 +881,14 @@ hipError_t launch_tower_fwd16(const TowerArgs& t, hipStream_t s, bool ns) {
 }
 }  // namespace sm16
 
-// One head block b.  OBJ: the selectable objective's branches are compiled in
-// (fc4_head_obj_kernel); without it this is the reference objective's code and
-// nothing else, so the default launch keeps its instruction stream
-template <bool OBJ, bool NS>
-__device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) {
+// One head block b.  OBJ 1: the selectable objective's branches are compiled in
+// (fc4_head_obj_kernel); 2: those and the Munchausen target in the max's place
+// (fc4_head_munch_kernel; the double target is excluded with it); 0: this is the
+// reference objective's code and nothing else, so the default launch keeps its
+// instruction stream.  M: read at OBJ 2 only
+template <int OBJ, bool NS>
+__device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem,
+                                          const MunchArgs& M = MunchArgs{}) {
   const float* __restrict__ part = H.part;
   const int splits = H.splits, B = H.B;
   const float gamma = H.gamma;
@@ -1001,8 +1010,11 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
   qs += qp[1] * ac[1];
   qs += qp[2] * ac[2];
   qs += qp[3] * ac[3];
-  float ps;
-  if (!OBJ || H.obj_target == 0) {
+  float ps, tg;
+  if (OBJ == 2) {                                                // soft value, log-policy bonus
+    const float pn[4] = {qp[4], qp[5], qp[6], qp[7]};
+    tg = munch_target(M, pn, ac, b, gamma, rwb, ntb, n == 0, ps);
+  } else if (!OBJ || H.obj_target == 0) {
     ps = fmaxf(fmaxf(qp[4], qp[5]), fmaxf(qp[6], qp[7]));       // SLICE + MAX
   } else {                                                       // P at argmax_a Q(s',a)
     const float* qn = H.qn + b * 4;
@@ -1011,8 +1023,10 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
       if (qn[a] > qn[best]) best = a;                            // argmax_kernel: first max
     ps = qp[4 + best];
   }
-  ps = ps * ntb;                                                 // P_sa_or_term
-  const float tg = gamma * ps + 1.0f * rwb;                      // SUM coeff {0.85, 1}
+  if (OBJ != 2) {
+    ps = ps * ntb;                                               // P_sa_or_term
+    tg = gamma * ps + 1.0f * rwb;                                // SUM coeff {0.85, 1}
+  }
   const float diff = qs - tg;
   float gsc, le;
   if (!OBJ || H.obj_loss == 0) {
@@ -1045,12 +1059,15 @@ __device__ __forceinline__ void head_body(const HeadArgs& H, int b, char* smem) 
 template <bool NS>
 __global__ __launch_bounds__(512) void fc4_head_kernel(const HeadArgs H) {
   __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
-  head_body<false, NS>(H, blockIdx.x, smem);
+  head_body<0, NS>(H, blockIdx.x, smem);
 }
 // a non-default objective (HeadArgs::obj_*): the same body with its branches
 // (defined after the step's other kernels, below launch_act)
 template <bool NS>
 __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H);
+// the Munchausen target (M) with the loss / weight branches
+template <bool NS>
+__global__ __launch_bounds__(512) void fc4_head_munch_kernel(const HeadArgs H, const MunchArgs M);
 
 // Cross-sample head sums, run by the 8 trailing blocks of the wgrad slab
 // reduce: block hb owns fc4 units j = 64 hb + lane, 4 sample groups.
@@ -1302,6 +1319,18 @@ static Fc4DgradArgs fc4_dgrad_args(const NetBuffers& nb, bool& narrow, int& ndx,
   return f;
 }
 
+// The Munchausen builds' launches (ddq_set_munchausen) are defined at the end of
+// this file and their kernels first used there, so the compiler emits those
+// kernels after every other one: the code object up to them is what it is
+// without them, address for address (kernels added in the middle moved the
+// training kernels and cost the default deepq16 step 0.5 %, measured).
+namespace sm16 {
+struct ChainArgs;
+}
+static hipError_t launch_head_munch(const NetBuffers& nb, const HeadArgs& H, dim3 grid, hipStream_t s);
+static hipError_t launch_chain_munch(const NetBuffers& nb, const sm16::ChainArgs& c, bool one, bool soft,
+                                     dim3 grid, hipStream_t s, Marks M);
+
 hipError_t launch_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s) {
   sm16::BookArgs k;
   CHECK_LAUNCH(head_book(nb, sl, &k));
@@ -1309,6 +1338,7 @@ hipError_t launch_head(const NetBuffers& nb, const StepLaunch& sl, hipStream_t s
   if (H.obj_target && !H.qn) return hipErrorInvalidValue;
   const int extra = H.dmeta ? 1 : 0;   // the next step's draw: a block of its own
   const bool obj = H.obj_target || H.obj_loss || H.weighted;
+  if (nb.m_on) return launch_head_munch(nb, H, dim3(nb.B + 25 + 9 + extra), s);
   ddq_launch(nb.nstep > 1 ? (obj ? fc4_head_obj_kernel<true> : fc4_head_kernel<true>)
                           : (obj ? fc4_head_obj_kernel<false> : fc4_head_kernel<false>),
              dim3(nb.B + 25 + 9 + extra), dim3(kFc4), 0, s, H);
@@ -2135,8 +2165,10 @@ static sm16::TowerArgs tower_args(const NetBuffers& nb, int nz, const sm16::Book
   if (bk) t.bk = *bk;
   t.xchg = nb.xchg; t.pairc = nb.pairc;
   t.timeout = nb.csync ? nb.csync + 48 : nullptr;   // (csync: allocated at S = 16)
-  // K3's transposed weights, from this launch's Q weights (its extra blocks)
-  t.ntr = 25 + 9;
+  // K3's transposed weights, from this launch's Q weights (its extra blocks);
+  // none in launch_act's P-tower form (both slots hold P's copies: K3 never
+  // reads transposes of those)
+  t.ntr = nb.wks[0] == nb.wks[1] ? 0 : 25 + 9;
   t.wks2_off = L.wks_off[1]; t.wkst_off = L.wkst_off;
   t.wks3_off = L.wks_off[2]; t.wkst3_off = L.wkst3_off;
   return t;
@@ -2270,13 +2302,14 @@ hipError_t launch_small_fwd_head(const NetBuffers& nb, const StepLaunch& sl, hip
   if (soft)
     kern = obj ? (one ? sm16::fc4_chain16_obj_kernel<1, true> : sm16::fc4_chain16_obj_kernel<2, true>)
                : (one ? sm16::fc4_chain16_kernel<1, true> : sm16::fc4_chain16_kernel<2, true>);
+  const dim3 grid((one ? 2 : 1) * sm16::kFcBlk * c.G - (sl.plan.k2_short ? 1 : 0));
+  if (nb.m_on) return launch_chain_munch(nb, c, one, soft, grid, s, M);
   static std::atomic<uint64_t> attr[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
   CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern),
                               attr[(soft ? 4 : 0) + (obj ? 2 : 0) + (one ? 0 : 1)],
                               sm16::kChainSmem));
   M("fc4_chain");
-  ddq_launch(kern, dim3((one ? 2 : 1) * sm16::kFcBlk * c.G - (sl.plan.k2_short ? 1 : 0)), dim3(512),
-             sm16::kChainSmem, s, c);
+  ddq_launch(kern, grid, dim3(512), sm16::kChainSmem, s, c);
   CHECK_LAUNCH(hipGetLastError());
   return hipSuccess;
 }
@@ -2338,6 +2371,8 @@ hipError_t small_coresident(int B, int* ok, char* why, int nwhy) {
        512, sm16::kChainSmem, (G == 1 ? 2 : 1) * sm16::kFcBlk * G},
       {"wgrad16_soft", reinterpret_cast<const void*>(sm16::wgrad16_kernel<false, true>), 256,
        wgrad16_lds(), (G3 > 1 ? sm16::kT3 * G3 : 0) + (G2 > 1 ? sm16::kT2 * G2 : 0)},
+      // (K2 built with the Munchausen target has the obj build's launch: the same
+      // grid and the same kChainSmem of LDS, which alone sets one workgroup a CU)
   };
   for (const Launch& l : ls) {
     if (l.meeting == 0) continue;
@@ -2592,9 +2627,16 @@ int act_spread_max_n(int S) { return std::min(32, 98304 / (S * S)); }
 
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s, Marks M, int act_path) {
+                      __bf16* pool2s, hipStream_t s, Marks M, int act_path, int tower) {
   NetBuffers a = nb;
   a.B = n;
+  // tower 1: every launch below (the batch convs and fc4 of launch_forward, the
+  // spread convs, the small-map tower kernel) takes slot 0's parameters and
+  // split copies -- P's in both slots
+  if (tower) {
+    a.theta[0] = nb.theta[1];
+    a.wks[0] = nb.wks[1];
+  }
   a.mb.state = const_cast<float*>(in);
   a.mb.next_state = const_cast<float*>(in);
   a.pool3[0] = pool3; a.h4[0] = h4;
@@ -2623,7 +2665,7 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
 template <bool NS>
 __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
   __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
-  head_body<true, NS>(H, blockIdx.x, smem);
+  head_body<1, NS>(H, blockIdx.x, smem);
 }
 
 }  // namespace ddq
@@ -2637,3 +2679,43 @@ __global__ __launch_bounds__(512) void fc4_head_obj_kernel(const HeadArgs H) {
 #include "monitor.h"
 // the Adam rule's two kernels (two state words: not a case of apply_rule)
 #include "adam.h"
+
+// The Munchausen builds of the two heads and their launches, last in the file
+// (see launch_head_munch's declaration).
+namespace ddq {
+
+template <bool NS>
+__global__ __launch_bounds__(512) void fc4_head_munch_kernel(const HeadArgs H, const MunchArgs M) {
+  __shared__ __attribute__((aligned(16))) char smem[kWkstSmemB];
+  head_body<2, NS>(H, blockIdx.x, smem, M);
+}
+
+static bool munch_args(const NetBuffers& nb, MunchArgs* M) {
+  *M = MunchArgs{nb.m_alpha, nb.m_tau, nb.m_clip, nb.pc_out, nb.m_bonus};
+  return nb.obj_target == 0 && M->bonus && (M->alpha == 0.f || M->pc);
+}
+
+static hipError_t launch_head_munch(const NetBuffers& nb, const HeadArgs& H, dim3 grid, hipStream_t s) {
+  MunchArgs M;
+  if (!munch_args(nb, &M)) return hipErrorInvalidValue;
+  ddq_launch(nb.nstep > 1 ? fc4_head_munch_kernel<true> : fc4_head_munch_kernel<false>, grid,
+             dim3(kFc4), 0, s, H, M);
+  return hipGetLastError();
+}
+
+static hipError_t launch_chain_munch(const NetBuffers& nb, const sm16::ChainArgs& c, bool one, bool soft,
+                                     dim3 grid, hipStream_t s, Marks M) {
+  MunchArgs mu;
+  if (!munch_args(nb, &mu)) return hipErrorInvalidValue;
+  auto kern = soft ? (one ? sm16::fc4_chain16_munch_kernel<1, true> : sm16::fc4_chain16_munch_kernel<2, true>)
+                   : (one ? sm16::fc4_chain16_munch_kernel<1> : sm16::fc4_chain16_munch_kernel<2>);
+  static std::atomic<uint64_t> attr[4] = {{0}, {0}, {0}, {0}};
+  CHECK_LAUNCH(ensure_dyn_lds(reinterpret_cast<const void*>(kern), attr[(soft ? 2 : 0) + (one ? 0 : 1)],
+                              sm16::kChainSmem));
+  M("fc4_chain");
+  ddq_launch(kern, grid, dim3(512), sm16::kChainSmem, s, c, mu);
+  CHECK_LAUNCH(hipGetLastError());
+  return hipSuccess;
+}
+
+}  // namespace ddq

@@ -109,12 +109,13 @@ __device__ __forceinline__ float wave_sum(float v) {
 // NZ towers a workgroup: 1 (B <= 32: 64 workgroups, below) or 2 (B > 32: G
 // chunks of 32 images, 32 G workgroups -- all resident with the launch's
 // 159 KB of LDS only if each carries both towers)
-// OBJ: the selectable objective's branches are compiled in (fc4_chain16_obj_kernel);
-// without it the head loop is the reference objective's code and nothing else
+// OBJ 1: the selectable objective's branches are compiled in (fc4_chain16_obj_kernel);
+// 2: those and the Munchausen target in the max's place (fc4_chain16_munch_kernel);
+// 0: the head loop is the reference objective's code and nothing else
 // SOFT: a due target sync blends (ddq_set_target_tau < 1); without it the soft
 // form is compiled out and the default launch keeps its instruction stream
-template <int NZ, bool OBJ, bool SOFT>
-__device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
+template <int NZ, int OBJ, bool SOFT>
+__device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c, const MunchArgs& mu = MunchArgs{}) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int bid = blockIdx.x;
@@ -318,8 +319,12 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
     qs += qp[1] * ac[1];
     qs += qp[2] * ac[2];
     qs += qp[3] * ac[3];
-    float ps;
-    if (!OBJ || c.obj_target == 0) {
+    float ps, tg;
+    if (OBJ == 2) {                                // soft value of the final P_out, log-policy
+      const float pn[4] = {pp[0], pp[1], pp[2], pp[3]};   // bonus (munchausen.h)
+      tg = munch_target(mu, pn, ac, b, c.gamma, csm[CH_MB + 4 * B + b], csm[CH_MB + 5 * B + b],
+                        jb == 0, ps);
+    } else if (!OBJ || c.obj_target == 0) {
       ps = fmaxf(fmaxf(pp[0], pp[1]), fmaxf(pp[2], pp[3]));
     } else {                                       // P at the first maximum of Qn_out[b]
       const float4 qn = *reinterpret_cast<const float4*>(c.qn + b * 4);
@@ -330,8 +335,10 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
         if (qv[a] > qv[best]) best = a;
       ps = pp[best];
     }
-    ps = ps * csm[CH_MB + 5 * B + b];
-    const float tg = c.gamma * ps + 1.0f * csm[CH_MB + 4 * B + b];
+    if (OBJ != 2) {
+      ps = ps * csm[CH_MB + 5 * B + b];
+      tg = c.gamma * ps + 1.0f * csm[CH_MB + 4 * B + b];
+    }
     const float diff = qs - tg;
     float gsc, le;
     if (!OBJ || c.obj_loss == 0) {
@@ -503,12 +510,19 @@ __device__ __forceinline__ void fc4_chain16_body(const ChainArgs& c) {
 
 template <int NZ, bool SOFT = false>
 __global__ __launch_bounds__(512) void fc4_chain16_kernel(const ChainArgs c) {
-  fc4_chain16_body<NZ, false, SOFT>(c);
+  fc4_chain16_body<NZ, 0, SOFT>(c);
 }
 // a non-default objective (ChainArgs::obj_*): the same body with its branches
 template <int NZ, bool SOFT = false>
 __global__ __launch_bounds__(512) void fc4_chain16_obj_kernel(const ChainArgs c) {
-  fc4_chain16_body<NZ, true, SOFT>(c);
+  fc4_chain16_body<NZ, 1, SOFT>(c);
+}
+// the Munchausen target with the loss / weight branches; mu: its constants and
+// Pc_out (an argument as qn is, but of this kernel alone: ChainArgs, and with it
+// every other build's kernarg segment, stays as it was)
+template <int NZ, bool SOFT = false>
+__global__ __launch_bounds__(512) void fc4_chain16_munch_kernel(const ChainArgs c, const MunchArgs mu) {
+  fc4_chain16_body<NZ, 2, SOFT>(c, mu);
 }
 
 // ---------------------------------------------------------------------------

@@ -71,6 +71,12 @@ class Objective(ctypes.Structure):
                 ("huber_delta", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class MunchausenCfg(ctypes.Structure):
+    """include/ddq_hip.h ddq_munchausen_cfg (16 bytes)."""
+    _fields_ = [("enabled", ctypes.c_int32), ("alpha", ctypes.c_float),
+                ("tau", ctypes.c_float), ("clip_lo", ctypes.c_float)]
+
+
 class PriorityCfg(ctypes.Structure):
     """include/ddq_hip.h ddq_priority_cfg (16 bytes)."""
     _fields_ = [("enabled", ctypes.c_int32), ("alpha", ctypes.c_float),
@@ -164,6 +170,8 @@ _SIGS = {
     "ddq_forward_q": (ctypes.c_int, [_P]),
     "ddq_set_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
     "ddq_get_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
+    "ddq_set_munchausen": (ctypes.c_int, [_P, ctypes.POINTER(MunchausenCfg)]),
+    "ddq_get_munchausen": (ctypes.c_int, [_P, ctypes.POINTER(MunchausenCfg)]),
     "ddq_set_acting_path": (ctypes.c_int, [_P, _i32]),
     "ddq_get_acting_path": (ctypes.c_int, [_P, ctypes.POINTER(_i32)]),
     "ddq_read_blob": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _i64]),

@@ -3,7 +3,8 @@ with the same constructor and methods, computing on the MI355X.
 
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
 reset_log=False, objective=None, n_step=None, priority=None, target_tau=None,
-checkpoint=None, checkpoint_every=0, resume=None, acting_path=None, augment_pad=None)``:
+checkpoint=None, checkpoint_every=0, resume=None, acting_path=None, augment_pad=None,
+munchausen=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -15,6 +16,9 @@ checkpoint=None, checkpoint_every=0, resume=None, acting_path=None, augment_pad=
 * ``objective`` -- None (the reference's max target and Euclidean loss) or a dict
   of ``DeepQNet.set_objective`` arguments, e.g. ``{"target": "double", "loss":
   "huber", "huber_delta": 1.0}``;
+* ``munchausen`` -- None (off) or a dict of ``DeepQNet.set_munchausen`` arguments,
+  e.g. ``{"alpha": 0.9, "tau": 0.03, "clip": -1.0}``: the Munchausen-DQN target
+  (``alpha`` 0: Soft-DQN); not with the double target;
 * ``n_step`` -- None (the dataset's own n-step length, 1 unless it was made with
   ``ReplayDataset(n_step=)``) or the n of the n-step returns the minibatches are
   gathered for (``DeepQNet.replay_set_nstep``), set on every dataset added;
@@ -108,13 +112,15 @@ class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
                  reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
                  priority=None, target_tau=None, checkpoint=None, checkpoint_every=0,
-                 resume=None, acting_path=None, augment_pad=None):
+                 resume=None, acting_path=None, augment_pad=None, munchausen=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
         self.dqn = DeepQNet(batch=batch, frame=frame, device=device, gamma=gamma, mode=mode)
         if objective is not None:
             self.dqn.set_objective(**objective)
+        if munchausen is not None:
+            self.dqn.set_munchausen(**munchausen)
         if acting_path is not None:
             self.dqn.set_acting_path(acting_path)
         if model is not None and os.path.exists(str(model)):

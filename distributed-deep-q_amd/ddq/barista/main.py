@@ -9,6 +9,7 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
         [--dset-size 1000] [--overwrite] [--debug] [--initial-replay 20000]
         [--device-actor [--actor-seed N]] [--logpath PREFIX]
         [--double-q] [--huber-delta D] [--target-tau T]
+        [--munchausen-alpha A] [--munchausen-tau T] [--munchausen-clip L]
         [--acting-path batch|spread|auto]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
@@ -24,6 +25,13 @@ the replay add run inside the net's context (ddq_actor_step_async), so
 objective the gradients are computed for (``DeepQNet.set_objective``): the
 Double-DQN target r + gamma P(s', argmax_a Q(s',a)) in place of the max, and the
 Huber loss with band D in place of the Euclidean one.  Both work in either mode.
+
+``--munchausen-alpha A`` or ``--munchausen-tau T`` (off by default; either turns it
+on) select the Munchausen-DQN target (``DeepQNet.set_munchausen``): the soft value
+T logsumexp(P(s',.) / T) in the max's place and A clip(T ln pi(a | s), L, 0) added to
+the reward, L = ``--munchausen-clip`` (default -1).  Defaults A 0.9, T 0.03;
+``--munchausen-alpha 0 --munchausen-tau T`` is Soft-DQN.  Not with ``--double-q``.
+Either mode.
 
 ``--acting-path`` (default ``batch``) selects the kernels of every acting
 forward of the net's context (``DeepQNet.set_acting_path``): ``spread`` runs a
@@ -135,6 +143,12 @@ def get_args(argv=None):
                     help="Double-DQN target: P at argmax_a Q(s',a) instead of max_a P")
     ap.add_argument("--huber-delta", dest="huber_delta", type=float, default=None,
                     help="Huber loss with this band instead of the Euclidean loss")
+    ap.add_argument("--munchausen-alpha", dest="munchausen_alpha", type=float, default=None,
+                    help="Munchausen-DQN target with this bonus scale in [0, 1] (0: Soft-DQN)")
+    ap.add_argument("--munchausen-tau", dest="munchausen_tau", type=float, default=None,
+                    help="Munchausen-DQN target with this temperature, > 0 (default 0.03)")
+    ap.add_argument("--munchausen-clip", dest="munchausen_clip", type=float, default=None,
+                    help="Munchausen-DQN: lower clip of the scaled log-policy, < 0 (default -1)")
     ap.add_argument("--target-tau", dest="target_tau", type=float, default=None,
                     help="soft target updates: P <- P + T (Q - P) at every target sync, T in (0, 1]")
     ap.add_argument("--acting-path", dest="acting_path", default=None,
@@ -182,6 +196,17 @@ def get_args(argv=None):
         ap.error("--target-tau must be in (0, 1]")
     if args.huber_delta is not None and not args.huber_delta > 0:
         ap.error("--huber-delta must be > 0")
+    if args.munchausen_alpha is not None and not 0.0 <= args.munchausen_alpha <= 1.0:
+        ap.error("--munchausen-alpha must be in [0, 1]")
+    if args.munchausen_tau is not None and not args.munchausen_tau > 0:
+        ap.error("--munchausen-tau must be > 0")
+    if args.munchausen_clip is not None:
+        if args.munchausen_alpha is None and args.munchausen_tau is None:
+            ap.error("--munchausen-clip needs --munchausen-alpha or --munchausen-tau")
+        if not args.munchausen_clip < 0:
+            ap.error("--munchausen-clip must be < 0")
+    if args.double_q and munchausen_of(args) is not None:
+        ap.error("--double-q and the Munchausen target exclude each other")
     if args.driver == "None":
         args.driver = None
     return args
@@ -197,6 +222,16 @@ def objective_of(args):
     if delta is not None:
         obj["huber_delta"] = delta
     return obj
+
+
+def munchausen_of(args):
+    """BaristaNet's ``munchausen`` for --munchausen-alpha / -tau / -clip (None: off)."""
+    alpha, tau = getattr(args, "munchausen_alpha", None), getattr(args, "munchausen_tau", None)
+    if alpha is None and tau is None:
+        return None
+    clip = getattr(args, "munchausen_clip", None)
+    return {"alpha": 0.9 if alpha is None else alpha, "tau": 0.03 if tau is None else tau,
+            "clip": -1.0 if clip is None else clip}
 
 
 def priority_of(args):
@@ -216,7 +251,8 @@ def build_worker(args):
                      objective=objective_of(args), target_tau=getattr(args, "target_tau", None),
                      checkpoint=getattr(args, "checkpoint", None),
                      checkpoint_every=getattr(args, "checkpoint_every", 0),
-                     acting_path=getattr(args, "acting_path", None))
+                     acting_path=getattr(args, "acting_path", None),
+                     munchausen=munchausen_of(args))
     # --resume: loaded below, once everything the checkpoint holds exists on the
     # context (the ring, and the device actor when there is one); the initial
     # replay fill is the checkpoint's then

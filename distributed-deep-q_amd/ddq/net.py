@@ -21,7 +21,8 @@ NUM_ACTIONS = 4     # barista/constants.py:8
 NFRAME = 4          # expgain.py:9
 
 BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0,
-         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1, "grad_norm": 0, "aug_shift": 4}
+         "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1, "grad_norm": 0, "aug_shift": 4,
+         "Pc_out": 4, "m_bonus": 1}
 
 # include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
 MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
@@ -229,6 +230,27 @@ class DeepQNet:
         names = lambda d, v: next(k for k, x in d.items() if x == v)  # noqa: E731
         return {"target": names(_lib.TARGETS, o.target), "loss": names(_lib.LOSSES, o.loss),
                 "huber_delta": float(o.huber_delta)}
+
+    def set_munchausen(self, alpha=0.9, tau=0.03, clip=-1.0):
+        """The Munchausen-DQN target for every later gradient (ddq_set_munchausen):
+        the soft value tau logsumexp(P(s',.) / tau) in the max's place and the
+        bonus alpha clip(tau ln pi(a_t | s), clip, 0) added to the reward, pi the
+        softmax of P(s,.) / tau (blobs "Pc_out", "m_bonus").  alpha = 0 is
+        Soft-DQN and adds no launch.  ``set_munchausen(None)`` turns it off.  Not
+        with the double target."""
+        if alpha is None:
+            m = _lib.MunchausenCfg(0, 0.0, 0.0, 0.0)
+        else:
+            m = _lib.MunchausenCfg(1, float(alpha), float(tau), float(clip))
+        self._check(self.lib.ddq_set_munchausen(self.ctx, ctypes.byref(m)))
+
+    def munchausen(self):
+        """{"alpha", "tau", "clip"} as set_munchausen takes them, or None when off."""
+        m = _lib.MunchausenCfg()
+        self._check(self.lib.ddq_get_munchausen(self.ctx, ctypes.byref(m)))
+        if not m.enabled:
+            return None
+        return {"alpha": float(m.alpha), "tau": float(m.tau), "clip": float(m.clip_lo)}
 
     def set_acting_path(self, path):
         """Which convolution kernels the acting forward launches

@@ -65,7 +65,10 @@ extern "C" {
                               likewise; and the acting path (ddq_set_acting_path,
                               ddq_get_acting_path), likewise; and random-shift
                               augmentation (ddq_replay_set_augment,
-                              ddq_replay_get_augment; blob "aug_shift"), likewise */
+                              ddq_replay_get_augment; blob "aug_shift"), likewise; and
+                              the Munchausen / soft-Q target (ddq_set_munchausen,
+                              ddq_get_munchausen; blobs "Pc_out", "m_bonus"), new
+                              symbols only */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -568,6 +571,47 @@ typedef struct ddq_objective {      /* 16 bytes */
  * the async exchange has begun on the ctx. */
 int ddq_set_objective(ddq_ctx* ctx, const ddq_objective* obj);
 int ddq_get_objective(const ddq_ctx* ctx, ddq_objective* obj);
+
+/* ---------------- Munchausen / soft-Q target (no reference counterpart) ---- */
+/* Munchausen-DQN (Vieillard et al., 2020): a soft-max (entropy-regularised)
+ * bootstrap in place of the hard max, and the scaled, clipped log-policy of the
+ * taken action added to the reward -- both from the target tower alone, so
+ * theta's layout is untouched.  alpha = 0 is Soft-DQN.  Off (the default), every
+ * launch and every bit is what it is without this section.  Per image b, in
+ * fp32, every * / + - rounded on its own (no FMA contraction), expf / logf the
+ * device's; P' = P_out[b] = P(s',.), Pc = Pc_out[b] = P(s,.) under theta_P, a_t
+ * the one-hot's index, r and nt as the gather delivers them (n-step: R and w):
+ *   m'   = max_a P'[a]        lse' = logf(sum_a expf((P'[a] - m') / tau)), a = 0..3
+ *   V'   = m' + tau lse'      P_sa = V' nt
+ *   mc   = max_a Pc[a]        lsec = logf(sum_a expf((Pc[a] - mc) / tau))
+ *   lp   = (Pc[a_t] - mc) / tau - lsec                 (= ln pi(a_t | s) <= 0)
+ *   bonus = alpha min(max(tau lp, clip_lo), 0)         (alpha = 0: 0, Pc not read)
+ *   target = gamma P_sa + (r + bonus)
+ * From d = Q_sa - target on nothing changes: the loss of ddq_set_objective, the
+ * importance-sampling weights, the prioritized commit of |d|, dQ and every sum
+ * behind them.  Blob "P_sa" holds V' nt; the new blobs "Pc_out" (B,4) and
+ * "m_bonus" (B) are DDQ_ESTATE while the target is off, "Pc_out" also while
+ * alpha = 0.  With alpha != 0 every pass begins with a forward-only run of the P
+ * tower over the minibatch's state (the acting forward's kernels at n = B with
+ * theta_P and its derived copies, on the ctx stream, in the acting scratch;
+ * ddq_profile_step lists them as "pc_<name>"); with alpha = 0 no launch is added.
+ * A property of the ctx like the acting path: honoured by every call that
+ * computes a gradient (the list of the objective section), not written to
+ * checkpoints.  It excludes DDQ_TARGET_DOUBLE, in both directions. */
+typedef struct ddq_munchausen_cfg {   /* 16 bytes */
+  int32_t enabled;    /* 0 = off (default): every launch and bit as without this section */
+  float   alpha;      /* in [0, 1]; 0 = Soft-DQN, no P(s,.) pass                          */
+  float   tau;        /* finite, > 0                                                      */
+  float   clip_lo;    /* l0: finite, < 0                                                  */
+} ddq_munchausen_cfg;
+/* Synchronises, invalidates graphs, allocates the two blobs and runs the extra
+ * pass once (so none of its set-up happens inside a capture).  enabled = 0: the
+ * other fields are ignored.  DDQ_EINVAL (state unchanged): null cfg, enabled not
+ * 0 or 1, a value out of range or NaN, enabling while the ctx's target is
+ * DDQ_TARGET_DOUBLE (ddq_set_objective likewise refuses DOUBLE while this is
+ * on).  DDQ_ESTATE: the async exchange has begun on the ctx. */
+int ddq_set_munchausen(ddq_ctx* ctx, const ddq_munchausen_cfg* cfg);
+int ddq_get_munchausen(const ddq_ctx* ctx, ddq_munchausen_cfg* cfg);
 
 /* ---------------- acting path (no reference counterpart) ------------------- */
 /* Which convolution kernels the acting forward launches -- ddq_forward_q,
