@@ -102,6 +102,14 @@ struct ddq_ctx {
   ddq_munchausen_cfg munch{0, 0.f, 0.f, 0.f};
   std::vector<float> pc_out, m_bonus;
   int32_t act_path = DDQ_ACT_BATCH;   // ddq_set_acting_path: stored (one forward here)
+  // parameter-space noise (ddq_set_param_noise): theta~, the resamples and acting
+  // moves since the enable, the adapted sigma (cfg.sigma: as of the last
+  // ddq_synchronize) and the blobs of the last adapt
+  ddq_param_noise_cfg pn{};
+  std::vector<float> pn_theta, qa_out, pn_kl;
+  float pn_sigma = 0.f;
+  uint64_t pn_epoch = 0;
+  int64_t pn_moves = 0;
   // replay ring (replay.py:23-68)
   std::vector<uint8_t> r_state, r_action, r_nonterm;
   std::vector<int16_t> r_reward;
@@ -257,10 +265,11 @@ void dense(const float* x, int B, int K, int N, const float* W, const float* bia
     }
 }
 
-// tower slot z with the weights of tower zw (slot 2: Q's weights on next_state)
-void tower_fwd(ddq_ctx* c, int z, const float* frames, int B, int zw = -1) {
+// tower slot z with the weights of tower zw (slot 2: Q's weights on next_state),
+// or with the flat vector th (parameter-space noise)
+void tower_fwd(ddq_ctx* c, int z, const float* frames, int B, int zw = -1, const float* th = nullptr) {
   const Layout& L = c->L;
-  const float* th = c->theta[zw < 0 ? z : zw].data();
+  if (!th) th = c->theta[zw < 0 ? z : zw].data();
   Tower& t = c->tw[z];
   int H = c->S;
   t.x[0].assign(frames, frames + (size_t)B * kC * H * H);
@@ -723,6 +732,27 @@ void gather(ddq_ctx* c) {
   }
 }
 
+// parameter-space noise: theta~ of the current (seed, epoch) at the device sigma
+void pn_draw(ddq_ctx* c) {
+  const int64_t n = c->L.total;
+  const float* th = c->theta[0].data();
+  c->pn_theta.resize((size_t)n);
+  const uint64_t key = c->pn.seed ^ 0x8EBC6AF09C88C6E3ull, eb = c->pn_epoch * 0x100000001B3ull;
+  const float s = c->pn_sigma;
+#pragma omp parallel for schedule(static)
+  for (int64_t j = 0; j < (n + 1) / 2; ++j) {
+    const uint64_t w = prio_mix64(key ^ prio_mix64(eb + (uint64_t)j * 0x9E37ull));
+    const float u1 = (float)((uint32_t)(w >> 40) + 1u) * 0x1p-24f;
+    const float u2 = (float)((uint32_t)(w >> 16) & 0xFFFFFFu) * 0x1p-24f;
+    const float r = sqrtf(-2.f * logf(u1));
+    const float a = 6.2831855f * u2;
+    const float e0 = r * cosf(a), e1 = r * sinf(a);
+    const float d0 = s * e0, d1 = s * e1;
+    c->pn_theta[2 * j] = th[2 * j] + d0;
+    if (2 * j + 1 < n) c->pn_theta[2 * j + 1] = th[2 * j + 1] + d1;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -779,7 +809,11 @@ int ddq_get_stream(const ddq_ctx* c, void** s) {
   return DDQ_OK;
 }
 
-int ddq_synchronize(ddq_ctx* c) { return c ? DDQ_OK : fail(nullptr, DDQ_EINVAL, "null ctx"); }
+int ddq_synchronize(ddq_ctx* c) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (c->pn.enabled) c->pn.sigma = c->pn_sigma;   // the mirror of ddq_get_param_noise
+  return DDQ_OK;
+}
 
 int ddq_inject_fault(ddq_ctx* c, int32_t fault) {
   if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
@@ -1356,7 +1390,8 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Qn_out", c->qn_out.data(), 4ll * c->B}, {"Q_out.diff", c->dq_out.data(), 4ll * c->B},
       {"is_weight", c->isw.data(), c->B},       {"grad_norm", &c->gnorm, 1},
       {"aug_shift", c->aug_shift.data(), 4ll * c->B}, {"Pc_out", c->pc_out.data(), 4ll * c->B},
-      {"m_bonus", c->m_bonus.data(), c->B}};
+      {"m_bonus", c->m_bonus.data(), c->B},     {"Qa_out", c->qa_out.data(), 4ll * c->B},
+      {"pn_kl", c->pn_kl.data(), c->B},         {"pn_sigma", &c->pn_sigma, 1}};
   for (auto& e : t)
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
@@ -1369,6 +1404,9 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
         return fail(c, DDQ_ESTATE, "blob is_weight exists while prioritized replay is on");
       if (!strcmp(name, "Qn_out") && c->obj.target != DDQ_TARGET_DOUBLE)
         return fail(c, DDQ_ESTATE, "blob Qn_out exists under the double target only");
+      if ((!strcmp(name, "Qa_out") || !strncmp(name, "pn_", 3)) && !c->pn.enabled)
+        return fail(c, DDQ_ESTATE, "blob %s exists while parameter-space noise is on "
+                                   "(ddq_set_param_noise)", name);
       if (!strcmp(name, "m_bonus") && !c->munch.enabled)
         return fail(c, DDQ_ESTATE, "blob m_bonus exists while the Munchausen target is on");
       if (!strcmp(name, "Pc_out") && !(c->munch.enabled && c->munch.alpha != 0.f))
@@ -1392,14 +1430,29 @@ int ddq_read_pool_mask(ddq_ctx* c, int32_t layer, uint8_t* dst, int64_t n) {
   return DDQ_OK;
 }
 
-int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* actions) {
+// one acting move of ddq_select_action, the actor or the pool begins: the
+// resample_every rule of parameter-space noise
+static void pn_move(ddq_ctx* c) {
+  if (!c->pn.enabled) return;
+  const int64_t K = c->pn.resample_every;
+  if (K > 0 && c->pn_moves > 0 && c->pn_moves % K == 0) {
+    c->pn_epoch++;
+    pn_draw(c);
+  }
+  c->pn_moves++;
+}
+
+// noisy: the forward of such a move (on theta~ while parameter-space noise is on);
+// the evaluator's is never noisy
+static int select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* actions, bool noisy) {
   if (!c || !states || !actions) return fail(c, DDQ_EINVAL, "null argument");
   if (n < 1 || n > c->B) return fail(c, DDQ_EINVAL, "n must be in [1,B]");
   if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   const size_t e = (size_t)n * kC * c->S * c->S;
   std::vector<float> in(states, states + e);
   Tower keep = c->tw[0];            // acting does not touch the last training pass
-  tower_fwd(c, 0, in.data(), n);
+  const float* th = noisy && c->pn.enabled ? c->pn_theta.data() : nullptr;
+  tower_fwd(c, 0, in.data(), n, -1, th);
   for (int b = 0; b < n; ++b) {     // first maximum (the GPU's argmax)
     const float* q = c->tw[0].out.data() + (size_t)b * kA;
     int best = 0;
@@ -1408,6 +1461,108 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
     actions[b] = best;
   }
   c->tw[0] = std::move(keep);
+  return DDQ_OK;
+}
+
+int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* actions) {
+  if (c && states && actions && n >= 1 && n <= c->B && !c->restoring) pn_move(c);
+  return select_action(c, states, n, actions, true);
+}
+
+// ---- parameter-space noise (include/ddq_hip.h has the definition; csrc/param_noise.hip
+// on the device).  -ffp-contract=off: every operation rounds on its own ----
+int ddq_set_param_noise(ddq_ctx* c, const ddq_param_noise_cfg* p) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!p) return fail(c, DDQ_EINVAL, "null param noise cfg");
+  if (p->enabled != 0 && p->enabled != 1)
+    return fail(c, DDQ_EINVAL, "enabled must be 0 or 1 (got %d)", (int)p->enabled);
+  if (p->reserved != 0) return fail(c, DDQ_EINVAL, "reserved must be 0");
+  if (!p->enabled) {
+    c->pn = ddq_param_noise_cfg{};
+    return DDQ_OK;
+  }
+  if (!(std::isfinite(p->sigma) && p->sigma >= 0.f))
+    return fail(c, DDQ_EINVAL, "sigma must be finite and >= 0 (got %g)", (double)p->sigma);
+  if (!(std::isfinite(p->delta) && p->delta > 0.f))
+    return fail(c, DDQ_EINVAL, "delta must be finite and > 0 (got %g)", (double)p->delta);
+  if (!(std::isfinite(p->adapt_coef) && p->adapt_coef > 1.f))
+    return fail(c, DDQ_EINVAL, "adapt_coef must be finite and > 1 (got %g)", (double)p->adapt_coef);
+  if (p->resample_every < 0)
+    return fail(c, DDQ_EINVAL, "resample_every must be >= 0 (got %d)", (int)p->resample_every);
+  if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
+  c->pn = *p;
+  c->pn_sigma = p->sigma;
+  c->pn_epoch = 0;
+  c->pn_moves = 0;
+  c->qa_out.assign((size_t)4 * c->B, 0.f);
+  c->pn_kl.assign((size_t)c->B, 0.f);
+  pn_draw(c);
+  return DDQ_OK;
+}
+
+int ddq_get_param_noise(const ddq_ctx* c, ddq_param_noise_cfg* p) {
+  if (!c || !p) return fail(nullptr, DDQ_EINVAL, "null argument");
+  *p = c->pn;
+  return DDQ_OK;
+}
+
+static int pn_on(ddq_ctx* c, const char* what) {
+  if (!c) return fail(nullptr, DDQ_EINVAL, "null ctx");
+  if (!c->pn.enabled)
+    return fail(c, DDQ_ESTATE, "%s: parameter-space noise is off (ddq_set_param_noise)", what);
+  return not_restoring(c);
+}
+
+int ddq_param_noise_resample_async(ddq_ctx* c) {
+  const int rc = pn_on(c, "ddq_param_noise_resample_async");
+  if (rc != DDQ_OK) return rc;
+  c->pn_epoch++;
+  pn_draw(c);
+  return DDQ_OK;
+}
+
+int ddq_param_noise_adapt_async(ddq_ctx* c) {
+  const int rc = pn_on(c, "ddq_param_noise_adapt_async");
+  if (rc != DDQ_OK) return rc;
+  c->pn_epoch++;
+  pn_draw(c);
+  Tower keep = c->tw[0];
+  tower_fwd(c, 0, c->state.data(), c->B);
+  const std::vector<float> q = c->tw[0].out;
+  tower_fwd(c, 0, c->state.data(), c->B, -1, c->pn_theta.data());
+  c->qa_out = c->tw[0].out;
+  c->tw[0] = std::move(keep);
+  auto lse4 = [](const float* v, float* m) {
+    *m = std::max(std::max(v[0], v[1]), std::max(v[2], v[3]));
+    float s = expf(v[0] - *m);
+    for (int a = 1; a < kA; ++a) s = s + expf(v[a] - *m);
+    return logf(s);
+  };
+  float sum = 0.f;
+  for (int b = 0; b < c->B; ++b) {
+    const float *x = q.data() + (size_t)b * kA, *y = c->qa_out.data() + (size_t)b * kA;
+    float m, mn;
+    const float lse = lse4(x, &m), lsen = lse4(y, &mn);
+    float kl = 0.f;
+    for (int a = 0; a < kA; ++a) {
+      const float lp = (x[a] - m) - lse, lq = (y[a] - mn) - lsen;
+      const float t = expf(lp) * (lp - lq);
+      kl = a == 0 ? t : kl + t;
+    }
+    c->pn_kl[b] = kl;
+    sum = b == 0 ? kl : sum + kl;
+  }
+  const float mean = sum / (float)c->B;
+  c->pn_sigma = mean < c->pn.delta ? c->pn_sigma * c->pn.adapt_coef : c->pn_sigma / c->pn.adapt_coef;
+  return DDQ_OK;
+}
+
+int ddq_param_noise_params(ddq_ctx* c, float* dst, int64_t n) {
+  if (c && !dst) return fail(c, DDQ_EINVAL, "null argument");
+  const int rc = pn_on(c, "ddq_param_noise_params");
+  if (rc != DDQ_OK) return rc;
+  if (n != c->L.total) return fail(c, DDQ_EINVAL, "size mismatch");
+  std::copy(c->pn_theta.begin(), c->pn_theta.end(), dst);
   return DDQ_OK;
 }
 
@@ -1509,14 +1664,14 @@ void env_render(const int8_t boards[4][100], const std::vector<int32_t>& row,
 
 // every game's state (idle ones included) in one batched forward: the greedy actions
 template <class G>
-int env_greedy(ddq_ctx* c, const ddq_ctx::Env<G>& e, std::vector<int32_t>* greedy) {
+int env_greedy(ddq_ctx* c, const ddq_ctx::Env<G>& e, std::vector<int32_t>* greedy, bool noisy) {
   const int n = (int)e.games.size();
   const size_t fs = (size_t)kC * c->S * c->S;
   std::vector<uint8_t> frames(n * fs);
   for (int g = 0; g < n; ++g)
     env_render(e.games[g].boards, e.row, e.col, c->S, frames.data() + g * fs);
   greedy->resize(n);
-  return ddq_select_action(c, frames.data(), n, greedy->data());
+  return select_action(c, frames.data(), n, greedy->data(), noisy);
 }
 
 // SnakeGame.cpu_play on board cur: the board after the move into next (not
@@ -1599,11 +1754,12 @@ int ddq_actor_step_async(ddq_ctx* c, int32_t nsteps, int64_t iter_num) {
     // ExpGain.select_action: the coin first; the net is asked only when greedy
     Stream rng{g.seed, g.draws};
     int32_t act = 0;
+    pn_move(c);
     if (rng.coin(eps)) {
       act = (int32_t)rng.randrange(kA);
     } else {
       env_render(g.boards, c->a_env.row, c->a_env.col, c->S, frames.data());
-      const int rc = ddq_select_action(c, frames.data(), 1, &act);
+      const int rc = select_action(c, frames.data(), 1, &act, true);
       if (rc != DDQ_OK) return rc;
     }
     const int reward = env_move(g, act);
@@ -1658,7 +1814,7 @@ int ddq_eval_run_async(ddq_ctx* c, int32_t nmoves) {
   if (not_restoring(c) != DDQ_OK) return DDQ_ESTATE;
   std::vector<int32_t> greedy;
   for (int m = 0; m < nmoves; ++m) {
-    const int rc = env_greedy(c, c->e_env, &greedy);
+    const int rc = env_greedy(c, c->e_env, &greedy, false);
     if (rc != DDQ_OK) return rc;
     for (size_t g = 0; g < c->e_env.games.size(); ++g) {
       ddq_ctx::EvalGame& eg = c->e_env.games[g];
@@ -1735,7 +1891,8 @@ int ddq_actors_step_async(ddq_ctx* c, int32_t nmoves, int64_t iter_num) {
   const size_t fs = (size_t)kC * c->S * c->S;
   std::vector<int32_t> greedy;
   for (int m = 0; m < nmoves; ++m) {
-    const int rc = env_greedy(c, c->p_env, &greedy);
+    pn_move(c);
+    const int rc = env_greedy(c, c->p_env, &greedy, true);
     if (rc != DDQ_OK) return rc;
     const int64_t h = c->head;
     for (int g = 0; g < n; ++g) {
@@ -2349,6 +2506,7 @@ int ddq_state_commit(ddq_ctx* c) {
   c->p_h0 = k.pool_h0;
   c->p_v0 = k.pool_v0;
   c->p_moves = k.pool_moves;
+  c->pn = ddq_param_noise_cfg{};   // the noise state is not checkpointed: off until set again
   if (c->prio_on) c->prio_pmax = k.pmax;
   for (size_t g = 0; g < c->a_env.games.size(); ++g)
     game_unpack(c->st_actor.data() + g * kGameBytes, &c->a_env.games[g]);

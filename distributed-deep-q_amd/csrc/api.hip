@@ -293,6 +293,8 @@ int ddq_synchronize(ddq_ctx* c) {
   TRY(set_dev(c));
   if (c->comm.cs) HIP_TRY(c, hipStreamSynchronize(c->comm.cs));   // owner duties of async ticks
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->pn.on)                       // the adapted sigma's host mirror (ddq_get_param_noise)
+    HIP_TRY(c, hipMemcpy(&c->pn.cfg.sigma, c->pn.d_sigma, sizeof(float), hipMemcpyDeviceToHost));
   if (c->nb.csync) {                  // the small-map kernels' sticky spin-timeout words
     int32_t w[64];
     HIP_TRY(c, hipMemcpy(w, c->nb.csync, sizeof(w), hipMemcpyDeviceToHost));
@@ -690,7 +692,8 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       {"Qn_out", c->nb.qn_out, 4ll * B}, {"Q_out.diff", c->nb.dqbuf, 4ll * B},
       {"is_weight", c->nb.mb.isw, B},       {"grad_norm", c->nb.gnorm, 1},
       {"aug_shift", c->nb.mb.shift, 4ll * B}, {"Pc_out", c->nb.pc_out, 4ll * B},
-      {"m_bonus", c->nb.m_bonus, B}};
+      {"m_bonus", c->nb.m_bonus, B},       {"Qa_out", c->pn.q ? c->pn.q + 4ll * B : nullptr, 4ll * B},
+      {"pn_kl", c->pn.kl, B},               {"pn_sigma", c->pn.d_sigma, 1}};
   for (auto& e : t) {
     if (strcmp(e.nm, name) == 0) {
       if (n != e.cnt) return fail(c, DDQ_EINVAL, "blob %s has %lld elements", name, (long long)e.cnt);
@@ -703,6 +706,9 @@ int ddq_read_blob(ddq_ctx* c, const char* name, float* dst, int64_t n) {
       if (!strcmp(name, "Pc_out") && !(c->nb.m_on && c->nb.m_alpha != 0.f))
         return fail(c, DDQ_ESTATE, "blob Pc_out exists while the Munchausen target is on with "
                                    "alpha != 0");
+      if ((!strcmp(name, "Qa_out") || !strncmp(name, "pn_", 3)) && !c->pn.on)
+        return fail(c, DDQ_ESTATE, "blob %s exists while parameter-space noise is on "
+                                   "(ddq_set_param_noise)", name);
       if (!strcmp(name, "aug_shift") && c->replay.aug_pad == 0)
         return fail(c, DDQ_ESTATE, "blob aug_shift exists while augmentation is on "
                                    "(ddq_replay_set_augment)");
@@ -737,11 +743,13 @@ int ddq_select_action(ddq_ctx* c, const uint8_t* states, int32_t n, int32_t* act
   if (!c || !states || !actions) return fail(c, DDQ_EINVAL, "null argument");
   if (n < 1 || n > c->nb.B) return fail(c, DDQ_EINVAL, "n must be in [1,B]");
   TRY(guard(c));
+  const ActWeights* over = nullptr;
+  TRY(param_noise_move(c, &over));
   const size_t bytes = (size_t)n * 4 * c->nb.S * c->nb.S;
   HIP_TRY(c, hipMemcpyAsync(c->act.act_u8, states, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, launch_u8_to_nhwc(c->act.act_u8, n, c->nb.S, c->act.act_in, c->stream));
   HIP_TRY(c, launch_act(c->nb, c->act.act_in, n, c->act.act_p3, c->act.act_h4, c->act.act_part, c->act.act_q,
-                        c->act.act_out, c->act.act_p1s, c->act.act_p2s, c->stream, {}, c->act.act_path));
+                        c->act.act_out, c->act.act_p1s, c->act.act_p2s, c->stream, {}, c->act.act_path, 0, over));
   HIP_TRY(c, hipMemcpyAsync(actions, c->act.act_out, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return DDQ_OK;

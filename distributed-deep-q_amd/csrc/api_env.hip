@@ -133,10 +133,14 @@ static int env_create(ddq_ctx* c, EnvBufs<Game>* b, int room, const std::vector<
 // being the limit at 19 us of host enqueue per move;
 // profiles/eval_rate_graph_ab.json.  Not faster beyond the noise, so it is
 // not kept.)
+// The ring roles (the actor, the pool) act on the perturbed set while
+// parameter-space noise is on, and count the move; the evaluator never does.
 template <class Role, class Game>
 static int env_move(ddq_ctx* c, const Role& r, const EnvBufs<Game>& b, uint64_t thresh) {
+  const ActWeights* over = nullptr;
+  if (Role::kRing) TRY(param_noise_move(c, &over));
   HIP_TRY(c, launch_act(c->nb, b.in, b.n, c->act.act_p3, c->act.act_h4, c->act.act_part, c->act.act_q, nullptr,
-                        c->act.act_p1s, c->act.act_p2s, c->stream, {}, c->act.act_path));
+                        c->act.act_p1s, c->act.act_p2s, c->stream, {}, c->act.act_path, 0, over));
   HIP_TRY(c, launch_env(r, env_io(c, b), c->act.act_q, thresh, 1, c->stream));
   return DDQ_OK;
 }

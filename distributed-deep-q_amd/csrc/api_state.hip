@@ -332,6 +332,8 @@ int ddq_state_commit(ddq_ctx* c) {
   c->envs.p_h0 = k.pool_h0;
   c->envs.p_v0 = k.pool_v0;
   c->envs.p_moves = k.pool_moves;
+  c->pn.on = false;   // the noise state is not checkpointed: off until it is set again
+  c->pn.cfg = ddq_param_noise_cfg{};
   // ---- derived: the conv weights' copies of both towers, the games' rendered states ----
   for (int z = 0; z < 2; ++z) HIP_TRY(c, launch_relayout(c->nb, z, c->stream));
   if (c->envs.a_env.n)

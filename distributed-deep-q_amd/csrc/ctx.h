@@ -14,6 +14,7 @@
 
 #include "../../include/ddq_hip.h"
 #include "kernels.h"
+#include "param_noise.h"
 
 // the largest frame side: launch_wgrads_conv23 (wgrads.h) has forms for conv2
 // maps up to 64 x 64
@@ -151,6 +152,21 @@ struct ddq_ctx {
     int32_t act_path = DDQ_ACT_BATCH;
   } act;
 
+  // api_param_noise.hip
+  struct ParamNoise {
+    // parameter-space noise (ddq_set_param_noise): w = (theta~, wks~), allocated by
+    // the first enable and kept; cfg.sigma mirrors *d_sigma as of the last
+    // ddq_synchronize; epoch: resamples since the enable; moves: acting moves
+    // since the enable (resample_every); q: (2, B, 4) Q and Q~ of the last adapt
+    // (blob "Qa_out" is the second half); kl: (B) blob "pn_kl"
+    bool on = false;
+    ddq_param_noise_cfg cfg{};
+    ddq::ActWeights w{nullptr, nullptr};
+    float *d_sigma = nullptr, *q = nullptr, *kl = nullptr;
+    uint64_t epoch = 0;
+    int64_t moves = 0;
+  } pn;
+
   // api_env.hip
   struct Envs {
     // device-resident Snake environments (env_create): the single actor
@@ -272,6 +288,10 @@ void mb_bind_weights(ddq_ctx* c, bool on);
 // api_replay.hip
 int prio_refuse(ddq_ctx* c, const char* what);
 bool too_few_slots(const ddq_ctx* c, int64_t batch);
+// api_param_noise.hip: one acting move of ddq_select_action, the device actor or
+// the pool is about to be enqueued -- the resample_every rule; *over <- the
+// perturbed set (nullptr while the feature is off)
+int param_noise_move(ddq_ctx* c, const ActWeights** over);
 // api_env.hip
 const char* actor_board_error(const int8_t* b);
 ActorRole actor_role(const ddq_ctx* c);

@@ -317,11 +317,17 @@ hipError_t launch_sum_slices(float* out, const float* in, int W, int64_t len, in
 // (ddq_set_acting_path): 0 launch_forward's convs, 1 the spread convs
 // (act_spread.h), 2 spread at n <= act_spread_max_n(S).  tower: whose
 // parameters and derived split copies every launch reads, 0 = Q (every caller
-// but the Munchausen target's P(s,.) pass), 1 = P.
+// but the Munchausen target's P(s,.) pass), 1 = P.  over: another flat vector and
+// its split forward copies in the tower's place (parameter-space noise: the
+// perturbed acting set of ddq_select_action, the device actor and the pool).
+struct ActWeights {
+  float* theta;
+  __bf16* wks;
+};
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
                       __bf16* pool2s, hipStream_t s, Marks M = {}, int act_path = 0,
-                      int tower = 0);
+                      int tower = 0, const ActWeights* over = nullptr);
 // The three convs of launch_act in their small-n form (act_spread.h): n images
 // of nb.mb.state through nb.pool1f[0] / pool2f[0] into nb.pool3[0]
 hipError_t launch_act_spread_convs(const NetBuffers& nb, int n, hipStream_t s, Marks M);

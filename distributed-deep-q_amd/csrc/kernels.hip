@@ -2627,7 +2627,8 @@ int act_spread_max_n(int S) { return std::min(32, 98304 / (S * S)); }
 
 hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3, float* h4,
                       float* part, float* qout, int32_t* actions, __bf16* pool1s,
-                      __bf16* pool2s, hipStream_t s, Marks M, int act_path, int tower) {
+                      __bf16* pool2s, hipStream_t s, Marks M, int act_path, int tower,
+                      const ActWeights* over) {
   NetBuffers a = nb;
   a.B = n;
   // tower 1: every launch below (the batch convs and fc4 of launch_forward, the
@@ -2636,6 +2637,10 @@ hipError_t launch_act(const NetBuffers& nb, const float* in, int n, float* pool3
   if (tower) {
     a.theta[0] = nb.theta[1];
     a.wks[0] = nb.wks[1];
+  }
+  if (over) {
+    a.theta[0] = over->theta;
+    a.wks[0] = over->wks;
   }
   a.mb.state = const_cast<float*>(in);
   a.mb.next_state = const_cast<float*>(in);

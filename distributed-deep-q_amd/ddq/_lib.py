@@ -77,6 +77,14 @@ class MunchausenCfg(ctypes.Structure):
                 ("tau", ctypes.c_float), ("clip_lo", ctypes.c_float)]
 
 
+class ParamNoiseCfg(ctypes.Structure):
+    """include/ddq_hip.h ddq_param_noise_cfg (32 bytes)."""
+    _fields_ = [("enabled", ctypes.c_int32), ("sigma", ctypes.c_float),
+                ("delta", ctypes.c_float), ("adapt_coef", ctypes.c_float),
+                ("resample_every", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
+
+
 class PriorityCfg(ctypes.Structure):
     """include/ddq_hip.h ddq_priority_cfg (16 bytes)."""
     _fields_ = [("enabled", ctypes.c_int32), ("alpha", ctypes.c_float),
@@ -172,6 +180,11 @@ _SIGS = {
     "ddq_get_objective": (ctypes.c_int, [_P, ctypes.POINTER(Objective)]),
     "ddq_set_munchausen": (ctypes.c_int, [_P, ctypes.POINTER(MunchausenCfg)]),
     "ddq_get_munchausen": (ctypes.c_int, [_P, ctypes.POINTER(MunchausenCfg)]),
+    "ddq_set_param_noise": (ctypes.c_int, [_P, ctypes.POINTER(ParamNoiseCfg)]),
+    "ddq_get_param_noise": (ctypes.c_int, [_P, ctypes.POINTER(ParamNoiseCfg)]),
+    "ddq_param_noise_resample_async": (ctypes.c_int, [_P]),
+    "ddq_param_noise_adapt_async": (ctypes.c_int, [_P]),
+    "ddq_param_noise_params": (ctypes.c_int, [_P, _P, _i64]),
     "ddq_set_acting_path": (ctypes.c_int, [_P, _i32]),
     "ddq_get_acting_path": (ctypes.c_int, [_P, ctypes.POINTER(_i32)]),
     "ddq_read_blob": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _i64]),

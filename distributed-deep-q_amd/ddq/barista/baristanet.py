@@ -4,7 +4,7 @@ with the same constructor and methods, computing on the MI355X.
 ``BaristaNet(architecture, model, driver, dataset=None, logpath=None,
 reset_log=False, objective=None, n_step=None, priority=None, target_tau=None,
 checkpoint=None, checkpoint_every=0, resume=None, acting_path=None, augment_pad=None,
-munchausen=None)``:
+munchausen=None, param_noise=None)``:
 * ``architecture`` -- the deepq ``train_val.prototxt`` (its MEMORY_DATA dims and
   the target coefficient are read from the text; the layer graph itself is the
   fixed deepq network implemented in libddq_hip.so) or a dict
@@ -19,6 +19,12 @@ munchausen=None)``:
 * ``munchausen`` -- None (off) or a dict of ``DeepQNet.set_munchausen`` arguments,
   e.g. ``{"alpha": 0.9, "tau": 0.03, "clip": -1.0}``: the Munchausen-DQN target
   (``alpha`` 0: Soft-DQN); not with the double target;
+* ``param_noise`` -- None (off) or a dict of ``DeepQNet.set_param_noise`` arguments
+  plus ``adapt_every`` (default 50): ``select_action`` and the device actors act on
+  a perturbed copy of the Q parameters, and every ``adapt_every``-th ``full_pass``
+  is followed by ``DeepQNet.param_noise_adapt`` on its minibatch.  Set after the
+  model is loaded; not checkpointed: ``load_checkpoint`` sets it again, at the
+  initial sigma and a fresh epoch 0;
 * ``n_step`` -- None (the dataset's own n-step length, 1 unless it was made with
   ``ReplayDataset(n_step=)``) or the n of the n-step returns the minibatches are
   gathered for (``DeepQNet.replay_set_nstep``), set on every dataset added;
@@ -112,7 +118,8 @@ class BaristaNet:
     def __init__(self, architecture, model, driver, dataset=None, logpath=None,
                  reset_log=False, device=0, mode="gpu", objective=None, n_step=None,
                  priority=None, target_tau=None, checkpoint=None, checkpoint_every=0,
-                 resume=None, acting_path=None, augment_pad=None, munchausen=None):
+                 resume=None, acting_path=None, augment_pad=None, munchausen=None,
+                 param_noise=None):
         batch, frame, gamma = parse_architecture(architecture)
         # mode: main.py:149-151 caffe.set_mode_gpu / set_mode_cpu
         self.mode = mode
@@ -134,6 +141,11 @@ class BaristaNet:
         else:
             self.dqn.set_flat(0, P.init_params_flat(frame))
         self.dqn.sync_target()
+        self.param_noise = None if param_noise is None else dict(param_noise)
+        self.adapt_every, self._passes = 0, 0
+        if self.param_noise is not None:
+            self.adapt_every = int(self.param_noise.pop("adapt_every", 50))
+            self.dqn.set_param_noise(**self.param_noise)
         self.target_tau = None if target_tau is None else float(target_tau)
         if self.target_tau is not None:
             self.dqn.set_target_tau(self.target_tau)
@@ -229,6 +241,10 @@ class BaristaNet:
             v, words, gauss = meta["py_random"]
             random.setstate((v, tuple(words), gauss))
         self._resume = None
+        # the noise state is not in the file and the restore turns the feature off:
+        # set it again on the restored parameters (a fresh epoch 0 at the initial sigma)
+        if self.param_noise is not None:
+            self.dqn.set_param_noise(**self.param_noise)
         return meta
 
     def maybe_checkpoint(self, step_cfg=None):
@@ -321,6 +337,9 @@ class BaristaNet:
         loss = self.dqn.forward_backward()
         if self.dataset and self.dataset.priority is not None:
             self.dqn.replay_update_priorities()
+        self._passes += 1
+        if self.adapt_every > 0 and self._passes % self.adapt_every == 0:
+            self.dqn.param_noise_adapt()
         return loss
 
     def select_action(self, state, batch_size=1):

@@ -11,6 +11,7 @@ the forward/backward pass on the GPU, push the Q gradients, reply.
         [--double-q] [--huber-delta D] [--target-tau T]
         [--munchausen-alpha A] [--munchausen-tau T] [--munchausen-clip L]
         [--acting-path batch|spread|auto]
+        [--param-noise-sigma S] [--param-noise-eps E] [--param-noise-resample K]
 
 ``--mode gpu`` (default) runs libddq_hip.so; ``--mode cpu`` runs the same
 step on the host through the CPU twin libddq_cpu.so (main.py:128,149-151, the
@@ -32,6 +33,12 @@ T logsumexp(P(s',.) / T) in the max's place and A clip(T ln pi(a | s), L, 0) add
 the reward, L = ``--munchausen-clip`` (default -1).  Defaults A 0.9, T 0.03;
 ``--munchausen-alpha 0 --munchausen-tau T`` is Soft-DQN.  Not with ``--double-q``.
 Either mode.
+
+``--param-noise-sigma S`` (off by default) turns on parameter-space noise
+(``DeepQNet.set_param_noise``): every act runs on theta_Q + sigma eps, sigma starting
+at S and adapted towards the KL distance of epsilon-greedy at ``--param-noise-eps``
+(default 0.05); ``--param-noise-resample K`` (default 64) redraws the noise every K
+moves.  Epsilon-greedy stays on top of it.  Either mode.
 
 ``--acting-path`` (default ``batch``) selects the kernels of every acting
 forward of the net's context (``DeepQNet.set_acting_path``): ``spread`` runs a
@@ -149,6 +156,13 @@ def get_args(argv=None):
                     help="Munchausen-DQN target with this temperature, > 0 (default 0.03)")
     ap.add_argument("--munchausen-clip", dest="munchausen_clip", type=float, default=None,
                     help="Munchausen-DQN: lower clip of the scaled log-policy, < 0 (default -1)")
+    ap.add_argument("--param-noise-sigma", dest="param_noise_sigma", type=float, default=None,
+                    help="parameter-space noise with this initial sigma, >= 0 (default: off)")
+    ap.add_argument("--param-noise-eps", dest="param_noise_eps", type=float, default=None,
+                    help="parameter-space noise: the epsilon whose KL distance sigma is adapted "
+                         "to, in (0, 1) (default 0.05)")
+    ap.add_argument("--param-noise-resample", dest="param_noise_resample", type=int, default=None,
+                    help="parameter-space noise: moves between resamples, >= 0 (default 64)")
     ap.add_argument("--target-tau", dest="target_tau", type=float, default=None,
                     help="soft target updates: P <- P + T (Q - P) at every target sync, T in (0, 1]")
     ap.add_argument("--acting-path", dest="acting_path", default=None,
@@ -205,6 +219,15 @@ def get_args(argv=None):
             ap.error("--munchausen-clip needs --munchausen-alpha or --munchausen-tau")
         if not args.munchausen_clip < 0:
             ap.error("--munchausen-clip must be < 0")
+    if args.param_noise_sigma is None and (args.param_noise_eps is not None or
+                                           args.param_noise_resample is not None):
+        ap.error("--param-noise-eps / --param-noise-resample need --param-noise-sigma")
+    if args.param_noise_sigma is not None and not args.param_noise_sigma >= 0:
+        ap.error("--param-noise-sigma must be >= 0")
+    if args.param_noise_eps is not None and not 0.0 < args.param_noise_eps < 1.0:
+        ap.error("--param-noise-eps must be in (0, 1)")
+    if args.param_noise_resample is not None and args.param_noise_resample < 0:
+        ap.error("--param-noise-resample must be >= 0")
     if args.double_q and munchausen_of(args) is not None:
         ap.error("--double-q and the Munchausen target exclude each other")
     if args.driver == "None":
@@ -234,6 +257,16 @@ def munchausen_of(args):
             "clip": -1.0 if clip is None else clip}
 
 
+def param_noise_of(args):
+    """BaristaNet's ``param_noise`` for --param-noise-sigma / -eps / -resample (None: off)."""
+    sigma = getattr(args, "param_noise_sigma", None)
+    if sigma is None:
+        return None
+    eps, k = getattr(args, "param_noise_eps", None), getattr(args, "param_noise_resample", None)
+    return {"sigma": sigma, "eps_ref": 0.05 if eps is None else eps,
+            "resample_every": 64 if k is None else k}
+
+
 def priority_of(args):
     """ReplayDataset's ``priority`` for --per-alpha / --per-beta / --per-eps (None: off)."""
     alpha = getattr(args, "per_alpha", None)
@@ -252,7 +285,7 @@ def build_worker(args):
                      checkpoint=getattr(args, "checkpoint", None),
                      checkpoint_every=getattr(args, "checkpoint_every", 0),
                      acting_path=getattr(args, "acting_path", None),
-                     munchausen=munchausen_of(args))
+                     munchausen=munchausen_of(args), param_noise=param_noise_of(args))
     # --resume: loaded below, once everything the checkpoint holds exists on the
     # context (the ring, and the device actor when there is one); the initial
     # replay fill is the checkpoint's then

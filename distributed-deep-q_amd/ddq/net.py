@@ -22,7 +22,7 @@ NFRAME = 4          # expgain.py:9
 
 BLOBS = {"Q_out": 4, "P_out": 4, "Q_sa": 1, "P_sa": 1, "target_Q_sa": 1, "loss": 0,
          "Qn_out": 4, "Q_out.diff": 4, "is_weight": 1, "grad_norm": 0, "aug_shift": 4,
-         "Pc_out": 4, "m_bonus": 1}
+         "Pc_out": 4, "m_bonus": 1, "Qa_out": 4, "pn_kl": 1, "pn_sigma": 0}
 
 # include/ddq_hip.h ddq_monitor_record as a numpy structured dtype
 MONITOR_DTYPE = np.dtype([("iteration", "<i8"), ("tag", "<i8"), ("loss", "<f4"),
@@ -251,6 +251,51 @@ class DeepQNet:
         if not m.enabled:
             return None
         return {"alpha": float(m.alpha), "tau": float(m.tau), "clip": float(m.clip_lo)}
+
+    def set_param_noise(self, sigma=0.01, eps_ref=0.05, delta=None, adapt_coef=1.01,
+                        resample_every=0, seed=0):
+        """Parameter-space noise (ddq_set_param_noise): select_action, the device
+        actor and the pool act greedily on theta~ = theta_Q + sigma eps, redrawn by
+        param_noise_resample() / every ``resample_every`` moves; param_noise_adapt()
+        scales sigma by ``adapt_coef`` towards the KL distance ``delta`` (default:
+        that of epsilon-greedy at ``eps_ref``, -ln(1 - eps_ref + eps_ref / 4)).
+        forward_q, the evaluator and training never see theta~.
+        ``set_param_noise(None)`` turns it off.  Not checkpointed."""
+        if sigma is None:
+            p = _lib.ParamNoiseCfg()
+        else:
+            if delta is None:
+                delta = -np.log(1.0 - eps_ref + eps_ref / 4.0)
+            p = _lib.ParamNoiseCfg(1, float(sigma), float(delta), float(adapt_coef),
+                                   int(resample_every), 0, int(seed) & (2 ** 64 - 1))
+        self._check(self.lib.ddq_set_param_noise(self.ctx, ctypes.byref(p)))
+
+    @property
+    def param_noise(self):
+        """{"sigma", "delta", "adapt_coef", "resample_every", "seed"} or None when
+        off; sigma as adapted up to the last synchronize()."""
+        p = _lib.ParamNoiseCfg()
+        self._check(self.lib.ddq_get_param_noise(self.ctx, ctypes.byref(p)))
+        if not p.enabled:
+            return None
+        return {"sigma": float(p.sigma), "delta": float(p.delta),
+                "adapt_coef": float(p.adapt_coef), "resample_every": int(p.resample_every),
+                "seed": int(p.seed)}
+
+    def param_noise_resample(self):
+        """A fresh theta~ at the current sigma (asynchronous)."""
+        self._check(self.lib.ddq_param_noise_resample_async(self.ctx))
+
+    def param_noise_adapt(self):
+        """Resample, measure KL(pi || pi~) on the bound minibatch's states and adapt
+        sigma, all on the device (asynchronous; blobs "Qa_out", "pn_kl", "pn_sigma")."""
+        self._check(self.lib.ddq_param_noise_adapt_async(self.ctx))
+
+    def param_noise_params(self):
+        """theta~ as the acting launches read it (flat, the order of get_flat)."""
+        out = np.empty(self.num_params, np.float32)
+        self._check(self.lib.ddq_param_noise_params(self.ctx, ptr(out), out.size))
+        return out
 
     def set_acting_path(self, path):
         """Which convolution kernels the acting forward launches

@@ -67,8 +67,11 @@ extern "C" {
                               augmentation (ddq_replay_set_augment,
                               ddq_replay_get_augment; blob "aug_shift"), likewise; and
                               the Munchausen / soft-Q target (ddq_set_munchausen,
-                              ddq_get_munchausen; blobs "Pc_out", "m_bonus"), new
-                              symbols only */
+                              ddq_get_munchausen; blobs "Pc_out", "m_bonus"), likewise;
+                              and parameter-space noise (ddq_set_param_noise,
+                              ddq_get_param_noise, ddq_param_noise_resample_async,
+                              ddq_param_noise_adapt_async, ddq_param_noise_params;
+                              blobs "Qa_out", "pn_kl", "pn_sigma"), new symbols only */
 
 enum ddq_status {
   DDQ_OK = 0,
@@ -612,6 +615,71 @@ typedef struct ddq_munchausen_cfg {   /* 16 bytes */
  * on).  DDQ_ESTATE: the async exchange has begun on the ctx. */
 int ddq_set_munchausen(ddq_ctx* ctx, const ddq_munchausen_cfg* cfg);
 int ddq_get_munchausen(const ddq_ctx* ctx, ddq_munchausen_cfg* cfg);
+
+/* ---------------- parameter-space noise (no reference counterpart) ---------- */
+/* Exploration by acting greedily on a perturbed copy of the Q parameters
+ * (Plappert et al., 2017): theta~ = theta_Q + sigma eps, held fixed between
+ * resamples, sigma adapted so that the perturbed policy stays a chosen KL
+ * distance from the unperturbed one.  While on, exactly three callers act on
+ * theta~ and its derived split conv copies: ddq_select_action, the device actor
+ * (ddq_actor_step_async) and the actor pool (ddq_actors_step_async); epsilon-
+ * greedy keeps working on top.  ddq_forward_q, the evaluator, the double
+ * target's Qn_out pass, the Munchausen P pass and every training launch never
+ * do.  theta~ is one launch's snapshot: ddq_set_params, updates and syncs do not
+ * touch it, it is stale until the next resample.  Off (the default) and with
+ * sigma = 0 every action is what it is without this section.  A property of the
+ * ctx: not written to checkpoints, and ddq_state_commit turns it off
+ * (ddq_get_param_noise then reports enabled = 0).
+ *
+ * The noise.  Parameters 2j and 2j+1 of the flat order (ddq_param_layout)
+ * share the 64-bit word
+ *   w = splitmix64((seed ^ 0x8EBC6AF09C88C6E3)
+ *                  ^ splitmix64(epoch * 0x100000001B3 + j * 0x9E37))     (mod 2^64)
+ * epoch = 0 at the enable, + 1 with every resample.  In fp32, every operation
+ * rounded on its own (no FMA contraction), logf / sinf / cosf the device's:
+ *   u1 = ((w >> 40) + 1) * 2^-24            u2 = ((w >> 16) & 0xFFFFFF) * 2^-24
+ *   r  = sqrtf(-2 * logf(u1))               a  = 6.2831855f * u2
+ *   eps_{2j} = r * cosf(a)                  eps_{2j+1} = r * sinf(a)
+ *   theta~_i = theta_i + sigma * eps_i
+ * (an odd last parameter takes the cosine branch of its own word).
+ *
+ * ddq_param_noise_adapt_async, on the ctx stream, no synchronisation: a resample
+ * at the current sigma; Q = Q(s,.) under theta_Q and Q~ under theta~ over the
+ * bound minibatch's B states; per row, with m = max_a Q[a] and
+ * lse = logf(sum_a expf(Q[a] - m)) (a = 0..3; likewise m~, lse~ of Q~):
+ *   lp[a] = (Q[a] - m) - lse                lq[a] = (Q~[a] - m~) - lse~
+ *   kl    = sum_a expf(lp[a]) * (lp[a] - lq[a])
+ * the mean of the B values summed in row order, and
+ *   sigma <- mean < delta ? sigma * adapt_coef : sigma / adapt_coef
+ * in device memory: the next resample reads it there.  Blobs (DDQ_ESTATE while
+ * off): "Qa_out" (B,4) = Q~, "pn_kl" (B), "pn_sigma" (1). */
+typedef struct ddq_param_noise_cfg {   /* 32 bytes */
+  int32_t  enabled;         /* 0 = off (default); the other fields are then ignored        */
+  float    sigma;           /* finite, >= 0; get: as of the last ddq_synchronize            */
+  float    delta;           /* KL threshold, finite, > 0 (epsilon-greedy equivalent at
+                               eps_ref: -ln(1 - eps_ref + eps_ref / 4))                     */
+  float    adapt_coef;      /* c, finite, > 1 (1.01 is customary)                           */
+  int32_t  resample_every;  /* K >= 0; K > 0: before acting move n (n = 0 the first since
+                               the enable) a resample when n > 0 and n mod K = 0; a move
+                               is one ddq_select_action call or one move of an actor /
+                               pool step call; 0: explicit resamples only                   */
+  int32_t  reserved;        /* must be 0                                                    */
+  uint64_t seed;            /* of the noise stream                                          */
+} ddq_param_noise_cfg;
+/* Synchronises.  Enabling allocates theta~ and its split copies on first use,
+ * stores sigma in device memory, resets epoch and the move count to 0 and draws
+ * epoch 0; disabling frees nothing and restores the default launches exactly.
+ * DDQ_EINVAL (state unchanged): null cfg, enabled not 0 or 1, reserved != 0, or
+ * (enabling) a value out of range or NaN. */
+int ddq_set_param_noise(ddq_ctx* ctx, const ddq_param_noise_cfg* cfg);
+int ddq_get_param_noise(const ddq_ctx* ctx, ddq_param_noise_cfg* cfg);
+/* epoch += 1 and a fresh theta~ at the current device sigma (one launch).
+ * These three: DDQ_ESTATE while the feature is off. */
+int ddq_param_noise_resample_async(ddq_ctx* ctx);
+int ddq_param_noise_adapt_async(ddq_ctx* ctx);
+/* theta~ as the acting launches read it, n = ddq_num_params floats to the host
+ * (synchronises; for tests and tools). */
+int ddq_param_noise_params(ddq_ctx* ctx, float* dst, int64_t n);
 
 /* ---------------- acting path (no reference counterpart) ------------------- */
 /* Which convolution kernels the acting forward launches -- ddq_forward_q,

@@ -67,3 +67,16 @@ for k in ("conv3f", "conv3d", "conv2f", "conv2d"):
 for cw in (4, 6, 10, 12):
     RS, ra, rb = cfg(*confs["conv1f"], cw=cw)
     print("conv1 cw", cw, rb)
+# ---- param_noise.hip: the conv workgroups' transposed ds_read_b32 (64 lanes on 64 banks
+# at once): conflict-free iff the 64 word addresses of one read hit distinct banks
+def param_noise_reads():
+    conv2 = [(l >> 5) * 800 + (l & 3) * 200 + ((l >> 2) & 7) for l in range(64)]
+    conv3 = [(l & 7) * 72 + (l >> 3) for l in range(64)]
+    conv1 = [(l >> 2) * 7 + 2 * (l & 3) for l in range(28)]
+    for name, ad in (("conv2", conv2), ("conv3", conv3), ("conv1", conv1)):
+        print("param_noise", name, "lanes", len(ad), "banks", len({a % 64 for a in ad}))
+    # two conv1 channels a pass: the row stride would have to shift the bank set off itself
+    A = {a % 64 for a in conv1}
+    print("param_noise conv1 two-channel strides:",
+          [196 + p for p in range(0, 64, 4) if not A & {(a + 196 + p) % 64 for a in A}])
+param_noise_reads()
